@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- particle-updates/s of the RBPF-SLAM particle-update hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N = 1: run directly)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N = 1: run directly)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one accepted lidar scan of the reference's main loop (main.py:138-214) over all particles:
@@ -10,10 +10,14 @@ IMU propagation (robot.py:45-57), Robot.map_update for every particle (robot.py:
 reference's scan-match cadence (main.py:156-159) and last_scan refresh (main.py:167-168).
 
 Workload (BASELINE.json configs[2]): 4096 particles per GPU, 1081 beams over 270
-degrees, 0.05 m cells, synthetic `room16` world (data/fr101.log is not in the reference's tree).  configs[1]
-(1024 particles) and the north-star size (10 240) are measured in the same run and reported beside it.  Weak scaling:
+degrees, 0.05 m cells, synthetic `room16` world (data/fr101.log is not in the reference's tree).  Weak scaling:
 every rank holds 4096 particles; the per-particle weights are all-reduced over RCCL before the global resampling.
 Inputs (the scan log) are generated before the timed region; one scan (17 KB) is uploaded per step.
+
+A plain run sets up, warms up, times the steps and prints the headline.  --full adds what takes measurements of its
+own: per-kernel times and the roofline of the dominant kernel (timing events in the steps), configs[1] (1024
+particles) and the north-star size (10 240) reported beside the headline, the copy peak and the CPU baseline.
+--dump-outputs DIR writes the particle state after the last timed step (dump_outputs) as DIR/<name>.npy.
 
 Rank 0 prints ONE JSON line.
 """
@@ -46,8 +50,11 @@ def parse():
     ap.add_argument("--cell-size", type=float, default=0.05)
     ap.add_argument("--ndt", type=int, default=NDT_DEFAULT, choices=(0, 1),
                     help="second matcher stage (matchScanCustom.m:32-50, NDT refinement)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-target-run", action="store_true", help="skip the extra 1024- and 10 240-particle measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times, roofline, the 1024- and 10 240-particle runs, copy peak and CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-target-run", action="store_true", help="with --full: skip the extra 1024- and 10 240-particle measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the particle state after the last timed step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -202,6 +209,30 @@ def cpu_baseline(log, B, cell_size, seconds=12.0):
                                                     "loop structure: Robot._generate_sample_weight + moments + HybridMap.update)"}}
 
 
+DUMP_BYTES = 56 << 20         # --dump-outputs in all (at most 64 MB)
+
+
+def dump_outputs(e, out_dir, prefix=""):
+    """What a caller of the step holds after it: poses, covariances and weights of every particle, and the maps of a
+    fixed, seeded sample of particles - whole tiles (cells as float32, lattice order) while DUMP_BYTES allows."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"poses": e.poses(), "covs": e.covs(), "weights": e.weights()}
+    max_tiles = max(0, DUMP_BYTES - sum(a.nbytes for a in out.values())) // (4 * e.dim * e.dim)
+    cells, centres, owners = [], [], []
+    for p in np.random.Generator(np.random.PCG64(2024)).permutation(e.P):
+        for centre, c in e.tiles(int(p)):
+            if len(cells) == max_tiles:
+                break
+            cells.append(c.astype(np.float32)); centres.append(centre); owners.append(p)
+        if len(cells) == max_tiles:
+            break
+    out["map_cells"] = np.stack(cells) if cells else np.zeros((0, e.dim, e.dim), np.float32)
+    out["map_tile_centres"] = np.asarray(centres, dtype=np.float64).reshape(-1, 2)
+    out["map_tile_particles"] = np.asarray(owners, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def _finite(x):
     """JSON has no NaN/Infinity: non-finite floats become null."""
     if isinstance(x, dict):
@@ -231,7 +262,7 @@ def main():
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     from thesis_amd.datasets import synthetic
-    n_scans = args.steps + args.warmup + 2 + 20            # + the untimed per-kernel pass
+    n_scans = args.steps + args.warmup + 2 + 20            # + --full's untimed per-kernel pass (made in every run: same inputs)
     log = synthetic.make_log(n_scans, args.beams, period=PERIOD_S)
 
     shard = None
@@ -256,24 +287,28 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Timing events cost a few microseconds of stream time each.  The warm-up steps bracket every kernel family (that
-    # is where the per-kernel table comes from and how the dominant kernel is found); the timed region brackets only
-    # the dominant one, whose live duration the roofline needs.
+    # Timing events cost a few microseconds of stream time each; a plain run records none.  With --full the warm-up
+    # steps bracket every kernel family (that is where the per-kernel table comes from and how the dominant kernel is
+    # found); the timed region brackets only the dominant one, whose live duration the roofline needs.
     FAMILIES = ("raycast", "weight", "resample", "match", "ndt")
     assert set(KERNEL_NAMES) == set(FAMILIES), "every timed kernel family needs its dominant kernel's symbol"
-    run.e.set_profiling(True)
+    if args.full:
+        run.e.set_profiling(True)
     for _ in range(args.warmup):
         run.step()
-    warm_ms = {k: run.e.kernel_ms(k) for k in FAMILIES} if args.warmup else {}
-    warm_mean = {k: (float(v[1:].mean()) if len(v) > 1 else float(v.mean()) if len(v) else 0.0) for k, v in warm_ms.items()}
-    dominant = max(FAMILIES, key=lambda k: warm_mean.get(k, 0.0)) if args.warmup else None
-    run.e.set_profiling([dominant] if dominant else True)
+    if args.full:
+        warm_ms = {k: run.e.kernel_ms(k) for k in FAMILIES} if args.warmup else {}
+        warm_mean = {k: (float(v[1:].mean()) if len(v) > 1 else float(v.mean()) if len(v) else 0.0) for k, v in warm_ms.items()}
+        dominant = max(FAMILIES, key=lambda k: warm_mean.get(k, 0.0)) if args.warmup else None
+        run.e.set_profiling([dominant] if dominant else True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         run.step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(run.e, args.dump_outputs, f"rank{rank}_" if world > 1 else "")
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -293,61 +328,6 @@ def main():
 
     P_total = args.particles * world
     value = P_total * args.steps / elapsed
-    # ---- roofline of the dominant kernel, HIP events recorded inside the timed region ------------------
-    kms = {k: run.e.kernel_ms(k) for k in FAMILIES}
-    c = run.e.counters()
-    if dominant is not None and dist is None:
-        # the other kernels' durations: twenty more steps, untimed, with every family bracketed
-        run.e.set_profiling(True)
-        for _ in range(min(20, len(run.ranges) - run.frame - 2)):
-            run.step()
-        post = {k: run.e.kernel_ms(k) for k in FAMILIES}
-        warm_mean = {k: (float(v.mean()) if len(v) else warm_mean.get(k, 0.0)) for k, v in post.items()}
-    mean_ms = {k: (float(v.mean()) if len(v) else warm_mean.get(k, 0.0)) for k, v in kms.items()}
-    n_upd = max(1, args.steps)
-    W_per_particle = c["cells_written"] / (n_upd * args.particles)          # |W|, unique cells written per particle-update
-    cells_per_particle = c["ray_cells_visited"] / (n_upd * args.particles)
-    if dominant is None:
-        dominant = max(FAMILIES, key=lambda k: mean_ms[k])
-    # algorithmic bytes with 4-byte cells.  Per particle-update:
-    #   ray-cast kernel   4|W| read + 4|W| write
-    #   weighting kernel  4|R_w|, R_w = cells under the K*B sample endpoints (<= K*B, ~B distinct)
-    #   match kernel      4 * region cells (the occupancy region staged once per particle)
-    alg_bytes = {"raycast": 8.0 * W_per_particle, "weight": 4.0 * args.beams * 2,
-                 "match": 4.0 * 480 * 480, "ndt": 4.0 * 480 * 480, "resample": 0.0}
-    if c["resample_copies"]:
-        alg_bytes["resample"] = 4.0 * c["bytes_copied"] / (n_upd * args.particles)
-    ach = alg_bytes[dominant] * args.particles / (mean_ms[dominant] * 1e-3) / 1e9 if mean_ms[dominant] > 0 else 0.0
-    traffic = pmc_traffic(dominant, args.particles)
-    # the whole step against the same peak: SURVEY 8(d)'s bytes per particle-update (4-byte cells: cells read by matcher,
-    # weighting and ray-cast, cells written, 2 x 104 B of state) over the step time
-    bytes_pu = 8.0 * W_per_particle + 4.0 * args.beams * 2 + 208.0
-    step_ach = bytes_pu * args.particles * world / (elapsed / args.steps) / 1e9
-    n_fb = max(1, args.steps) * args.particles
-    roofline = {"bound": "hbm", "kernel": dominant, "kernel_symbol": KERNEL_NAMES.get(dominant), "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
-                # the same kernel in the bytes it actually moves (int8 cells; PMC FETCH/WRITE passes, profiles/)
-                "frac_stored_bytes": (traffic / (mean_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and mean_ms[dominant] > 0 else None,
-                "step_frac": step_ach / (HBM_PEAK_GBS * world),
-                "step_bytes_per_particle_update": bytes_pu,
-                "window_fallbacks_per_particle_step": c["window_fallbacks"] / n_fb,
-                "fast_kernel_give_backs_per_particle_step": (int(c["fallback_geometry"]) + int(c["fallback_bound"]) + int(c["fallback_tables"])) / n_fb,
-                "global_index_kernel_windows_per_particle_step": c["map_windows"] / n_fb,
-                "algorithmic_bytes_per_particle_update": alg_bytes[dominant],
-                "cell_bytes_algorithmic": 4, "cell_bytes_stored": 1,
-                "achieved_stored_bytes_GBs": ach / 4.0,
-                "kernel_ms_mean": mean_ms,
-                "kernel_ms_source": f"{dominant}: HIP events in the timed region (raycast: the events ride on the first map kernel's dispatch "
-                                    "and take its own start and end); the others: HIP events round the family's launches in untimed steps "
-                                    "(after the timed region on one GPU, the warm-up steps otherwise)",
-                "slow_cells_per_step": c["slow_cells"] / n_upd,
-                "ndt": {"enabled": bool(args.ndt), "runs_per_step": c["ndt_runs"] / n_upd,
-                        "evaluations_per_run": c["ndt_evaluations"] / max(1, c["ndt_runs"]),
-                        "accepted_fraction": c["ndt_accepted"] / max(1, c["ndt_runs"])},
-                "match_shared_per_step": c["match_shared"] / n_upd,       # exact duplicates that took their representative's match
-                "window_fallback_particles_per_step": c["window_fallbacks"] / n_upd,
-                "unique_cells_written_per_particle": W_per_particle,
-                "ray_cells_per_particle": cells_per_particle}
     out = {"metric": "particle-updates/sec (particles x scans/s) @1081 beams", "value": value,
            "unit": "particle-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -360,8 +340,64 @@ def main():
                                   + ("both matcher stages, " if args.ndt else "grid matcher stage only, ") +
                                   "resample every step",
                       "particles_per_gpu": args.particles, "beams": args.beams, "cell_size": args.cell_size,
-                      "parallelism": f"particles sharded x{world}"},
-           "roofline": roofline}
+                      "parallelism": f"particles sharded x{world}"}}
+    if args.full:
+        # ---- roofline of the dominant kernel, HIP events recorded inside the timed region ------------------
+        kms = {k: run.e.kernel_ms(k) for k in FAMILIES}
+        c = run.e.counters()
+        if dominant is not None and dist is None:
+            # the other kernels' durations: twenty more steps, untimed, with every family bracketed
+            run.e.set_profiling(True)
+            for _ in range(min(20, len(run.ranges) - run.frame - 2)):
+                run.step()
+            post = {k: run.e.kernel_ms(k) for k in FAMILIES}
+            warm_mean = {k: (float(v.mean()) if len(v) else warm_mean.get(k, 0.0)) for k, v in post.items()}
+        mean_ms = {k: (float(v.mean()) if len(v) else warm_mean.get(k, 0.0)) for k, v in kms.items()}
+        n_upd = max(1, args.steps)
+        W_per_particle = c["cells_written"] / (n_upd * args.particles)          # |W|, unique cells written per particle-update
+        cells_per_particle = c["ray_cells_visited"] / (n_upd * args.particles)
+        if dominant is None:
+            dominant = max(FAMILIES, key=lambda k: mean_ms[k])
+        # algorithmic bytes with 4-byte cells.  Per particle-update:
+        #   ray-cast kernel   4|W| read + 4|W| write
+        #   weighting kernel  4|R_w|, R_w = cells under the K*B sample endpoints (<= K*B, ~B distinct)
+        #   match kernel      4 * region cells (the occupancy region staged once per particle)
+        alg_bytes = {"raycast": 8.0 * W_per_particle, "weight": 4.0 * args.beams * 2,
+                     "match": 4.0 * 480 * 480, "ndt": 4.0 * 480 * 480, "resample": 0.0}
+        if c["resample_copies"]:
+            alg_bytes["resample"] = 4.0 * c["bytes_copied"] / (n_upd * args.particles)
+        ach = alg_bytes[dominant] * args.particles / (mean_ms[dominant] * 1e-3) / 1e9 if mean_ms[dominant] > 0 else 0.0
+        traffic = pmc_traffic(dominant, args.particles)
+        # the whole step against the same peak: SURVEY 8(d)'s bytes per particle-update (4-byte cells: cells read by matcher,
+        # weighting and ray-cast, cells written, 2 x 104 B of state) over the step time
+        bytes_pu = 8.0 * W_per_particle + 4.0 * args.beams * 2 + 208.0
+        step_ach = bytes_pu * args.particles * world / (elapsed / args.steps) / 1e9
+        n_fb = max(1, args.steps) * args.particles
+        roofline = {"bound": "hbm", "kernel": dominant, "kernel_symbol": KERNEL_NAMES.get(dominant), "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
+                    # the same kernel in the bytes it actually moves (int8 cells; PMC FETCH/WRITE passes, profiles/)
+                    "frac_stored_bytes": (traffic / (mean_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic and mean_ms[dominant] > 0 else None,
+                    "step_frac": step_ach / (HBM_PEAK_GBS * world),
+                    "step_bytes_per_particle_update": bytes_pu,
+                    "window_fallbacks_per_particle_step": c["window_fallbacks"] / n_fb,
+                    "fast_kernel_give_backs_per_particle_step": (int(c["fallback_geometry"]) + int(c["fallback_bound"]) + int(c["fallback_tables"])) / n_fb,
+                    "global_index_kernel_windows_per_particle_step": c["map_windows"] / n_fb,
+                    "algorithmic_bytes_per_particle_update": alg_bytes[dominant],
+                    "cell_bytes_algorithmic": 4, "cell_bytes_stored": 1,
+                    "achieved_stored_bytes_GBs": ach / 4.0,
+                    "kernel_ms_mean": mean_ms,
+                    "kernel_ms_source": f"{dominant}: HIP events in the timed region (raycast: the events ride on the first map kernel's dispatch "
+                                        "and take its own start and end); the others: HIP events round the family's launches in untimed steps "
+                                        "(after the timed region on one GPU, the warm-up steps otherwise)",
+                    "slow_cells_per_step": c["slow_cells"] / n_upd,
+                    "ndt": {"enabled": bool(args.ndt), "runs_per_step": c["ndt_runs"] / n_upd,
+                            "evaluations_per_run": c["ndt_evaluations"] / max(1, c["ndt_runs"]),
+                            "accepted_fraction": c["ndt_accepted"] / max(1, c["ndt_runs"])},
+                    "match_shared_per_step": c["match_shared"] / n_upd,       # exact duplicates that took their representative's match
+                    "window_fallback_particles_per_step": c["window_fallbacks"] / n_upd,
+                    "unique_cells_written_per_particle": W_per_particle,
+                    "ray_cells_per_particle": cells_per_particle}
+        out["roofline"] = roofline
     if dist is not None:
         out["collective"] = {"weights": "one RCCL all-reduce of %d float64 per step" % P_total,
                              "migrated_particles_per_step": float(moved[0].item()) / (2 * max(1, args.steps + args.warmup)),
@@ -369,38 +405,39 @@ def main():
     if run.shard is not None:
         run.shard.close()
     run.e.close()
-    if world == 1:
-        roofline["peak_measured_copy"] = copy_peak_gbs(torch)        # after the timed region, on an idle device
-        roofline["frac_of_measured_copy"] = ach / roofline["peak_measured_copy"]
-    if not args.no_target_run and world == 1:
-        # the same step at configs[1] (1024 particles) and at the north-star size (>= 10k particles x 1081 beams on one
-        # GPU): reported beside `value`, not in it
-        for name, Pn in (("config1_1024", 1024), ("target_10k", 10240)):
-            if Pn == args.particles:
-                continue
-            big = Runner(Pn, args.beams, args.cell_size, log, ndt=args.ndt)
-            for _ in range(3):
-                big.step()
-            big.e.set_profiling(True)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            nb = min(args.steps, 40)
-            for _ in range(nb):
-                big.step()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            km = {k: (float(x.mean()) if len(x) else 0.0)
-                  for k, x in ((k, big.e.kernel_ms(k)) for k in ("raycast", "weight", "resample", "match", "ndt"))}
-            cb = big.e.counters()
-            Wb = cb["cells_written"] / (nb * Pn)
-            out[name] = {"particles": Pn, "value": Pn * nb / dt, "ms_per_step": 1e3 * dt / nb, "steps": nb,
-                         "kernel_ms_mean": km,
-                         "raycast_frac_of_hbm_peak": 8.0 * Wb * Pn / (km["raycast"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "step_frac": (8.0 * Wb + 4.0 * args.beams * 2 + 208.0) * Pn / (dt / nb) / 1e9 / HBM_PEAK_GBS,
-                         "window_fallbacks_per_particle_step": cb["window_fallbacks"] / (nb * Pn)}
-            big.e.close()
-    if not args.no_cpu_baseline and world == 1:
-        out["cpu_baseline"] = cpu_baseline(log, args.beams, args.cell_size)
+    if args.full:
+        if world == 1:
+            roofline["peak_measured_copy"] = copy_peak_gbs(torch)        # after the timed region, on an idle device
+            roofline["frac_of_measured_copy"] = ach / roofline["peak_measured_copy"]
+        if not args.no_target_run and world == 1:
+            # the same step at configs[1] (1024 particles) and at the north-star size (>= 10k particles x 1081 beams on one
+            # GPU): reported beside `value`, not in it
+            for name, Pn in (("config1_1024", 1024), ("target_10k", 10240)):
+                if Pn == args.particles:
+                    continue
+                big = Runner(Pn, args.beams, args.cell_size, log, ndt=args.ndt)
+                for _ in range(3):
+                    big.step()
+                big.e.set_profiling(True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                nb = min(args.steps, 40)
+                for _ in range(nb):
+                    big.step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                km = {k: (float(x.mean()) if len(x) else 0.0)
+                      for k, x in ((k, big.e.kernel_ms(k)) for k in ("raycast", "weight", "resample", "match", "ndt"))}
+                cb = big.e.counters()
+                Wb = cb["cells_written"] / (nb * Pn)
+                out[name] = {"particles": Pn, "value": Pn * nb / dt, "ms_per_step": 1e3 * dt / nb, "steps": nb,
+                             "kernel_ms_mean": km,
+                             "raycast_frac_of_hbm_peak": 8.0 * Wb * Pn / (km["raycast"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "step_frac": (8.0 * Wb + 4.0 * args.beams * 2 + 208.0) * Pn / (dt / nb) / 1e9 / HBM_PEAK_GBS,
+                             "window_fallbacks_per_particle_step": cb["window_fallbacks"] / (nb * Pn)}
+                big.e.close()
+        if not args.no_cpu_baseline and world == 1:
+            out["cpu_baseline"] = cpu_baseline(log, args.beams, args.cell_size)
     sys.stdout.flush()
     os.write(real_stdout, (json.dumps(_finite(out), allow_nan=False) + "\n").encode())
     if dist is not None:

@@ -16,6 +16,7 @@ Vector sets:
   G11 dataset adapters (what the Default* / Intel* loaders hand to main.py)
   G12 the Freid101-family adapters on data/orebro.log (OberoIMUData as is; OberoLidarData with its beam count set to
       the file's 181 - as committed it says 360 and cannot parse the file)
+  data  data fixtures G11 is checked on: orebro_raw.log.gz, csail_correct.log.gz, default_mat/*.mat (cut down)
 """
 import contextlib
 import io
@@ -481,8 +482,39 @@ def g12():
     save("G12_obero_adapters", **out)
 
 
+def data_fixtures():
+    """The data files test_host_logic reads G11 against: the CARMEN logs gzip-compressed, and the default dataset's
+    lidar.mat / imu.mat / speed.mat cut down to the records G11 samples (the first 50 and last 5 scans; the first 1000
+    IMU and speed samples, which the adapters' baselines average, and the last 5).  Every field keeps its name, dtype and
+    layout; the cut arrays are the long axis of Scans / times / DATAf / speeds."""
+    import gzip
+    import shutil
+    from scipy.io import loadmat, savemat
+    for name in ("orebro_raw.log", "csail_correct.log"):
+        path = os.path.join(HERE, name + ".gz")
+        with open(os.path.join(REF, "data", name), "rb") as src, open(path, "wb") as raw, \
+                gzip.GzipFile(fileobj=raw, mode="wb", compresslevel=9, mtime=0) as dst:
+            shutil.copyfileobj(src, dst)
+        print("wrote", os.path.relpath(path, REPO))
+    out_dir = os.path.join(HERE, "default_mat")
+    os.makedirs(out_dir, exist_ok=True)
+    for fname, struct, long_fields, head in (("lidar", "dataL", ("Scans", "times"), 50),
+                                             ("imu", "IMU", ("times", "DATAf"), 1000),
+                                             ("speed", "Vel", ("times", "speeds"), 1000)):
+        s = loadmat(os.path.join(REF, "data", fname), squeeze_me=False)[struct]
+        fields = {}
+        for f in s.dtype.names:
+            a = np.asarray(s[f][0][0])
+            if f in long_fields:
+                a = np.concatenate([a[:, :head], a[:, -5:]], axis=1)
+            fields[f] = a
+        path = os.path.join(out_dir, fname + ".mat")
+        savemat(path, {struct: fields}, do_compression=True)
+        print("wrote", os.path.relpath(path, REPO), {k: v.shape for k, v in fields.items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g345", "g69", "g7", "g8", "g10", "g11", "g12"]
+    which = sys.argv[1:] or ["g1", "g2", "g345", "g69", "g7", "g8", "g10", "g11", "g12", "data"]
     if "g1" in which: g1()
     if "g2" in which: g2()
     if "g345" in which: g3_g4_g5()
@@ -492,3 +524,4 @@ if __name__ == "__main__":
     if "g10" in which: g10()
     if "g11" in which: g11()
     if "g12" in which: g12()
+    if "data" in which: data_fixtures()

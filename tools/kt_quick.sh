@@ -6,7 +6,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/kt_quick
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $ROOT/bench.py --no-target-run --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/kt.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $ROOT/bench.py --full --no-target-run --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/kt.log
 F=$(find $OUT/kt -name "*kernel_stats.csv" | head -1)
 if [ -z "$F" ]; then echo "no kernel_stats.csv"; tail -5 $OUT/kt.log; exit 1; fi
 python3 - "$F" <<'PY'

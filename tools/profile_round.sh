@@ -9,8 +9,8 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $ROOT/bench.py --no-target-run --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kt.log
+python3 $ROOT/bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $ROOT/bench.py --full --no-target-run --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/kt.log
 for P in 4096 1024; do
   for C in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_${P}_$C -o pmc -- python3 $ROOT/tools/pmc_run.py $P > /dev/null 2> $OUT/pmc_${P}_$C.log
