@@ -28,28 +28,15 @@
 
 namespace rbpf {
 
-#ifdef RBPF_STAMPS
-#define STAMP(k) do { if (tid == 0) { long long t_ = clock64(); st_acc[k] += t_ - st_prev; st_prev = t_; } } while (0)
-#ifdef EV_BARRIER_WAITS      // diagnostic: cycles every wave spends at the workgroup's barriers (printed by workgroup 0)
+#if defined(RBPF_STAMPS) && defined(EV_BARRIER_WAITS)   // diagnostic: cycles every wave spends at the workgroup's barriers (printed by workgroup 0)
 #undef BAR_LDS
 #define BAR_LDS() do { const long long t0_ = clock64(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); { const long long d_ = clock64() - t0_; bar_wait += d_; if (bar_n < 12) bar_w[bar_n] = (int)d_; } ++bar_n; } while (0)
 #endif
-#else
-#define STAMP(k) do { } while (0)
-#endif
 
 static const int EB = 1024;                    // threads per particle
-static const int NEAR_R = 16;                  // ray steps j < NEAR_R are counted in the 16-bit block round the start cell
-static const int LCH = 16;                     // steps per chunk of the walk beyond it
-static const int NEAR_W = 2 * NEAR_R + 1;
-static const int NBIN = 256;                   // slope buckets per direction class (counter bound)
-static const int NB_WIN = NBIN / NEAR_R + 2;   // buckets that can hold the rays through one cell beyond the 16-bit block
 static const int HIT_BOUND = 62;               // per direction class; two classes can meet in a cell, +1 for the flag's count bit: 125 < 128
-static const int MAXLEV = 63;                  // whole 16-step chunks per ray (reach < 1000 cells)
 static const int EVCAP = 3072;                 // passes over flagged cells kept per particle (more: exact replay of every flagged cell)
 static const int NPAIR = 3;                    // pairs (beam, e) per thread kept in registers: 3 * EB pairs = 1536 beams
-
-__host__ __device__ inline int ev_al16(int x) { return (x + 15) & ~15; }
 
 struct EvGeom {
     int fanw, bpad, ncell, T, logT, E;
@@ -63,18 +50,18 @@ __host__ __device__ inline EvGeom ev_geom(int B, int reach) {
     g.fanw = (2 * reach + 8 + 7) & ~7;
     g.bpad = (B + 3) & ~3;
     int o = 0;
-    g.o_mini = o;  o += ev_al16(((NEAR_W * NEAR_W + 1) / 2) * 4);
-    g.o_fs = o;    o += ev_al16(g.bpad * 4);
-    g.o_end = o;   o += ev_al16(g.bpad * 4);
-    g.o_nE = o;    o += ev_al16(g.bpad * 2);
-    g.o_perm = o;  o += ev_al16(g.bpad * 2);
-    g.o_kl = o;    o += ev_al16(g.bpad * 2);
-    g.o_info = o;  o += ev_al16(g.bpad);
-    g.o_ux = o;    o += ev_al16(g.fanw * 2);
-    g.o_uy = o;    o += ev_al16(g.fanw * 2);
-    g.o_gxb = o;   o += ev_al16(g.fanw);
-    g.o_gyb = o;   o += ev_al16(g.fanw);
-    g.o_gym = o;   o += ev_al16(g.fanw + 16);
+    g.o_mini = o;  o += al16(((NEAR_W * NEAR_W + 1) / 2) * 4);
+    g.o_fs = o;    o += al16(g.bpad * 4);
+    g.o_end = o;   o += al16(g.bpad * 4);
+    g.o_nE = o;    o += al16(g.bpad * 2);
+    g.o_perm = o;  o += al16(g.bpad * 2);
+    g.o_kl = o;    o += al16(g.bpad * 2);
+    g.o_info = o;  o += al16(g.bpad);
+    g.o_ux = o;    o += al16(g.fanw * 2);
+    g.o_uy = o;    o += al16(g.fanw * 2);
+    g.o_gxb = o;   o += al16(g.fanw);
+    g.o_gyb = o;   o += al16(g.fanw);
+    g.o_gym = o;   o += al16(g.fanw + 16);
     g.o_evl = o;   o += EVCAP * 4;
     g.o_cnt = o;
     const int avail = 160 * 1024 - 2560 - o - 64;      // 2.5 KB for the kernel's static LDS
@@ -91,31 +78,17 @@ __host__ __device__ inline EvGeom ev_geom(int B, int reach) {
     g.p_offs = q;  q += T * 2;                         // passes after the cell's last event
     g.p_oldv = q;  q += T;
     g.p_rlist = q; q += T * 2;
-    g.p_evl = q;   q += ev_al16(g.E * 2) * 2;          // next pair of the list; the lists laid out for the fold
-    g.p_ic = q;    q += ev_al16(g.E * 2);              // passes right before the pair's event
+    g.p_evl = q;   q += al16(g.E * 2) * 2;          // next pair of the list; the lists laid out for the fold
+    g.p_ic = q;    q += al16(g.E * 2);              // passes right before the pair's event
     g.p_bytes = q;
     g.ok = g.ncell >= 24576 && g.p_bytes <= g.ncell && 2 * 8 * NBIN * 2 <= g.ncell && 2 * B <= NPAIR * EB && reach >= NEAR_R + 4 && reach < 1000;
     return g;
 }
 
 bool map_update_ev_available(const DevView& v) {
-    const int sat = (v.cc.vmax - v.cc.vmin + (-v.cc.emp) - 1) / (-v.cc.emp);
     const EvGeom g = ev_geom(v.B, v.reach);
     const int gpt = (v.dim + 31) >> 5;
-    return g.ok && v.dim % 8 == 0 && 3 * gpt <= 192 && v.L * v.L <= 49 && v.cc.emp < 0 && sat <= 31 &&
-           v.cc.vmax - v.cc.vmin <= 127 && v.cc.vmin <= 0 && v.cc.vmax >= 0 && v.cc.vmin >= -127 && sat * -v.cc.emp <= 127 &&
-           v.cc.thr >= v.cc.vmin && v.cc.thr < v.cc.vmax;
-}
-
-// int(x / cell_size) (hybridmap.py:102,106) without the division when the product with the reciprocal is safely inside
-// a cell: x / c and x * (1 / c) differ by a few units in the last place, so they truncate alike unless an integer lies
-// within 1e-9 of the product; the division decides the rest.
-__device__ __forceinline__ int ev_cell_of(double x, double cs, double inv_cs) {
-    const double q = x * inv_cs;
-    const double t = __builtin_trunc(q);
-    const double f = q - t, af = f < 0 ? -f : f;
-    if (af > 1e-9 && af < 1.0 - 1e-9) return (int)t;
-    return trunc_to_int(x / cs);
+    return g.ok && lattice_fits_byte_fields(v.cc) && v.dim % 8 == 0 && 3 * gpt <= 192 && v.L * v.L <= 49;
 }
 
 // 32-bit fixed-point slope: ceil(dmin * 2^32 / dmaj), the diagonal clamped to 2^32 - 1.  With it
@@ -136,46 +109,12 @@ __device__ __forceinline__ int ev_minor(uint32_t fs, int j) {
     return (int)(((unsigned long long)fs * (unsigned)j + 0x80000000ull) >> 32);
 }
 
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ int ev_lds_addr(const void* p) { return (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char*)p; }
 __device__ __forceinline__ uint32_t ev_lds_add_rtn(int byte_addr, uint32_t val) {
     return __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(uint32_t)byte_addr, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// byte-wise min(x, sat) of four 7-bit counts
-__device__ __forceinline__ uint32_t ev_min4(uint32_t n7, uint32_t satb, uint32_t sadd) {
-    const uint32_t ge = (n7 + sadd) & 0x80808080u;
-    const uint32_t gem = ge | (ge - (ge >> 7));
-    return (satb & gem) | (n7 & ~gem);
-}
-
-// One word of four cells through the write-back's arithmetic (gridmap.py:97-101, n times, byte-wise): returns the new word;
-// `touched` / `occ` get the word's four bits (field not zero / cell > threshold).
-struct EvWb { uint32_t kb1, oadd, satb, sadd; int eabs; };
-__device__ __forceinline__ uint32_t ev_wb_word(const EvWb& k, uint32_t pre, uint32_t n7, uint32_t& touched4, uint32_t& occ4) {
-    const uint32_t Ob = (pre ^ 0x80808080u) - k.kb1;                          // cells biased to [0, vmax - vmin]
-    const uint32_t m = ev_min4(n7, k.satb, k.sadd);                           // min(n, sat)
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    const uint32_t dec = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, m) * (us2)(unsigned short)k.eabs);   // byte-wise: sat * |emp| < 128, no carries
-    const uint32_t T1 = (Ob | 0x80808080u) - dec;
-    const uint32_t pos = T1 & 0x80808080u;                                    // O - dec >= 0
-    const uint32_t R = T1 & 0x7F7F7F7Fu & (pos | (pos - (pos >> 7)));
-    const uint32_t nz = (n7 + 0x7F7F7F7Fu) & 0x80808080u;                     // fields that are not zero
-    touched4 = __builtin_amdgcn_udot4(nz >> 7, 0x08040201u, 0u, false);
-    occ4 = __builtin_amdgcn_udot4(((R + k.oadd) & 0x80808080u) >> 7, 0x08040201u, 0u, false);   // cell > thr
-    return (R + k.kb1) ^ 0x80808080u;
-}
-
 // open addressing, linear probing, keys never ~0
-__device__ __forceinline__ int ev_hash_insert(uint32_t* keys, int T, int logT, uint32_t sc) {
-    uint32_t h = (sc * 2654435761u) >> (32 - logT);
-    for (;;) {
-        const uint32_t old = atomicCAS(&keys[h], 0xFFFFFFFFu, sc);
-        if (old == 0xFFFFFFFFu || old == sc) return (int)h;
-        h = (h + 1) & (uint32_t)(T - 1);                                         // (the table has more slots than there can be keys)
-    }
-}
-__device__ __forceinline__ int ev_hash_insert2(uint32_t* keys, int T, int logT, uint32_t sc, bool& created) {
+__device__ __forceinline__ int ev_hash_insert(uint32_t* keys, int T, int logT, uint32_t sc, bool& created) {
     uint32_t h = (sc * 2654435761u) >> (32 - logT);
     for (;;) {
         const uint32_t old = atomicCAS(&keys[h], 0xFFFFFFFFu, sc);
@@ -195,9 +134,6 @@ __device__ __forceinline__ int ev_hash_find(const uint32_t* keys, int T, int log
     return -1;
 }
 
-// hand the particle to the window kernel (uniform over the workgroup; nothing has been written to the map yet);
-// reason codes: 1 geometry / index map, 2 counter bound
-#define EV_GIVE_BACK(reason) do { if (tid == 0) { v.mu_fallback[p] = (reason); atomicAdd(&v.stats[(reason) == 1 ? ST_FALLBACK_REASONS : ST_FB_BOUND], 1ull); } return; } while (0)
 
 __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -230,10 +166,9 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     __shared__ uint8_t s_ggf[192];                    // per (tile column, 32-column group): a glitched column among its 33
 
     const int LL = v.L * v.L;
-    const int KW = (v.dim + WIN - 1) / WIN;
     int32_t* tab = v.tile_tab + (size_t)v.slot[p] * LL;
-#ifdef RBPF_STAMPS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = clock64();
+    STAMP_DECL;
+#if defined(RBPF_STAMPS) && defined(EV_BARRIER_WAITS)
     long long bar_wait = 0; int bar_n = 0; const long long t_begin = clock64(); int bar_w[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     // =============================================== setup ===============================================
@@ -243,31 +178,10 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     const double pre_x1 = pb1 < v.B ? v.bx[pb1] : 0.0, pre_y1 = pb1 < v.B ? v.by[pb1] : 0.0, pre_s1 = pb1 < v.B ? v.bscale[pb1] : 0.0;
     const int pre_f0 = pb0 < v.B ? v.bflags[pb0] : 0, pre_f1 = pb1 < v.B ? v.bflags[pb1] : 0;
     const double s_px = v.upd_pose[p], s_py = v.upd_pose[v.P + p];
-    if (wave == 0) {   // one wave takes the sine and cosine (a few hundred instructions); the others read them after the first barrier
-        double sn, cs_;
-        sincos(v.upd_pose[2 * v.P + p], &sn, &cs_);
-        if (lane == 0) { s_sincos[0] = sn; s_sincos[1] = cs_; }
-    }
-    const int x0 = UNI(trunc_to_int(s_px / v.cs)), y0 = UNI(trunc_to_int(s_py / v.cs));   // hybridmap.py:102
-    {
-        int lx, ly;                                                          // hybridmap.py:98-100
-        bool ok = tile_of_coord(s_px, v.tile_len, v.R, lx) && tile_of_coord(s_py, v.tile_len, v.R, ly);
-        if (ok) ok = tab[(lx + v.R) * v.L + (ly + v.R)] >= 0;
-        const bool in_lut = lut_valid_g(v, x0 - v.reach - 2) && lut_valid_g(v, x0 + v.reach + 2) &&
-                            lut_valid_g(v, y0 - v.reach - 2) && lut_valid_g(v, y0 + v.reach + 2);
-        if (ok && !in_lut) { if (tid == 0) atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }
-        if (tid == 0) v.mu_fallback[p] = 0;
-        if (!UNI(ok)) return;
-    }
-    // the index map over everything a ray can reach, with a margin of two columns (the sources of a storage cell are its
-    // own global index and the next one)
+    int x0, y0;
+    // (the LUT must cover the index map's margin here, only the rays' reach in the other kernels: which poses are RBPF_ERANGE depends on it)
+    if (!fan_preamble<EB>(v, tab, p, tid, s_px, s_py, v.reach + 2, G.fanw, s_sincos, ux, uy, x0, y0)) return;
     const int fxl = x0 - v.reach - 2, fyl = y0 - v.reach - 2, nfx = 2 * v.reach + 5;
-    for (int i = tid; i < G.fanw; i += EB) {
-        const int gxq = fxl + i, gyq = fyl + i;
-        const uint32_t ex = lut_valid_g(v, gxq) ? lut_at(v, gxq) : LUT_INVALID, ey = lut_valid_g(v, gyq) ? lut_at(v, gyq) : LUT_INVALID;
-        ux[i] = ex != LUT_INVALID ? (uint16_t)(lut_lat(ex) * v.dim + lut_cidx(ex)) : 0xFFFFu;
-        uy[i] = ey != LUT_INVALID ? (uint16_t)(lut_lat(ey) * v.dim + lut_cidx(ey)) : 0xFFFFu;
-    }
     uint16_t* const s_bins = reinterpret_cast<uint16_t*>(cnt);               // [8 NBIN] rays per (class, slope bucket) (the window is not in use yet)
     uint16_t* const s_far = s_bins + 8 * NBIN;                               // ... of the rays that reach the 8-bit fields
     if (tid == 0) {
@@ -289,56 +203,18 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     auto lat_x = [&](int g) { const int U = ux[g - fxl]; return a0 + (U >= (a0 + 1) * v.dim ? 1 : 0) - (U < a0 * v.dim ? 1 : 0); };   // (rays are shorter than a tile)
     auto lat_y = [&](int g) { const int U = uy[g - fyl]; return b0 + (U >= (b0 + 1) * v.dim ? 1 : 0) - (U < b0 * v.dim ? 1 : 0); };
     {
-        unsigned long long my_cells = 0;
-        int fx0 = x0, fx1 = x0, fy0 = y0, fy1 = y0;
-        const double inv_cs = 1.0 / v.cs;
+        FanBox fan = {x0, x0, y0, y0, 0ull};
         for (int b = tid; b < v.B; b += EB) {
             const double x = b == pb0 ? pre_x0 : b == pb1 ? pre_x1 : v.bx[b], y = b == pb0 ? pre_y0 : b == pb1 ? pre_y1 : v.by[b];
             const int bf = b == pb0 ? pre_f0 : b == pb1 ? pre_f1 : (int)v.bflags[b];
-            double gx = (s_c * x + (-s_s) * y) + s_px;                             // lidar.py:123
-            double gy = (s_s * x + s_c * y) + s_py;
-            int x1 = ev_cell_of(gx, v.cs, inv_cs), y1 = ev_cell_of(gy, v.cs, inv_cs);   // hybridmap.py:106
-            if (bf & BF_LONG) {                                                    // hybridmap.py:107-113
-                const double sc = b == pb0 ? pre_s0 : b == pb1 ? pre_s1 : v.bscale[b];
-                x1 = trunc_to_int((double)x0 + sc * (double)(x1 - x0));
-                y1 = trunc_to_int((double)y0 + sc * (double)(y1 - y0));
-            }
-            int ddx = x1 - x0, ddy = y1 - y0;
-            if (ddx < -v.reach || ddx > v.reach || ddy < -v.reach || ddy > v.reach) {
-                atomicCAS(v.err, 0, RBPF_ERANGE);
-                ddx = 0; ddy = -1; x1 = x0; y1 = y0 - 1;                           // degenerate: no points
-            }
-            Ray r = ray_make(x0, y0, x1, y1);
-            int info = 0, nE = 0;
+            auto scale = [&] { return b == pb0 ? pre_s0 : b == pb1 ? pre_s1 : v.bscale[b]; };
+            const BeamRay br = beam_ray(v, x, y, bf, scale, s_s, s_c, s_px, s_py, x0, y0, a0, b0, lat_x, lat_y, s_need, fan);
+            const Ray& r = br.r;
+            const int ddx = br.x1 - x0, ddy = br.y1 - y0, info = br.info;
+            int nE = 0;
             uint32_t fs = 0;
             if (r.n > 0) {
-                info = RI_VALID | ((bf & BF_LONG) ? 0 : RI_OCC);
-                my_cells += (unsigned long long)r.n;
-                fx0 = min(fx0, x1); fx1 = max(fx1, x1); fy0 = min(fy0, y1); fy1 = max(fy1, y1);
                 fs = ev_fix_slope(r.dmin, r.dmaj);
-                const int a1 = lat_x(x1), b1 = lat_y(y1);
-                if (r.n >= 2 && (info & RI_OCC)) {                                 // hybridmap.py:139-142
-                    const int jn = r.n - 2, mn = ev_minor(fs, jn);
-                    const int nx = r.steep ? x0 + r.sx * mn : x0 + r.sx * jn, ny = r.steep ? y0 + r.sy * jn : y0 + r.sy * mn;
-                    if (lat_x(nx) == a1 && lat_y(ny) == b1) info |= RI_NEAR;          // hybridmap.py:141 same tile as the end cell
-                    info |= ((nx - x1 + 1) & 3) << 3;
-                    info |= ((ny - y1 + 1) & 3) << 5;
-                }
-                // tiles entered by this ray (staircase start -> [corner] -> end)
-                s_need[a0 * v.L + b0] = 1;
-                if (a1 != a0 || b1 != b0) {
-                    s_need[a1 * v.L + b1] = 1;
-                    if (a1 != a0 && b1 != b0) {
-                        int gxb_ = r.sx > 0 ? v.gwin[a1 * (KW + 1)] : v.gwin[a0 * (KW + 1)] - 1;
-                        int gyb_ = r.sy > 0 ? v.gwin[b1 * (KW + 1)] : v.gwin[b0 * (KW + 1)] - 1;
-                        int ox = gxb_ - x0; ox = ox < 0 ? -ox : ox;
-                        int oy = gyb_ - y0; oy = oy < 0 ? -oy : oy;
-                        int jx = r.steep ? first_j_minor_ge(r, ox) : ox;
-                        int jy = r.steep ? oy : first_j_minor_ge(r, oy);
-                        if (jx < jy) s_need[a1 * v.L + b0] = 1;
-                        else if (jy < jx) s_need[a0 * v.L + b1] = 1;
-                    }
-                }
                 // steps the walk takes: all of them but the beam's own occupied step and the pass before its own nearby hit
                 nE = r.n - ((info & RI_OCC) ? 1 : 0) - ((info & RI_NEAR) ? 1 : 0);
                 const int cls = (r.steep ? 4 : 0) | (ddx > 0 ? 2 : 0) | (ddy > 0 ? 1 : 0);
@@ -354,46 +230,14 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
             r_info[b] = (uint8_t)info;
             r_kl[b] = (uint16_t)(1 | ((nE > NEAR_R ? (nE - NEAR_R) / LCH : 0) << 8));
         }
-        const int ws = wave_sum((int)my_cells);
-        fx0 = wave_min(fx0); fx1 = wave_max(fx1); fy0 = wave_min(fy0); fy1 = wave_max(fy1);
-        if (lane == 0) {
-            atomicAdd(&s_cells, (unsigned long long)ws);
-            atomicMin(&s_fan[0], fx0); atomicMax(&s_fan[1], fx1);
-            atomicMin(&s_fan[2], fy0); atomicMax(&s_fan[3], fy1);
-        }
+        fan_box_join(fan, lane, s_fan, &s_cells);
     }
     __syncthreads();
-    // ---- the window: the fan's bounding box in global cell indices; strips of storage rows if it does not fit ----
-    const int bxl = UNI(s_fan[0]), bxh = UNI(s_fan[1]), byl = UNI(s_fan[2]), byh = UNI(s_fan[3]);
-    // the reference's index formula over the fan (one column more on either side): U(g) = g + C - G(g) with G in {0, 1}
-    for (int i = tid; i < G.fanw; i += EB) {
-        const int dxg = (fxl + i + C) - (int)ux[i], dyg = (fyl + i + C) - (int)uy[i];
-        if (fxl + i >= bxl - 1 && fxl + i <= bxh + 1 && (unsigned)dxg > 1u) s_fb = 1;   // also: the LUT ends inside the fan
-        if (fyl + i >= byl - 1 && fyl + i <= byh + 1 && (unsigned)dyg > 1u) s_fb = 1;
-        gxb[i] = (uint8_t)(dxg & 1); gyb[i] = (uint8_t)(dyg & 1);
-    }
-    const int S_lo = UNI(ux[bxl - fxl]), S_hi = UNI(ux[bxh - fxl]);           // storage rows / columns the fan can write
-    const int T_lo = UNI(uy[byl - fyl]), T_hi = UNI(uy[byh - fyl]);
-    const int gy_base = (T_lo - C) & ~3;                                      // window column 0 (C is a multiple of 4)
-    int stride = (T_hi - C + 2 - gy_base + 3) & ~3;                           // columns gy_base .. T_hi - C + 1
-    if (((stride >> 2) & 1) == 0) stride += 4;                                // rows an odd number of banks apart
-    const int rows_cap = G.ncell / stride;                                    // global rows a window can hold
-    const int gpt = (v.dim + 31) >> 5;                                        // 32-cell groups per tile row (the last one may be partial)
-    const int bt_lo = T_lo / v.dim;
-    if (wave == 0) {   // levels: N_k = rays with at least k whole chunks (suffix sums over the wave: MAXLEV = 63)
-        const int k = lane;                                                    // lane 0 is unused (level 0 = the 16-bit block)
-        const int ck = k >= 1 ? s_lcnt[k] : 0;
-        int suf = ck;
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (lane + o < 64) suf += t; }
-        const int nwk = k >= 1 ? (suf + 63) >> 6 : 0;
-        int pre = nwk;                                                         // inclusive prefix of the levels' wave counts
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(pre, o, 64); if (lane >= o) pre += t; }
-        const unsigned long long live = __ballot(k >= 1 && suf > 0);
-        const int nlev = live ? 63 - __clzll((long long)live) : 0;
-        if (k >= 1) { s_lfill[k] = suf - ck; s_nk[k] = suf; s_lp[k] = pre - nwk; }
-        if (k == 63) s_lp[64] = pre;
-        if (k == 0) { s_nlev = nlev; s_nk[MAXLEV + 1] = 0; }
-    }
+    // ---- the window (rbpf_mapupdate.h: strips of storage rows if the fan does not fit) ----
+    const StripGeom sg = strip_geom<EB>(ux, uy, gxb, gyb, G.fanw, fxl, fyl, C, s_fan, &s_fb, G.ncell, tid);
+    const int S_lo = sg.S_lo, S_hi = sg.S_hi, T_lo = sg.T_lo, T_hi = sg.T_hi, gy_base = sg.gy_base, stride = sg.stride, rows_cap = sg.rows_cap;
+    const int gpt = (v.dim + 31) >> 5, ggf_base = T_lo / v.dim * gpt;        // 32-cell groups per tile row (the last one may be partial); s_ggf[0]'s group
+    if (wave == 0) level_sums(lane, s_lcnt, s_lfill, s_nk, s_lp, &s_nlev);
     {   // no 8-bit field can overflow: a cell at major distance j >= NEAR_R is hit, per direction class, only by rays
         // whose slope lies in a window of width 2^32 / j + 1, i.e. in at most NB_WIN consecutive buckets: bounded with all
         // rays of those buckets, or (the smaller of the two) with the rays long enough to reach an 8-bit field.
@@ -424,53 +268,16 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         const int nfull = (nE - NEAR_R) / LCH;
         if (nE > NEAR_R && nfull >= 1) perm[atomicAdd(&s_lfill[min(nfull, MAXLEV)], 1)] = (uint16_t)b;
     }
-    for (int lc = tid; lc < stride + 16 && lc < G.fanw + 16; lc += EB) {       // column glitch mask in window coordinates
-        const int i = lc + gy_base - fyl;
-        const bool gl = i >= 0 && i < nfx && gyb[i];
-        gym[lc] = gl ? 0xFFu : 0u;
-        if (gl) {   // the write-back's groups that see this column: its own and, for a group's first four columns, the one before
-            const int sc = lc + gy_base + C, bt = sc / v.dim, t = sc - bt * v.dim, gt = t >> 5;
-            const int idx = (bt - bt_lo) * gpt + gt;
-            if ((unsigned)idx < 192u) s_ggf[idx] = 1;
-            if ((t & 31) < 4 && (unsigned)(idx - 1) < 192u) s_ggf[idx - 1] = 1;   // (gt = 0: the last group of the tile before)
-        }
-    }
+    glitch_mask<EB>(gyb, gym, s_ggf, ggf_base, 192, sg, G.fanw, fyl, nfx, C, v.dim, gpt, tid);
     __syncthreads();
-    if (UNI(s_fb) || rows_cap < 8) { EV_GIVE_BACK(1); }
-    if (UNI(s_exact)) { EV_GIVE_BACK(2); }
-    if (tid < LL && s_need[tid] && s_tab[tid] < 0) {                          // allocate missing tiles (kept zero-filled)
-        int idx = atomicSub(v.free_top, 1) - 1;
-        if (idx < 0) {
-            atomicAdd(v.free_top, 1);
-            atomicCAS(v.err, 0, RBPF_ENOMEM);
-        } else {
-            int t = v.free_stack[idx];
-            s_tab[tid] = t;                                                    // (a new tile's cells are zero: an old value read through either state of the table is 0)
-            tab[tid] = t;
-            v.tile_bbox[4 * t + 0] = INT_MAX; v.tile_bbox[4 * t + 1] = -1;
-            v.tile_bbox[4 * t + 2] = INT_MAX; v.tile_bbox[4 * t + 3] = -1;
-        }
-    }
+    if (UNI(s_fb) || rows_cap < 8) { GIVE_BACK(1); }
+    if (UNI(s_exact)) { GIVE_BACK(2); }
+    alloc_missing_tiles(v, tab, s_need, s_tab, tid);
     STAMP(1);
 
-    // the storage cell (U_x << 16 | U_y) flagged by pair (beam, e): the beam's end cell (e = 0) or the cell before it (e = 1,
-    // only when it lies in the end cell's tile); ~0 = none
-    auto pair_cell = [&](int pr) -> uint32_t {
-        const int b = pr >> 1, info = r_info[b];
-        if ((info & (RI_VALID | RI_OCC)) != (RI_VALID | RI_OCC) || ((pr & 1) && !(info & RI_NEAR))) return 0xFFFFFFFFu;
-        const int32_t re = r_end[b];
-        int x1 = x0 + (int)(int16_t)(re & 0xFFFF), y1 = y0 + (int)(int16_t)((uint32_t)re >> 16);
-        if (pr & 1) { x1 += ((info >> 3) & 3) - 1; y1 += ((info >> 5) & 3) - 1; }
-        return ((uint32_t)ux[x1 - fxl] << 16) | (uint32_t)uy[y1 - fyl];
-    };
-    struct FCell { int sx, sy; int gx0, gx1, gy0, gy1; int ngx, ngy; };            // storage cell and its source global cells
-    auto cell_sources = [&](uint32_t sc, FCell& f) {
-        f.sx = (int)(sc >> 16); f.sy = (int)(sc & 0xFFFFu);
-        const int ax = f.sx - C, ay = f.sy - C;                                     // sources: a (if not glitched), a + 1 (if glitched)
-        const bool xa = !gxb[ax - fxl], xb = gxb[ax + 1 - fxl], ya = !gyb[ay - fyl], yb = gyb[ay + 1 - fyl];
-        f.ngx = (xa ? 1 : 0) + (xb ? 1 : 0); f.gx0 = xa ? ax : ax + 1; f.gx1 = ax + 1;
-        f.ngy = (ya ? 1 : 0) + (yb ? 1 : 0); f.gy0 = ya ? ay : ay + 1; f.gy1 = ay + 1;
-    };
+    // pairs (beam, e) and the storage cells they flag, flagged cells and their sources (rbpf_mapupdate.h)
+    auto pair_cell = [&](int pr) { return flagged_cell(pr, r_info, r_end, x0, y0, ux, uy, fxl, fyl); };
+    auto sources = [&](uint32_t sc, FCell& f) { cell_sources(sc, C, gxb, gyb, fxl, fyl, f); };
     // tile and offset of a storage cell (rays are shorter than a tile: the lattice coordinate moves by at most one)
     auto cell_addr = [&](int sx, int sy, int& tile, int& row_t, int& col_t) {
         const int a = a0 + (sx >= (a0 + 1) * v.dim ? 1 : 0) - (sx < a0 * v.dim ? 1 : 0);
@@ -487,9 +294,9 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         RayDir d; d.steep = aey > aex; d.sx = ex > 0 ? 1 : -1; d.sy = ey > 0 ? 1 : -1;          // hybridmap.py:282-283
         return d;
     };
-    const int sat = (v.cc.vmax - v.cc.vmin + (-v.cc.emp) - 1) / (-v.cc.emp);        // passes that saturate any cell: 20
-    const uint32_t satb = (uint32_t)sat * 0x01010101u, sadd = (128u - (uint32_t)sat) * 0x01010101u;
-    const int cnt_lds = ev_lds_addr(cnt), mini_lds = ev_lds_addr(mini);
+    const int sat = sat_passes(v.cc);
+    const WbConsts wbk = wb_consts(v.cc);
+    const int cnt_lds = lds_addr(cnt), mini_lds = lds_addr(mini);
     // a thin fan: fewer ray cells than two fifths of the fan's box (181 beams on a 0.025 m grid: a seventh)
     const bool sparse = (long long)UNI((int)s_cells) * 5 < 2LL * (long long)(S_hi - S_lo + 1) * (long long)(T_hi - T_lo + 1);
     // a lane's steps that met a flagged cell (bit 16 + u of m = step j0 + u): into the event list
@@ -529,11 +336,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         const int gx_base = S0 - C, rows_w = S1 - S0 + 2;                        // global rows gx_base .. gx_base + rows_w - 1
         const bool whole = S0 == S_lo && S1 == S_hi;                             // one window holds the fan
         BAR_LDS();                                                               // the previous window (or the slope buckets) is done with the counters
-        {
-            uint4* c4 = reinterpret_cast<uint4*>(cnt);
-            const int n16 = (rows_w * stride + 15) >> 4;
-            for (int i = tid; i < n16; i += EB) c4[i] = make_uint4(0, 0, 0, 0);
-        }
+        for (int i = tid; i < (rows_w * stride + 15) >> 4; i += EB) reinterpret_cast<uint4*>(cnt)[i] = make_uint4(0, 0, 0, 0);
         BAR_LDS();
         // ---- flags: every global cell that maps to a storage cell with an occupied / nearby hit; the flag comes with a
         //      count of one, so a flagged field is never zero (the write-back takes "touched" from the field) ----
@@ -543,7 +346,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
             asm volatile("" : "+v"(sc));                                         // (the cell's sources are worked out here, strip by strip: hoisted out of the strips' loop they were 24 registers spilled to scratch)
             if (sc == 0xFFFFFFFFu) continue;
             FCell f;
-            cell_sources(sc, f);
+            sources(sc, f);
 #pragma unroll
             for (int ix = 0; ix < 2; ++ix)
 #pragma unroll
@@ -683,19 +486,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
                     if (len) atomicAdd(&s_lcnt[min(len, MAXLEV)], 1);
                 }
                 BAR_LDS();
-                if (wave == 0) {   // relative levels: N_k = rays with at least k whole chunks inside the strip
-                    const int k = lane;
-                    const int ck = k >= 1 ? s_lcnt[k] : 0;
-                    int suf = ck;
-                    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (lane + o < 64) suf += t; }
-                    const int nwk = k >= 1 ? (suf + 63) >> 6 : 0;
-                    int pre = nwk;
-                    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(pre, o, 64); if (lane >= o) pre += t; }
-                    const unsigned long long live = __ballot(k >= 1 && suf > 0);
-                    if (k >= 1) { s_lfill[k] = suf - ck; s_nk[k] = suf; s_lp[k] = pre - nwk; }
-                    if (k == 63) s_lp[64] = pre;
-                    if (k == 0) { s_nlev = live ? 63 - __clzll((long long)live) : 0; s_nk[MAXLEV + 1] = 0; }
-                }
+                if (wave == 0) level_sums(lane, s_lcnt, s_lfill, s_nk, s_lp, &s_nlev);   // relative levels: rays with at least k whole chunks inside the strip
                 BAR_LDS();
                 for (int b = tid; b < v.B; b += EB) {
                     const int len = (int)r_kl[b] >> 8;
@@ -764,167 +555,10 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         }
         if (tid == 0) s_wbq = 0;
         BAR_LDS();
-        // ---- write-back: one read-modify-write per touched 32-cell group of storage cells, tile by tile.  Storage cell s
-        //      receives global cell s - C where that one is not glitched plus global cell s - C + 1 where that one is.  The
-        //      flagged cells get a value from their counts like all others; their real value follows after the windows. ----
-        {
-            int my_written = 0;
-            const int eabs = -v.cc.emp;
-            const EvWb wbk = {(uint32_t)(128 + v.cc.vmin) * 0x01010101u, (uint32_t)(127 - (v.cc.thr - v.cc.vmin)) * 0x01010101u, satb, sadd, -v.cc.emp};
-            const uint32_t kb1 = (uint32_t)(128 + v.cc.vmin) * 0x01010101u;             // byte-wise: (cell ^ 0x80) - kb1 = cell - vmin
-            const uint32_t oadd = (uint32_t)(127 - (v.cc.thr - v.cc.vmin)) * 0x01010101u; // bit 7 of (R + oadd) = cell > thr
-            // Waves draw batches of 64 items (32-cell groups) from a queue: the rows at the fan's rim hold few touched groups, and
-            // with a fixed share per wave the workgroup waited a quarter of the write-back's time for its slowest wave.
-            auto next_batch = [&]() -> int { int g = 0; if (lane == 0) g = atomicAdd(&s_wbq, 1); return UNI(g); };
-            int batch = next_batch(), batch0 = 0;                        // batch0: the first batch of the tile at hand
-            for (int a = S0 / v.dim; a <= S1 / v.dim; ++a)
-            for (int bt = T_lo / v.dim; bt <= T_hi / v.dim; ++bt) {
-                if (a >= v.L || bt >= v.L) continue;                                   // uniform
-                const int tile = UNI(s_tab[a * v.L + bt]);
-                if (tile < 0) continue;
-                const int sr_lo = max(S0, a * v.dim), sr_hi = min(S1, (a + 1) * v.dim - 1);      // storage rows
-                const int g_lo = max(T_lo - bt * v.dim, 0) >> 5, g_hi = min(T_hi - bt * v.dim, v.dim - 1) >> 5;   // groups of this tile's rows
-                const int ngr = g_hi - g_lo + 1, items = (sr_hi - sr_lo + 1) * ngr;
-                int8_t* __restrict__ tile_base = v.pool + (size_t)tile * v.dim * v.dim;
-                int bx0 = INT_MAX, bx1 = -1, by0 = INT_MAX, by1 = -1;
-                const int nbatch = (items + 63) >> 6;
-                const float inv_ngr = 1.0f / (float)ngr;
-                for (; batch < batch0 + nbatch; batch = next_batch()) {
-                    const int it = ((batch - batch0) << 6) + lane;
-                    if (it >= items) continue;
-                    const int rr = (int)(((float)it + 0.5f) * inv_ngr), gg = it - rr * ngr;   // it / ngr: (it + 0.5) / ngr is at least 0.5 / 192 from a whole number, the float product's error 1e-4 of that
-                    const int srow = sr_lo + rr, gt = g_lo + gg;
-                    const int ia = srow - C - fxl;                                     // source rows a (if not glitched), a + 1 (if glitched)
-                    const bool va = !gxb[ia], vb = gxb[ia + 1];
-                    if (!va && !vb) continue;                                          // no global row maps here
-                    const int lr = srow - C - gx_base;                                 // window row of source a
-                    const int lc0 = bt * v.dim + 32 * gt - C - gy_base;                // window column of the group's first cell, multiple of 4
-                    const int nw = min(32, v.dim - 32 * gt) >> 2;                      // words of this group (8; fewer in a tile's last group)
-                    uint32_t n[8];
-                    uint32_t any = 0;
-                    const bool both = va && vb;
-                    if (!both && !s_ggf[(bt - bt_lo) * gpt + gt]) {   // one source row, no glitched column: the fields are the group's counts
-                        const int rowo = (lr + (va ? 0 : 1)) * stride + lc0;
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) {
-                            const int lc = lc0 + 4 * w;
-                            n[w] = (lc >= 0 && lc < stride && w < nw) ? (cnt[(rowo + 4 * w) >> 2] >> 1) & 0x7F7F7F7Fu : 0u;
-                            any |= n[w];
-                        }
-                    } else {
-                        uint32_t gm[9];                                                // glitched columns in the group (its 32 cells and the one after)
-#pragma unroll
-                        for (int w = 0; w < 9; ++w) {
-                            const int lc = lc0 + 4 * w;
-                            gm[w] = (lc >= 0 && lc < stride + 12) ? *reinterpret_cast<const uint32_t*>(gym + lc) : 0u;
-                        }
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) n[w] = 0;
-                        for (int src = 0; src < 2; ++src) {
-                            if (src == 0 ? !va : !vb) continue;
-                            const int row = lr + src;
-                            uint32_t x[9];
-#pragma unroll
-                            for (int w = 0; w < 9; ++w) {
-                                const int lc = lc0 + 4 * w;
-                                x[w] = (lc >= 0 && lc < stride) ? (cnt[(row * stride + lc) >> 2] >> 1) & 0x7F7F7F7Fu : 0u;
-                            }
-#pragma unroll
-                            for (int w = 0; w < 9; ++w) x[w] = ev_min4(x[w], satb, sadd);
-#pragma unroll
-                            for (int w = 0; w < 8; ++w) {
-                                const uint32_t keep = x[w] & ~gm[w];
-                                const uint32_t mv = ((x[w] & gm[w]) >> 8) | ((x[w + 1] & gm[w + 1]) << 24);
-                                n[w] += keep + mv;
-                            }
-                        }
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) { if (w >= nw) n[w] = 0; any |= n[w]; }
-                    }
-                    if (!any) continue;
-                    const int row_t = srow - a * v.dim, col_t = 32 * gt;
-                    uint32_t* g_ptr = reinterpret_cast<uint32_t*>(tile_base + (size_t)row_t * v.dim + col_t);
-                    uint32_t pre[8];
-                    if (nw == 8) {
-                        const uint4 q0 = reinterpret_cast<const uint4*>(g_ptr)[0], q1 = reinterpret_cast<const uint4*>(g_ptr)[1];
-                        pre[0] = q0.x; pre[1] = q0.y; pre[2] = q0.z; pre[3] = q0.w; pre[4] = q1.x; pre[5] = q1.y; pre[6] = q1.z; pre[7] = q1.w;
-                    } else {
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) pre[w] = w < nw ? g_ptr[w] : 0u;
-                    }
-                    if (sparse) {   // a thin fan (few beams on a fine grid): a group holds one or two touched words - the arithmetic and
-                                    // the stores are theirs alone; the other words only give their occupancy bits (the group's 32 bytes are
-                                    // one memory sector: read whole, written by the word)
-                        uint32_t nzm = 0;
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) nzm |= n[w] ? 1u << w : 0u;
-                        if (__popc(nzm) <= 3) {
-                            uint32_t occ = 0, touched = 0;
-#pragma unroll
-                            for (int w = 0; w < 8; ++w)                                       // cell > thr of the cells as they are
-                                occ |= __builtin_amdgcn_udot4(((((pre[w] ^ 0x80808080u) - wbk.kb1) + wbk.oadd) & 0x80808080u) >> 7, 0x08040201u, 0u, false) << (4 * w);
-                            if (nw < 8) occ &= (1u << (4 * nw)) - 1u;
-                            uint32_t mm = nzm;
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) {
-                                const int wq = mm ? __ffs((int)mm) - 1 : -1;
-                                mm &= mm - 1;
-                                if (wq < 0) continue;
-                                uint32_t pw = 0, nv = 0;
-#pragma unroll
-                                for (int w = 0; w < 8; ++w) { pw = w == wq ? pre[w] : pw; nv = w == wq ? n[w] : nv; }
-                                uint32_t t4, o4;
-                                g_ptr[wq] = ev_wb_word(wbk, pw, nv, t4, o4);
-                                touched |= t4 << (4 * wq);
-                                occ = (occ & ~(0xFu << (4 * wq))) | (o4 << (4 * wq));
-                            }
-                            v.occ[((size_t)tile * v.dim + row_t) * v.ow + gt] = occ;
-                            my_written += __popc(touched);
-                            by0 = min(by0, col_t + __ffs(touched) - 1); by1 = max(by1, col_t + 31 - __clz(touched));
-                            bx0 = min(bx0, row_t); bx1 = max(bx1, row_t);
-                            continue;
-                        }
-                    }
-                    uint32_t occ = 0, touched = 0, out[8];
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) {
-                        // branch-free (a word without hits passes through unchanged: dec = 0, nz = 0)
-                        const uint32_t Ob = (pre[w] ^ 0x80808080u) - kb1;                   // cells biased to [0, vmax - vmin]
-                        const uint32_t n7 = n[w];
-                        const uint32_t m = ev_min4(n7, satb, sadd);                         // min(n, sat)
-                        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-                        const uint32_t dec = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, m) * (us2)(unsigned short)eabs);   // byte-wise: sat * |emp| < 128, no carries
-                        const uint32_t T1 = (Ob | 0x80808080u) - dec;
-                        const uint32_t pos = T1 & 0x80808080u;                              // O - dec >= 0
-                        const uint32_t R = T1 & 0x7F7F7F7Fu & (pos | (pos - (pos >> 7)));
-                        out[w] = (R + kb1) ^ 0x80808080u;
-                        const uint32_t nz = (n7 + 0x7F7F7F7Fu) & 0x80808080u;               // fields that are not zero
-                        touched |= __builtin_amdgcn_udot4(nz >> 7, 0x08040201u, 0u, false) << (4 * w);
-                        occ |= __builtin_amdgcn_udot4(((R + oadd) & 0x80808080u) >> 7, 0x08040201u, 0u, false) << (4 * w);   // cell > thr
-                    }
-                    if (nw == 8) {
-                        reinterpret_cast<uint4*>(g_ptr)[0] = make_uint4(out[0], out[1], out[2], out[3]);
-                        reinterpret_cast<uint4*>(g_ptr)[1] = make_uint4(out[4], out[5], out[6], out[7]);
-                    } else {
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) if (w < nw) g_ptr[w] = out[w];
-                        occ &= (1u << (4 * nw)) - 1u;                                      // (cells past the tile's last column are not cells)
-                    }
-                    my_written += __popc(touched);
-                    by0 = min(by0, col_t + __ffs(touched) - 1); by1 = max(by1, col_t + 31 - __clz(touched));
-                    v.occ[((size_t)tile * v.dim + row_t) * v.ow + gt] = occ;
-                    bx0 = min(bx0, row_t); bx1 = max(bx1, row_t);
-                }
-                batch0 += nbatch;
-                bx0 = wave_min(bx0); bx1 = wave_max(bx1); by0 = wave_min(by0); by1 = wave_max(by1);
-                if (lane == 0 && bx1 >= 0) {                                           // this workgroup is the tile's only writer
-                    atomicMin(&v.tile_bbox[4 * tile + 0], bx0); atomicMax(&v.tile_bbox[4 * tile + 1], bx1);
-                    atomicMin(&v.tile_bbox[4 * tile + 2], by0); atomicMax(&v.tile_bbox[4 * tile + 3], by1);
-                }
-            }
-            const int ww = wave_sum(my_written);
-            if (lane == 0 && ww) atomicAdd(&s_written, ww);
-        }
+        // ---- write-back (rbpf_mapupdate.h): the flagged cells get a value from their counts like all others; their real value
+        //      follows after the windows ----
+        strip_write_back<FIELD_COUNT_HI, true, true, false>(v, sg, S0, S1, gx_base, C, fxl, ggf_base, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
+                                                            &s_wbq, &s_written, sparse, lane);
         STAMP(4);
     }
     BAR_LDS();                                                                // the window's LDS is free (the write-back's stores are still on their way)
@@ -939,14 +573,14 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     int8_t*   const oldc = reinterpret_cast<int8_t*>(smem + G.o_cnt + G.p_oldv);      // [T] the cell's value before the scan
     uint16_t* const rlist = reinterpret_cast<uint16_t*>(smem + G.o_cnt + G.p_rlist);  // [records] slots in use
     uint16_t* const nextp = reinterpret_cast<uint16_t*>(smem + G.o_cnt + G.p_evl);    // [pairs] next pair (beam << 1 | nearby) on the same cell
-    uint16_t* const evl = nextp + ev_al16(G.E * 2) / 2;                               // [pairs] the lists, one after the other (laid out by the fold)
+    uint16_t* const evl = nextp + al16(G.E * 2) / 2;                               // [pairs] the lists, one after the other (laid out by the fold)
     uint16_t* const ic16 = reinterpret_cast<uint16_t*>(smem + G.o_cnt + G.p_ic);      // [pairs] passes right before the pair's event
     const int T = G.T;
     const int nev_all = UNI(s_nev);
     const bool overflow = nev_all > EVCAP;
     for (int i = tid; i < T / 4; i += EB) { reinterpret_cast<uint4*>(keys)[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu); reinterpret_cast<uint4*>(head)[i] = make_uint4(0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu); }
     for (int i = tid; i < T / 8; i += EB) reinterpret_cast<uint4*>(iclast)[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < ev_al16(G.E * 2) / 16; i += EB) reinterpret_cast<uint4*>(ic16)[i] = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < al16(G.E * 2) / 16; i += EB) reinterpret_cast<uint4*>(ic16)[i] = make_uint4(0, 0, 0, 0);
     if (tid == 0) { s_wsum[0] = 0; s_wsum[1] = 0; }
     BAR_LDS();
     // every pair joins the list of its cell (the cell's first pair lists the cell and leaves its old value)
@@ -954,7 +588,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     for (int i = 0; i < NPAIR; ++i) {
         if (my_sc[i] == 0xFFFFFFFFu) continue;
         bool created;
-        const int h = ev_hash_insert2(keys, T, G.logT, my_sc[i], created);
+        const int h = ev_hash_insert(keys, T, G.logT, my_sc[i], created);
         {   // a record per new cell: the wave's new cells take their places in the record list with ONE add (1300 returning adds
             // on one LDS word stand in line otherwise)
             const unsigned long long mk = __ballot(created);
@@ -1033,7 +667,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
             const int h = rlist[r];
             const uint32_t key = keys[h];
             FCell f;
-            cell_sources(key, f);
+            sources(key, f);
             const int gxc[2] = {f.gx0, f.gx1}, gyc[2] = {f.gy0, f.gy1};
             const int val = replay_cell_wave(v, r_info, r_end, x0, y0, gxc, f.ngx, gyc, f.ngy, (int)oldc[h], lane);
             if (lane == 0) store_cell(key, val);
@@ -1050,9 +684,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         atomicAdd(&v.stats[ST_MAP_WINDOWS], (unsigned long long)n_win);
         atomicAdd(&v.stats[ST_MAP_EVENTS], (unsigned long long)nev_all);
         if (overflow) atomicAdd(&v.stats[ST_EV_OVERFLOWS], 1ull);
-#ifdef RBPF_STAMPS
-        for (int k = 0; k < 8; ++k) atomicAdd(&v.stats[8 + k], (unsigned long long)st_acc[k]);
-#endif
+        STAMP_FLUSH();
     }
 }
 

@@ -29,21 +29,7 @@
 
 namespace rbpf {
 
-#ifdef RBPF_STAMPS
-#define STAMP(k) do { if (tid == 0) { long long t_ = clock64(); st_acc[k] += t_ - st_prev; st_prev = t_; } } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
-// hand the particle to the window kernel (uniform over the workgroup; nothing has been written to the map yet);
-// reason codes: 1 geometry / index map, 2 counter bound, 3 event tables
-#define GIVE_BACK(reason) do { if (tid == 0) { v.mu_fallback[p] = (reason); atomicAdd(&v.stats[(reason) == 1 ? ST_FALLBACK_REASONS : (reason) == 2 ? ST_FB_BOUND : ST_FB_TABLES], 1ull); } return; } while (0)
-
 static const int RB = 1024;                    // threads per particle
-static const int NEAR_R = 16;                  // ray steps j < NEAR_R are counted in the 16-bit block
-static const int LCH = 16;                     // steps per chunk of the walk beyond it
-static const int NEAR_W = 2 * NEAR_R + 1;      // cells with Chebyshev distance <= NEAR_R from the start cell (one spare ring)
-static const int NBIN = 256;                   // slope buckets per direction class
 static const int RFIX = 22;                    // fixed-point bits of the slope (fix_slope)
 static const int BIN_SHIFT = RFIX - 8;
 static const int RSLOW = 256;                  // flagged cells replayed by the wave-wide exact scan, per particle
@@ -53,8 +39,6 @@ static const int NSPC = 32;                    // occupied / nearby events of su
 static const int NPOOL = 48;                   // flagged cells with more than ECAP events: lists of PCAP events, sorted and folded by a wave
 static const int PCAP = 64;
 static const int RSPEC = 512;                  // flagged cells on an axis or a diagonal through the sensor, per particle
-static const int MAXLEV = 63;                  // whole 16-step chunks per ray (reach < 1000 cells)
-static const int NB_WIN = NBIN / NEAR_R + 2;   // slope buckets that can hold the rays through one cell beyond the 16-bit block
 static const int HIT_BOUND = 63;               // per direction class; two classes can meet in one cell: 126 < 128
 
 struct RayGeom {
@@ -64,33 +48,31 @@ struct RayGeom {
     bool ok;
 };
 
-__host__ __device__ inline int ray_al16(int x) { return (x + 15) & ~15; }
-
 __host__ __device__ inline RayGeom ray_geom(int B, int reach) {
     RayGeom g;
     g.fanw = (2 * reach + 8 + 7) & ~7;
     g.bpad = (B + 3) & ~3;
     int o = 0;
-    g.o_mini = o;  o += ray_al16(((NEAR_W * NEAR_W + 1) / 2) * 4);
-    g.o_rend = o;  o += ray_al16(g.bpad * 4);
-    g.o_fstep = o; o += ray_al16(g.bpad * 4);
-    g.o_rinfo = o; o += ray_al16(g.bpad);
-    g.o_ux = o;    o += ray_al16(g.fanw * 2);
-    g.o_uy = o;    o += ray_al16(g.fanw * 2);
-    g.o_gxb = o;   o += ray_al16(g.fanw);
-    g.o_gyb = o;   o += ray_al16(g.fanw);
-    g.o_gym = o;   o += ray_al16(g.fanw + 16);
+    g.o_mini = o;  o += al16(((NEAR_W * NEAR_W + 1) / 2) * 4);
+    g.o_rend = o;  o += al16(g.bpad * 4);
+    g.o_fstep = o; o += al16(g.bpad * 4);
+    g.o_rinfo = o; o += al16(g.bpad);
+    g.o_ux = o;    o += al16(g.fanw * 2);
+    g.o_uy = o;    o += al16(g.fanw * 2);
+    g.o_gxb = o;   o += al16(g.fanw);
+    g.o_gyb = o;   o += al16(g.fanw);
+    g.o_gym = o;   o += al16(g.fanw + 16);
     g.o_bins = o;  o += 8 * NBIN * 2;                  // 2048 packed 16-bit fill pointers = one 32-bit word per thread
-    g.o_brays = o; o += ray_al16(g.bpad * 2);
-    g.o_oval = o;  o += ray_al16(g.bpad * 2);
+    g.o_brays = o; o += al16(g.bpad * 2);
+    g.o_oval = o;  o += al16(g.bpad * 2);
     g.o_slow = o;  o += RSLOW * 2;
-    g.o_oldv = o;  o += ray_al16(g.bpad * 2);
-    g.o_rcc = o;   o += ray_al16(g.bpad * 4);
-    g.o_rdmaj = o; o += ray_al16(g.bpad * 2);
-    g.o_perm = o;  o += ray_al16(g.bpad * 2);
-    g.o_rpos = o;  o += ray_al16(g.bpad * 2);
-    g.o_pflag = o; o += ray_al16(g.bpad * 2);
-    g.o_nid = o;   o += ray_al16(NEAR_W * NEAR_W);
+    g.o_oldv = o;  o += al16(g.bpad * 2);
+    g.o_rcc = o;   o += al16(g.bpad * 4);
+    g.o_rdmaj = o; o += al16(g.bpad * 2);
+    g.o_perm = o;  o += al16(g.bpad * 2);
+    g.o_rpos = o;  o += al16(g.bpad * 2);
+    g.o_pflag = o; o += al16(g.bpad * 2);
+    g.o_nid = o;   o += al16(NEAR_W * NEAR_W);
     g.o_nearl = o; o += NNEAR * 2;
     g.o_cnt = o;
     const int avail = 160 * 1024 - 2048 - o - 64;      // 2 KB for the kernel's static LDS
@@ -108,10 +90,8 @@ __host__ __device__ inline bool ray_lists_fit(const RayGeom& g) {
 }
 
 bool map_update_ray_available(const DevView& v) {
-    const int sat = (v.cc.vmax - v.cc.vmin + (-v.cc.emp) - 1) / (-v.cc.emp);
     const RayGeom g = ray_geom(v.B, v.reach);
-    return g.ok && ray_lists_fit(g) && v.dim % 32 == 0 && v.L * v.L <= 49 && v.cc.emp < 0 && sat <= 31 && v.cc.vmax - v.cc.vmin <= 127 &&
-           v.cc.vmin <= 0 && v.cc.vmax >= 0 && v.cc.vmin >= -127 && sat * -v.cc.emp <= 127 && v.cc.thr >= v.cc.vmin && v.cc.thr < v.cc.vmax;
+    return g.ok && ray_lists_fit(g) && lattice_fits_byte_fields(v.cc) && v.dim % 32 == 0 && v.L * v.L <= 49;
 }
 
 __device__ __forceinline__ uint32_t ray_fix_slope(int dmin, int dmaj) {
@@ -121,25 +101,11 @@ __device__ __forceinline__ uint32_t ray_fix_slope(int dmin, int dmaj) {
 // Fire-and-forget adds on hit fields, addressed by field index + the array's LDS address folded into the index (the
 // addresses are multiples of 4, so the field's position inside its word is unchanged): the LDS instruction takes the
 // masked index as its address, without a separate add of the array's base.
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ int lds_addr(const void* p) { return (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char*)p; }
 __device__ __forceinline__ void fld8_add(int cabs, uint32_t one) {      // 8-bit fields; cabs = index + lds_addr(array); one = 1 or 0
     __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(uint32_t)(cabs & ~3), one << ((cabs & 3) * 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ void fld16_add(int cabs, uint32_t one) {     // 16-bit fields; cabs = index + lds_addr(array) / 2
     __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(uint32_t)((cabs << 1) & ~3), one << ((cabs & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// byte-wise min(field, sat) of four unflagged 7-bit hit counts; flagged bytes (bit 7: the field holds a replayed value)
-// pass through
-__device__ __forceinline__ uint32_t premin4(uint32_t x, uint32_t satb, uint32_t sadd) {
-    const uint32_t n7 = x & 0x7F7F7F7Fu;
-    const uint32_t ge = (n7 + sadd) & 0x80808080u;
-    const uint32_t gem = ge | (ge - (ge >> 7));
-    const uint32_t m = (satb & gem) | (n7 & ~gem);
-    const uint32_t fl = x & 0x80808080u;
-    const uint32_t flm = fl | (fl - (fl >> 7));
-    return (x & flm) | (m & ~flm);
 }
 
 __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int32_t* __restrict__ only) {
@@ -183,43 +149,18 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int LL = v.L * v.L;
-    const int KW = (v.dim + WIN - 1) / WIN;
     int32_t* tab = v.tile_tab + (size_t)v.slot[p] * LL;
 
-#ifdef RBPF_STAMPS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = clock64();
-#endif
+    STAMP_DECL;
     // =============================================== setup ===============================================
     const int pb0 = tid, pb1 = tid + RB;
     const double pre_x0 = pb0 < v.B ? v.bx[pb0] : 0.0, pre_y0 = pb0 < v.B ? v.by[pb0] : 0.0;
     const double pre_x1 = pb1 < v.B ? v.bx[pb1] : 0.0, pre_y1 = pb1 < v.B ? v.by[pb1] : 0.0;
     const int pre_f0 = pb0 < v.B ? v.bflags[pb0] : 0, pre_f1 = pb1 < v.B ? v.bflags[pb1] : 0;
     const double s_px = v.upd_pose[p], s_py = v.upd_pose[v.P + p];
-    if (wave == 0) {   // one wave takes the sine and cosine (a few hundred instructions); the others read them after the first barrier
-        double sn, cs_;
-        sincos(v.upd_pose[2 * v.P + p], &sn, &cs_);
-        if (lane == 0) { s_sincos[0] = sn; s_sincos[1] = cs_; }
-    }
-    const int x0 = UNI(trunc_to_int(s_px / v.cs)), y0 = UNI(trunc_to_int(s_py / v.cs));   // hybridmap.py:102
-    {
-        int lx, ly;                                                          // hybridmap.py:98-100
-        bool ok = tile_of_coord(s_px, v.tile_len, v.R, lx) && tile_of_coord(s_py, v.tile_len, v.R, ly);
-        if (ok) ok = tab[(lx + v.R) * v.L + (ly + v.R)] >= 0;
-        const bool in_lut = lut_valid_g(v, x0 - v.reach) && lut_valid_g(v, x0 + v.reach) &&
-                            lut_valid_g(v, y0 - v.reach) && lut_valid_g(v, y0 + v.reach);
-        if (ok && !in_lut) { if (tid == 0) atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }
-        if (tid == 0) v.mu_fallback[p] = 0;
-        if (!UNI(ok)) return;
-    }
-    // the index map over everything a ray can reach, with a margin of two columns (the sources of a storage cell are its
-    // own global index and the next one)
+    int x0, y0;
+    if (!fan_preamble<RB>(v, tab, p, tid, s_px, s_py, v.reach, G.fanw, s_sincos, ux, uy, x0, y0)) return;
     const int fxl = x0 - v.reach - 2, fyl = y0 - v.reach - 2, nfx = 2 * v.reach + 5;
-    for (int i = tid; i < G.fanw; i += RB) {
-        const int gxq = fxl + i, gyq = fyl + i;
-        uint32_t ex = lut_valid_g(v, gxq) ? lut_at(v, gxq) : LUT_INVALID, ey = lut_valid_g(v, gyq) ? lut_at(v, gyq) : LUT_INVALID;
-        ux[i] = ex != LUT_INVALID ? (uint16_t)(lut_lat(ex) * v.dim + lut_cidx(ex)) : 0xFFFFu;
-        uy[i] = ey != LUT_INVALID ? (uint16_t)(lut_lat(ey) * v.dim + lut_cidx(ey)) : 0xFFFFu;
-    }
     if (tid == 0) {
         s_fan[0] = x0; s_fan[1] = x0; s_fan[2] = y0; s_fan[3] = y0;
         s_cells = 0; s_fb = 0; s_written = 0; s_nslow = 0; s_nspec = 0; s_nact = 0; s_exact = 0; s_nnear = 0; s_npool = 0;
@@ -240,23 +181,11 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
     const int a0 = Uxs / v.dim, b0 = Uys / v.dim;
     auto lat_x = [&](int g) { const int U = ux[g - fxl]; return a0 + (U >= (a0 + 1) * v.dim ? 1 : 0) - (U < a0 * v.dim ? 1 : 0); };
     auto lat_y = [&](int g) { const int U = uy[g - fyl]; return b0 + (U >= (b0 + 1) * v.dim ? 1 : 0) - (U < b0 * v.dim ? 1 : 0); };
-    // the storage cell (U_x << 16 | U_y) flagged by pair (beam, e): the beam's end cell (e = 0) or the cell before it (e = 1,
-    // only when it lies in the end cell's tile); ~0 = none.  And the ray's window-address steps (per major / minor step).
-    auto pair_cell = [&](int pr) -> uint32_t {
-        const int b = pr >> 1, info = r_info[b];
-        if ((info & (RI_VALID | RI_OCC)) != (RI_VALID | RI_OCC) || ((pr & 1) && !(info & RI_NEAR))) return 0xFFFFFFFFu;
-        const int32_t re = r_end[b];
-        int x1 = x0 + (int)(int16_t)(re & 0xFFFF), y1 = y0 + (int)(int16_t)((uint32_t)re >> 16);
-        if (pr & 1) { x1 += ((info >> 3) & 3) - 1; y1 += ((info >> 5) & 3) - 1; }
-        return ((uint32_t)ux[x1 - fxl] << 16) | (uint32_t)uy[y1 - fyl];
-    };
+    // pairs (beam, e) and the storage cells they flag, flagged cells and their sources (rbpf_mapupdate.h)
+    auto pair_cell = [&](int pr) { return flagged_cell(pr, r_info, r_end, x0, y0, ux, uy, fxl, fyl); };
     auto pair_gcell = [&](int pr) -> uint32_t {          // the same as a global cell relative to the start, biased: never ~0
-        const int b = pr >> 1, info = r_info[b];
-        if ((info & (RI_VALID | RI_OCC)) != (RI_VALID | RI_OCC) || ((pr & 1) && !(info & RI_NEAR))) return 0xFFFFFFFFu;
-        const int32_t re = r_end[b];
-        int dx = (int)(int16_t)(re & 0xFFFF), dy = (int)(int16_t)((uint32_t)re >> 16);
-        if (pr & 1) { dx += ((info >> 3) & 3) - 1; dy += ((info >> 5) & 3) - 1; }
-        return (uint32_t)(dx + 0x4000) | ((uint32_t)(dy + 0x4000) << 16);
+        int dx, dy;
+        return pair_offset(pr, r_info, r_end, dx, dy) ? (uint32_t)(dx + 0x4000) | ((uint32_t)(dy + 0x4000) << 16) : 0xFFFFFFFFu;
     };
     // direction class and slope bucket of a ray
     auto ray_key = [&](int ddx, int ddy, uint32_t fstep) {
@@ -266,55 +195,16 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
         return cls * NBIN + bin;
     };
     {
-        unsigned long long my_cells = 0;
-        int fx0 = x0, fx1 = x0, fy0 = y0, fy1 = y0;
+        FanBox fan = {x0, x0, y0, y0, 0ull};
         for (int b = tid; b < v.B; b += RB) {
             const double x = b == pb0 ? pre_x0 : b == pb1 ? pre_x1 : v.bx[b], y = b == pb0 ? pre_y0 : b == pb1 ? pre_y1 : v.by[b];
             const int bf = b == pb0 ? pre_f0 : b == pb1 ? pre_f1 : (int)v.bflags[b];
-            double gx = (s_c * x + (-s_s) * y) + s_px;                             // lidar.py:123
-            double gy = (s_s * x + s_c * y) + s_py;
-            int x1 = trunc_to_int(gx / v.cs), y1 = trunc_to_int(gy / v.cs);        // hybridmap.py:106
-            if (bf & BF_LONG) {                                                    // hybridmap.py:107-113
-                double sc = v.bscale[b];
-                x1 = trunc_to_int((double)x0 + sc * (double)(x1 - x0));
-                y1 = trunc_to_int((double)y0 + sc * (double)(y1 - y0));
-            }
-            int ddx = x1 - x0, ddy = y1 - y0;
-            if (ddx < -v.reach || ddx > v.reach || ddy < -v.reach || ddy > v.reach) {
-                atomicCAS(v.err, 0, RBPF_ERANGE);
-                ddx = 0; ddy = -1; x1 = x0; y1 = y0 - 1;                           // degenerate: no points
-            }
+            const BeamRay br = beam_ray(v, x, y, bf, [&] { return v.bscale[b]; }, s_s, s_c, s_px, s_py, x0, y0, a0, b0, lat_x, lat_y, s_need, fan);
+            const Ray& r = br.r;
+            const int ddx = br.x1 - x0, ddy = br.y1 - y0;
             r_end[b] = (int32_t)(((uint32_t)ddx & 0xFFFFu) | ((uint32_t)ddy << 16));
-            Ray r = ray_make(x0, y0, x1, y1);
-            int info = 0;
             uint32_t fstep = 0;
             if (r.n > 0) {
-                info = RI_VALID | ((bf & BF_LONG) ? 0 : RI_OCC);
-                my_cells += (unsigned long long)r.n;
-                fx0 = min(fx0, x1); fx1 = max(fx1, x1); fy0 = min(fy0, y1); fy1 = max(fy1, y1);
-                const int a1 = lat_x(x1), b1 = lat_y(y1);
-                if (r.n >= 2 && (info & RI_OCC)) {                                 // hybridmap.py:139-142
-                    int nx, ny;
-                    ray_point(r, r.n - 2, nx, ny);
-                    if (lat_x(nx) == a1 && lat_y(ny) == b1) info |= RI_NEAR;          // hybridmap.py:141 same tile as the end cell
-                    info |= ((nx - x1 + 1) & 3) << 3;
-                    info |= ((ny - y1 + 1) & 3) << 5;
-                }
-                // tiles entered by this ray (staircase start -> [corner] -> end)
-                s_need[a0 * v.L + b0] = 1;
-                if (a1 != a0 || b1 != b0) {
-                    s_need[a1 * v.L + b1] = 1;
-                    if (a1 != a0 && b1 != b0) {
-                        int gxb_ = r.sx > 0 ? v.gwin[a1 * (KW + 1)] : v.gwin[a0 * (KW + 1)] - 1;
-                        int gyb_ = r.sy > 0 ? v.gwin[b1 * (KW + 1)] : v.gwin[b0 * (KW + 1)] - 1;
-                        int ox = gxb_ - x0; ox = ox < 0 ? -ox : ox;
-                        int oy = gyb_ - y0; oy = oy < 0 ? -oy : oy;
-                        int jx = r.steep ? first_j_minor_ge(r, ox) : ox;
-                        int jy = r.steep ? oy : first_j_minor_ge(r, oy);
-                        if (jx < jy) s_need[a1 * v.L + b0] = 1;
-                        else if (jy < jx) s_need[a0 * v.L + b1] = 1;
-                    }
-                }
                 fstep = ray_fix_slope(r.dmin, r.dmaj);
                 const int key = ray_key(ddx, ddy, fstep);
                 atomicAdd(&bins32[key >> 1], 1u << ((key & 1) * 16));
@@ -322,77 +212,21 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
                 if (nfull >= 1) atomicAdd(&s_lcnt[min(nfull, MAXLEV)], 1);
             }
             r_dmaj[b] = (uint16_t)(r.n > 0 ? r.dmaj : 0);
-            r_info[b] = (uint8_t)info;
+            r_info[b] = (uint8_t)br.info;
             r_fstep[b] = fstep;
         }
-        {
-            const int ws = wave_sum((int)my_cells);
-            fx0 = wave_min(fx0); fx1 = wave_max(fx1); fy0 = wave_min(fy0); fy1 = wave_max(fy1);
-            if (lane == 0) {
-                atomicAdd(&s_cells, (unsigned long long)ws);
-                atomicMin(&s_fan[0], fx0); atomicMax(&s_fan[1], fx1);
-                atomicMin(&s_fan[2], fy0); atomicMax(&s_fan[3], fy1);
-            }
-        }
+        fan_box_join(fan, lane, s_fan, &s_cells);
     }
     __syncthreads();
     STAMP(0);
-    // ---- the window: the fan's bounding box in global cell indices; strips of storage rows if it does not fit ----
-    const int bxl = UNI(s_fan[0]), bxh = UNI(s_fan[1]), byl = UNI(s_fan[2]), byh = UNI(s_fan[3]);
-    // the reference's index formula over the fan (one column more on either side): U(g) = g + C - G(g) with G in {0, 1}
-    for (int i = tid; i < G.fanw; i += RB) {
-        const int dxg = (fxl + i + C) - (int)ux[i], dyg = (fyl + i + C) - (int)uy[i];
-        if (fxl + i >= bxl - 1 && fxl + i <= bxh + 1 && (unsigned)dxg > 1u) s_fb = 1;   // also: the LUT ends inside the fan
-        if (fyl + i >= byl - 1 && fyl + i <= byh + 1 && (unsigned)dyg > 1u) s_fb = 1;
-        gxb[i] = (uint8_t)(dxg & 1); gyb[i] = (uint8_t)(dyg & 1);
-    }
-    const int S_lo = UNI(ux[bxl - fxl]), S_hi = UNI(ux[bxh - fxl]);           // storage rows / columns the fan can write
-    const int T_lo = UNI(uy[byl - fyl]), T_hi = UNI(uy[byh - fyl]);
-    const int gy_base = (T_lo - C) & ~3;                                      // window column 0 (C is a multiple of 4)
-    int stride = (T_hi - C + 2 - gy_base + 3) & ~3;                           // columns gy_base .. T_hi - C + 1
-    if (((stride >> 2) & 1) == 0) stride += 4;                                // rows an odd number of banks apart
-    const int rows_cap = G.ncell / stride;                                    // global rows a window can hold
+    // ---- the window (rbpf_mapupdate.h: strips of storage rows if the fan does not fit) ----
+    const StripGeom sg = strip_geom<RB>(ux, uy, gxb, gyb, G.fanw, fxl, fyl, C, s_fan, &s_fb, G.ncell, tid);
+    const int S_lo = sg.S_lo, S_hi = sg.S_hi, T_lo = sg.T_lo, gy_base = sg.gy_base, stride = sg.stride, rows_cap = sg.rows_cap;
     BAR_LDS();
     if (UNI(s_fb) || rows_cap < 8) { GIVE_BACK(1); }
-    if (tid < LL && s_need[tid] && s_tab[tid] < 0) {                          // allocate missing tiles (kept zero-filled)
-        int idx = atomicSub(v.free_top, 1) - 1;
-        if (idx < 0) {
-            atomicAdd(v.free_top, 1);
-            atomicCAS(v.err, 0, RBPF_ENOMEM);
-            s_need[tid] = 0;
-        } else {
-            int t = v.free_stack[idx];
-            s_tab[tid] = t;
-            tab[tid] = t;
-            v.tile_bbox[4 * t + 0] = INT_MAX; v.tile_bbox[4 * t + 1] = -1;
-            v.tile_bbox[4 * t + 2] = INT_MAX; v.tile_bbox[4 * t + 3] = -1;
-        }
-    }
-    if (wave == 0) {   // levels: N_k = rays with at least k whole chunks (suffix sums over the wave: MAXLEV = 63)
-        const int k = lane;                                                    // lane 0 is unused (level 0 = the 16-bit block)
-        const int ck = k >= 1 ? s_lcnt[k] : 0;
-        int suf = ck;
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(suf, o, 64); if (lane + o < 64) suf += t; }
-        // suf = N_k; rays with more chunks come first in perm
-        const int nwk = k >= 1 ? (suf + 63) >> 6 : 0;
-        int pre = nwk;                                                         // inclusive prefix of the levels' wave counts
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(pre, o, 64); if (lane >= o) pre += t; }
-        const unsigned long long live = __ballot(k >= 1 && suf > 0);
-        const int nlev = live ? 63 - __clzll((long long)live) : 0;
-        if (k >= 1) { s_lfill[k] = suf - ck; s_nk[k] = suf; s_lp[k] = pre - nwk; }
-        if (k == 63) s_lp[64] = pre;
-        if (k == 0) { s_nlev = nlev; s_nk[MAXLEV + 1] = 0; }
-    }
-    for (int lc = tid; lc < stride + 16 && lc < G.fanw + 16; lc += RB) {       // column glitch mask in window coordinates
-        const int i = lc + gy_base - fyl;
-        const bool gl = i >= 0 && i < nfx && gyb[i];
-        gym[lc] = gl ? 0xFFu : 0u;
-        if (gl) {   // the write-back's 32-column groups that see this column: its own and, for a group's first four columns, the one before
-            const int sc = lc + gy_base + C, g = (sc >> 5) - (T_lo >> 5);
-            if ((unsigned)g < 96u) s_ggf[g] = 1;
-            if ((sc & 31) < 4 && (unsigned)(g - 1) < 96u) s_ggf[g - 1] = 1;
-        }
-    }
+    alloc_missing_tiles(v, tab, s_need, s_tab, tid);
+    if (wave == 0) level_sums(lane, s_lcnt, s_lfill, s_nk, s_lp, &s_nlev);
+    glitch_mask<RB>(gyb, gym, s_ggf, T_lo >> 5, 96, sg, G.fanw, fyl, nfx, C, v.dim, v.dim >> 5, tid);
     uint32_t* const farh = cnt;                                                // [8 * NBIN] 16-bit counts of the rays longer than the 16-bit block (the window is not in use yet)
     farh[tid] = 0;
     {   // bucket fill pointers: exclusive prefix sum over the 2048 (class, bucket) counts, two per thread
@@ -470,19 +304,12 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
     // keeps the (beam, rank) events; cells that rays of another class can reach too (on an axis or a diagonal through the
     // sensor) are finished by a second, dense pass with one lane per (cell, class).  The counter window is not in use yet:
     // the event lists live there.
-    const int sat = (v.cc.vmax - v.cc.vmin + (-v.cc.emp) - 1) / (-v.cc.emp);        // hits that saturate any cell: 20
+    const int sat = sat_passes(v.cc);                                              // hits that saturate any cell: 20
     const int npair = 2 * G.bpad;
     uint32_t* const evn32 = cnt;                                                   // [npair] 16-bit event counts
     uint16_t* const evl = reinterpret_cast<uint16_t*>(cnt + npair / 2);            // [npair][ECAP] (beam << 3) | rank
     uint16_t* const spl = evl + npair * ECAP;                                      // [RSPEC] pairs that need the other classes
-    struct FCell { int sx, sy; int gx0, gx1, gy0, gy1; int ngx, ngy; };            // storage cell and its source global cells (scalars: no indexed arrays)
-    auto cell_sources = [&](uint32_t sc, FCell& f) {
-        f.sx = (int)(sc >> 16); f.sy = (int)(sc & 0xFFFFu);
-        const int ax = f.sx - C, ay = f.sy - C;                                     // sources: a (if not glitched), a + 1 (if glitched)
-        const bool xa = !gxb[ax - fxl], xb = gxb[ax + 1 - fxl], ya = !gyb[ay - fyl], yb = gyb[ay + 1 - fyl];
-        f.ngx = (xa ? 1 : 0) + (xb ? 1 : 0); f.gx0 = xa ? ax : ax + 1; f.gx1 = ax + 1;
-        f.ngy = (ya ? 1 : 0) + (yb ? 1 : 0); f.gy0 = ya ? ay : ay + 1; f.gy1 = ay + 1;
-    };
+    auto sources = [&](uint32_t sc, FCell& f) { cell_sources(sc, C, gxb, gyb, fxl, fyl, f); };
     auto old_value = [&](const FCell& f) {
         const int a = a0 + (f.sx >= (a0 + 1) * v.dim ? 1 : 0) - (f.sx < a0 * v.dim ? 1 : 0);   // rays are shorter than a tile
         const int bb = b0 + (f.sy >= (b0 + 1) * v.dim ? 1 : 0) - (f.sy < b0 * v.dim ? 1 : 0);
@@ -669,7 +496,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
             const int cls = steep * 4 + (ex > 0 ? 2 : 0) + (ey > 0 ? 1 : 0);
             const int cst = bkt_start(cls * NBIN), cen = bkt_end(cls * NBIN + NBIN - 1);
             FCell f;
-            cell_sources(pair_cell(mykey), f);
+            sources(pair_cell(mykey), f);
             oldv = old_value(f);                                                   // in flight during the scan
             // sources along the major and the minor axis of the class frame
             const int gmaj0 = steep ? f.gy0 : f.gx0, gmaj1 = steep ? f.gy1 : f.gx1, nmaj = steep ? f.ngy : f.ngx;
@@ -834,7 +661,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
             load_ray(b, me);
             if (cls == me.steep * 4 + (me.ex > 0 ? 2 : 0) + (me.ey > 0 ? 1 : 0)) continue;      // done in pass 1
             FCell f;
-            cell_sources(pair_cell(pair), f);
+            sources(pair_cell(pair), f);
             // slope buckets of this class that can hold a ray through one of the sources
             const int steep = cls >> 2, smaj = steep ? ((cls & 1) ? 1 : -1) : ((cls & 2) ? 1 : -1), smin = steep ? ((cls & 2) ? 1 : -1) : ((cls & 1) ? 1 : -1);
             int blo = NBIN, bhi = -1;
@@ -918,7 +745,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
                     int need = 0;
                     if (id < nnear) {
                         FCell f;
-                        cell_sources(pair_cell(nearl[id]), f);
+                        sources(pair_cell(nearl[id]), f);
 #pragma unroll
                         for (int ix = 0; ix < 2; ++ix)
 #pragma unroll
@@ -946,7 +773,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
                 uint16_t* const sp = wsp + wave * NSPC;
                 int* const ic = wcnt + wave * (NSPC + 1);
                 FCell f;
-                cell_sources(pair_cell(key), f);
+                sources(pair_cell(key), f);
                 const int val0 = lane == 0 ? old_value(f) : 0;
                 bool ok = beg + m <= nend[id] && nend[id] > beg;
                 // the occupied / nearby events, sorted by (beam, rank)
@@ -1016,7 +843,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
         for (int k = 0; k < nslow; ++k) {
             const int key = UNI(slowl[k]);
             FCell f;
-            cell_sources(pair_cell(key), f);
+            sources(pair_cell(key), f);
             const int val0 = tid == 0 ? old_value(f) : 0;
             for (int base = 0; base < v.B; base += RB) {
                 const int b = base + tid;
@@ -1061,17 +888,13 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
     STAMP(3);
 
     // =============================================== windows ==============================================
-    const uint32_t satb = (uint32_t)sat * 0x01010101u, sadd = (128u - (uint32_t)sat) * 0x01010101u;
+    const WbConsts wbk = wb_consts(v.cc);
     int n_win = 0;
     for (int S0 = S_lo; S0 <= S_hi; S0 += rows_cap - 1, ++n_win) {
         const int S1 = min(S_hi, S0 + rows_cap - 2);                             // storage rows S0..S1
         const int gx_base = S0 - C, rows_w = S1 - S0 + 2;                        // global rows gx_base .. gx_base + rows_w - 1
         BAR_LDS();                                                               // the previous window is done with the counters
-        {
-            uint4* c4 = reinterpret_cast<uint4*>(cnt);
-            const int n16 = (rows_w * stride + 15) >> 4;
-            for (int i = tid; i < n16; i += RB) c4[i] = make_uint4(0, 0, 0, 0);
-        }
+        for (int i = tid; i < (rows_w * stride + 15) >> 4; i += RB) reinterpret_cast<uint4*>(cnt)[i] = make_uint4(0, 0, 0, 0);
         BAR_LDS();
         STAMP(4);
         // ---- walk: lanes are rays, a work item is one 16-step chunk of 64 rays ----
@@ -1245,7 +1068,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
             const uint32_t ov = oval[pr];
             if (ov == 0xFFu) continue;
             FCell f;
-            cell_sources(pair_cell(pr), f);
+            sources(pair_cell(pr), f);
             if (f.sx < S0 || f.sx > S1) continue;
 #pragma unroll
             for (int ix = 0; ix < 2; ++ix)
@@ -1259,125 +1082,9 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
         if (tid == 0) s_wbq = 0;
         BAR_LDS();
         STAMP(6);
-        // ---- write-back: one read-modify-write per touched 32-cell group of storage cells, tile by tile ----
-        {
-            int my_written = 0;
-            const int eabs = -v.cc.emp;
-            const uint32_t kb1 = (uint32_t)(128 + v.cc.vmin) * 0x01010101u;             // byte-wise: (cell ^ 0x80) - kb1 = cell - vmin
-            const uint32_t oadd = (uint32_t)(127 - (v.cc.thr - v.cc.vmin)) * 0x01010101u; // bit 7 of (R + oadd) = cell > thr
-            const int gpt = v.dim >> 5;                                                // 32-cell groups per tile row
-            // waves draw batches of 64 items (32-cell groups) from a queue (as kernels_mapev.hip: the rows at a fan's rim hold few
-            // touched groups, a fixed share per wave leaves the workgroup waiting for its slowest wave)
-            auto next_batch = [&]() -> int { int g = 0; if (lane == 0) g = atomicAdd(&s_wbq, 1); return UNI(g); };
-            int batch = next_batch(), batch0 = 0;
-            for (int a = S0 / v.dim; a <= S1 / v.dim; ++a)
-            for (int bt = T_lo / v.dim; bt <= T_hi / v.dim; ++bt) {
-                if (a >= v.L || bt >= v.L || !s_need[a * v.L + bt]) continue;          // uniform
-                const int tile = UNI(s_tab[a * v.L + bt]);
-                if (tile < 0) continue;
-                const int sr_lo = max(S0, a * v.dim), sr_hi = min(S1, (a + 1) * v.dim - 1);      // storage rows
-                const int g_lo = max(T_lo >> 5, bt * gpt), g_hi = min(T_hi >> 5, (bt + 1) * gpt - 1);
-                const int ngr = g_hi - g_lo + 1, items = (sr_hi - sr_lo + 1) * ngr;
-                int8_t* __restrict__ tile_base = v.pool + (size_t)tile * v.dim * v.dim;
-                int bx0 = INT_MAX, bx1 = -1, by0 = INT_MAX, by1 = -1;
-                const int nbatch = (items + 63) >> 6;
-                const float inv_ngr = 1.0f / (float)ngr;
-                for (; batch < batch0 + nbatch; batch = next_batch()) {
-                    const int it = ((batch - batch0) << 6) + lane;
-                    if (it >= items) continue;
-                    const int rr = (int)(((float)it + 0.5f) * inv_ngr), gg = it - rr * ngr;   // it / ngr (kernels_mapev.hip has the error bound)
-                    const int srow = sr_lo + rr, Gy = g_lo + gg;
-                    const int ia = srow - C - fxl;                                     // source rows a (if not glitched), a + 1 (if glitched)
-                    const bool va = !gxb[ia], vb = gxb[ia + 1];
-                    if (!va && !vb) continue;                                          // no global row maps here
-                    const int lr = srow - C - gx_base;                                 // window row of source a
-                    const int lc0 = 32 * Gy - C - gy_base;                             // window column of the group's first cell, multiple of 4
-                    uint32_t n[8];
-                    uint32_t any = 0;
-                    const bool both = va && vb;
-                    if (!both && !s_ggf[Gy - (T_lo >> 5)]) {   // one source row, no glitched column: the fields are the group's counts
-                        const int rowo = (lr + (va ? 0 : 1)) * stride + lc0;
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) {
-                            const int lc = lc0 + 4 * w;
-                            n[w] = (lc >= 0 && lc < stride) ? cnt[(rowo + 4 * w) >> 2] : 0u;
-                            any |= n[w];
-                        }
-                    } else {
-                        // glitched columns in the group (its 32 cells and the one after)
-                        uint32_t gm[9];
-#pragma unroll
-                        for (int w = 0; w < 9; ++w) {
-                            const int lc = lc0 + 4 * w;
-                            gm[w] = (lc >= 0 && lc < stride + 12) ? *reinterpret_cast<const uint32_t*>(gym + lc) : 0u;
-                        }
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) n[w] = 0;
-                        for (int src = 0; src < 2; ++src) {
-                            if (src == 0 ? !va : !vb) continue;
-                            const int row = lr + src;
-                            uint32_t x[9];
-#pragma unroll
-                            for (int w = 0; w < 9; ++w) {
-                                const int lc = lc0 + 4 * w;
-                                x[w] = (lc >= 0 && lc < stride) ? cnt[(row * stride + lc) >> 2] : 0u;
-                            }
-#pragma unroll
-                            for (int w = 0; w < 9; ++w) x[w] = premin4(x[w], satb, sadd);
-#pragma unroll
-                            for (int w = 0; w < 8; ++w) {
-                                const uint32_t keep = x[w] & ~gm[w];
-                                const uint32_t mv = ((x[w] & gm[w]) >> 8) | ((x[w + 1] & gm[w + 1]) << 24);
-                                n[w] += keep + mv;
-                            }
-                        }
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) any |= n[w];
-                    }
-                    if (!any) continue;
-                    const int row_t = srow - a * v.dim, col_t = 32 * Gy - bt * v.dim;
-                    uint32_t* g_ptr = reinterpret_cast<uint32_t*>(tile_base + (size_t)row_t * v.dim + col_t);
-                    const uint4 q0 = reinterpret_cast<const uint4*>(g_ptr)[0], q1 = reinterpret_cast<const uint4*>(g_ptr)[1];
-                    const uint32_t pre[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-                    uint32_t occ = 0, touched = 0, out[8];
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) {
-                        // branch-free (a word without hits passes through unchanged: dec = 0, no flag, nz = 0)
-                        const uint32_t Ob = (pre[w] ^ 0x80808080u) - kb1;                   // cells biased to [0, vmax - vmin]
-                        const uint32_t nw = n[w], n7 = nw & 0x7F7F7F7Fu;
-                        const uint32_t ge = (n7 + sadd) & 0x80808080u;                      // fields >= sat
-                        const uint32_t gem = ge | (ge - (ge >> 7));
-                        const uint32_t m = (satb & gem) | (n7 & ~gem);                      // min(n, sat)
-                        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-                        const uint32_t dec = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, m) * (us2)(unsigned short)eabs);   // byte-wise: sat * |emp| < 128, no carries
-                        const uint32_t T1 = (Ob | 0x80808080u) - dec;
-                        const uint32_t pos = T1 & 0x80808080u;                              // O - dec >= 0
-                        uint32_t R = T1 & 0x7F7F7F7Fu & (pos | (pos - (pos >> 7)));
-                        const uint32_t fl = nw & 0x80808080u;                               // replayed cells: the field holds value - vmin
-                        const uint32_t flm = fl | (fl - (fl >> 7));
-                        R = (n7 & flm) | (R & ~flm);
-                        out[w] = (R + kb1) ^ 0x80808080u;
-                        const uint32_t nz = ((n7 + 0x7F7F7F7Fu) | nw) & 0x80808080u;        // fields that are not zero
-                        touched |= __builtin_amdgcn_udot4(nz >> 7, 0x08040201u, 0u, false) << (4 * w);
-                        occ |= __builtin_amdgcn_udot4(((R + oadd) & 0x80808080u) >> 7, 0x08040201u, 0u, false) << (4 * w);   // cell > thr
-                    }
-                    reinterpret_cast<uint4*>(g_ptr)[0] = make_uint4(out[0], out[1], out[2], out[3]);
-                    reinterpret_cast<uint4*>(g_ptr)[1] = make_uint4(out[4], out[5], out[6], out[7]);
-                    my_written += __popc(touched);
-                    by0 = min(by0, col_t + __ffs(touched) - 1); by1 = max(by1, col_t + 31 - __clz(touched));
-                    v.occ[((size_t)tile * v.dim + row_t) * v.ow + (col_t >> 5)] = occ;
-                    bx0 = min(bx0, row_t); bx1 = max(bx1, row_t);
-                }
-                batch0 += nbatch;
-                bx0 = wave_min(bx0); bx1 = wave_max(bx1); by0 = wave_min(by0); by1 = wave_max(by1);
-                if (lane == 0 && bx1 >= 0) {                                           // this workgroup is the tile's only writer
-                    atomicMin(&v.tile_bbox[4 * tile + 0], bx0); atomicMax(&v.tile_bbox[4 * tile + 1], bx1);
-                    atomicMin(&v.tile_bbox[4 * tile + 2], by0); atomicMax(&v.tile_bbox[4 * tile + 3], by1);
-                }
-            }
-            const int ww = wave_sum(my_written);
-            if (lane == 0 && ww) atomicAdd(&s_written, ww);
-        }
+        // ---- write-back (rbpf_mapupdate.h) ----
+        strip_write_back<FIELD_REPLAY_BIT7, false, false, true>(v, sg, S0, S1, gx_base, C, fxl, T_lo >> 5, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
+                                                                &s_wbq, &s_written, false, lane);
         BAR_LDS();
         STAMP(7);
     }
@@ -1386,9 +1093,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
         if (s_cells) atomicAdd(&v.stats[ST_RAY_CELLS], s_cells);
         if (s_written) atomicAdd(&v.stats[ST_CELLS_WRITTEN], (unsigned long long)s_written);
         atomicAdd(&v.stats[ST_MAP_WINDOWS], (unsigned long long)n_win);
-#ifdef RBPF_STAMPS
-        for (int k = 0; k < 8; ++k) atomicAdd(&v.stats[8 + k], (unsigned long long)st_acc[k]);
-#endif
+        STAMP_FLUSH();
     }
 }
 

@@ -26,15 +26,6 @@
 
 namespace rbpf {
 
-// Diagnostic build only (-DRBPF_STAMPS): thread 0 of every workgroup sums the cycles between phase boundaries;
-// the sums go to the reserved counters and are never read by the kernel.
-#ifdef RBPF_STAMPS
-#define STAMP(k) do { if (tid == 0) { long long t_ = clock64(); st_acc[k] += t_ - st_prev; st_prev = t_; } } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
-
 static const int MU_BLOCK = 512;       // 8 waves per particle
 static const int NB_MAX = 1536;        // bucket ids per window (flagged cells beyond it take the membership-scan path)
 static const int EV_TOT = 4096;        // event slots per window
@@ -72,7 +63,6 @@ struct MuLds {
 
 __device__ __forceinline__ uint32_t cnt16_get(const uint32_t* cnt, int c) { return (cnt[c >> 1] >> ((c & 1) * 16)) & 0xFFFFu; }
 __device__ __forceinline__ void cnt16_set(uint32_t* cnt, int c, uint32_t val) { reinterpret_cast<uint16_t*>(cnt)[c] = (uint16_t)val; }
-__device__ __forceinline__ bool flag_get(const uint32_t* flag, int c) { return (flag[c >> 5] >> (c & 31)) & 1u; }
 
 
 // first global index g in [lo, hi] whose storage index fan[g - f0] is >= target (hi + 1 if none), from a close guess
@@ -134,9 +124,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
     const int KW = (v.dim + WIN - 1) / WIN;        // windows per tile axis
     int32_t* tab = v.tile_tab + (size_t)v.slot[p] * LL;
 
-#ifdef RBPF_STAMPS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = clock64();
-#endif
+    STAMP_DECL;
     // =============================================== setup ===============================================
     if (tid == 0) {
         double px = v.upd_pose[p], py = v.upd_pose[v.P + p], th = v.upd_pose[2 * v.P + p];
@@ -145,14 +133,9 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
         s_c = cs; s_s = sn; s_px = px; s_py = py;
         int x0 = trunc_to_int(px / v.cs), y0 = trunc_to_int(py / v.cs);      // hybridmap.py:102
         s_x0 = x0; s_y0 = y0;
-        // hybridmap.py:98-100: no tile holds the robot position -> the update is a no-op
-        int lx, ly;
-        bool ok = tile_of_coord(px, v.tile_len, v.R, lx) && tile_of_coord(py, v.tile_len, v.R, ly);
-        if (ok) ok = tab[(lx + v.R) * v.L + (ly + v.R)] >= 0;
-        const int reach = v.reach;                 // the whole fan must stay inside the LUT (lattice radius)
-        bool in_lut = lut_valid_g(v, x0 - reach) && lut_valid_g(v, x0 + reach) &&
-                      lut_valid_g(v, y0 - reach) && lut_valid_g(v, y0 + reach);
-        if (ok && !in_lut) { atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }
+        // hybridmap.py:98-100: no tile holds the robot position -> the update is a no-op; the whole fan must stay inside the LUT
+        bool ok = home_tile_ok(v, tab, px, py);
+        if (ok && !lut_covers(v, x0, y0, v.reach)) { atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }
         s_skip = ok ? 0 : 1;
         s_fan[0] = x0; s_fan[1] = x0; s_fan[2] = y0; s_fan[3] = y0;
         s_cells = 0; s_tot_written = 0; s_tot_slow = 0;
@@ -164,67 +147,15 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
     const int x0 = UNI(s_x0), y0 = UNI(s_y0);
     const int a0 = lut_lat(lut_at(v, x0)), b0 = lut_lat(lut_at(v, y0));
     {
-        unsigned long long my_cells = 0;
-        int fx0 = x0, fx1 = x0, fy0 = y0, fy1 = y0;
+        FanBox fan = {x0, x0, y0, y0, 0ull};
+        auto lat_x = [&](int g) { return (int)lut_lat(lut_at(v, g)); };
         for (int b = tid; b < v.B; b += MU_BLOCK) {
-            const double x = v.bx[b], y = v.by[b];
-            const int bf = v.bflags[b];
-            double gx = (s_c * x + (-s_s) * y) + s_px;                             // lidar.py:123
-            double gy = (s_s * x + s_c * y) + s_py;
-            int x1 = trunc_to_int(gx / v.cs), y1 = trunc_to_int(gy / v.cs);        // hybridmap.py:106
-            if (bf & BF_LONG) {                                                    // hybridmap.py:107-113
-                double sc = v.bscale[b];
-                x1 = trunc_to_int((double)x0 + sc * (double)(x1 - x0));
-                y1 = trunc_to_int((double)y0 + sc * (double)(y1 - y0));
-            }
-            int ddx = x1 - x0, ddy = y1 - y0;
-            if (ddx < -v.reach || ddx > v.reach || ddy < -v.reach || ddy > v.reach) {
-                atomicCAS(v.err, 0, RBPF_ERANGE);
-                ddx = 0; ddy = -1; x1 = x0; y1 = y0 - 1;                           // degenerate: no points
-            }
-            s.r_end[b] = (int32_t)(((uint32_t)ddx & 0xFFFFu) | ((uint32_t)ddy << 16));
-            Ray r = ray_make(x0, y0, x1, y1);
-            int info = 0;
-            if (r.n > 0) {
-                info = RI_VALID | ((bf & BF_LONG) ? 0 : RI_OCC);
-                my_cells += (unsigned long long)r.n;
-                fx0 = min(fx0, x1); fx1 = max(fx1, x1); fy0 = min(fy0, y1); fy1 = max(fy1, y1);
-                if (r.n >= 2 && (info & RI_OCC)) {                                 // hybridmap.py:139-142
-                    int nx, ny;
-                    ray_point(r, r.n - 2, nx, ny);
-                    if (same_tile(v, nx, ny, x1, y1)) info |= RI_NEAR;
-                    info |= ((nx - x1 + 1) & 3) << 3;
-                    info |= ((ny - y1 + 1) & 3) << 5;
-                }
-                // tiles entered by this ray (staircase start -> [corner] -> end)
-                const int a1 = lut_lat(lut_at(v, x1)), b1 = lut_lat(lut_at(v, y1));
-                s_need[a0 * v.L + b0] = 1;
-                if (a1 != a0 || b1 != b0) {
-                    s_need[a1 * v.L + b1] = 1;
-                    if (a1 != a0 && b1 != b0) {
-                        // first global index on the far side of each boundary, in the ray's direction
-                        int gxb = r.sx > 0 ? v.gwin[a1 * (KW + 1)] : v.gwin[a0 * (KW + 1)] - 1;
-                        int gyb = r.sy > 0 ? v.gwin[b1 * (KW + 1)] : v.gwin[b0 * (KW + 1)] - 1;
-                        int ox = gxb - x0; ox = ox < 0 ? -ox : ox;
-                        int oy = gyb - y0; oy = oy < 0 ? -oy : oy;
-                        int jx = r.steep ? first_j_minor_ge(r, ox) : ox;
-                        int jy = r.steep ? oy : first_j_minor_ge(r, oy);
-                        if (jx < jy) s_need[a1 * v.L + b0] = 1;
-                        else if (jy < jx) s_need[a0 * v.L + b1] = 1;
-                    }
-                }
-            }
-            s.r_info[b] = (uint8_t)info;
+            const BeamRay br = beam_ray(v, v.bx[b], v.by[b], (int)v.bflags[b], [&] { return v.bscale[b]; }, s_s, s_c, s_px, s_py, x0, y0, a0, b0,
+                                        lat_x, lat_x, s_need, fan);
+            s.r_end[b] = (int32_t)(((uint32_t)(br.x1 - x0) & 0xFFFFu) | ((uint32_t)(br.y1 - y0) << 16));
+            s.r_info[b] = (uint8_t)br.info;
         }
-        {
-            const int ws = wave_sum((int)my_cells);                      // < 64 * 16 rays * 2^16 steps
-            fx0 = wave_min(fx0); fx1 = wave_max(fx1); fy0 = wave_min(fy0); fy1 = wave_max(fy1);
-            if ((tid & 63) == 0) {
-                atomicAdd(&s_cells, (unsigned long long)ws);
-                atomicMin(&s_fan[0], fx0); atomicMax(&s_fan[1], fx1);
-                atomicMin(&s_fan[2], fy0); atomicMax(&s_fan[3], fy1);
-            }
-        }
+        fan_box_join(fan, tid & 63, s_fan, &s_cells);
     }
     __syncthreads();
     // the storage index of every global column of the fan, once per particle (the window loop never reads the LUT again)
@@ -234,21 +165,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
         s.fanx[i] = lut_valid_g(v, gxq) ? (uint16_t)lut_cidx(lut_at(v, gxq)) : 0xFFFFu;
         s.fany[i] = lut_valid_g(v, gyq) ? (uint16_t)lut_cidx(lut_at(v, gyq)) : 0xFFFFu;
     }
-    // allocate missing tiles (free tiles are kept zero-filled)
-    if (tid < LL && s_need[tid] && s_tab[tid] < 0) {
-        int idx = atomicSub(v.free_top, 1) - 1;
-        if (idx < 0) {
-            atomicAdd(v.free_top, 1);
-            atomicCAS(v.err, 0, RBPF_ENOMEM);
-            s_need[tid] = 0;
-        } else {
-            int t = v.free_stack[idx];
-            s_tab[tid] = t;
-            tab[tid] = t;
-            v.tile_bbox[4 * t + 0] = INT_MAX; v.tile_bbox[4 * t + 1] = -1;
-            v.tile_bbox[4 * t + 2] = INT_MAX; v.tile_bbox[4 * t + 3] = -1;
-        }
-    }
+    alloc_missing_tiles(v, tab, s_need, s_tab, tid);
     __syncthreads();
 
     STAMP(0);
@@ -698,9 +615,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
         if (s_cells) atomicAdd(&v.stats[ST_RAY_CELLS], s_cells);
         if (s_tot_written) atomicAdd(&v.stats[ST_CELLS_WRITTEN], (unsigned long long)s_tot_written);
         if (s_tot_slow) atomicAdd(&v.stats[ST_SLOW_CELLS], (unsigned long long)s_tot_slow);
-#ifdef RBPF_STAMPS
-        for (int k = 0; k < 8; ++k) atomicAdd(&v.stats[8 + k], (unsigned long long)st_acc[k]);
-#endif
+        STAMP_FLUSH();
     }
 }
 
@@ -722,10 +637,10 @@ int map_update_first_kernel(const DevView& v) {
     // window; on finer grids every fan takes three or four strips, and there the global-index kernel of round 2 (kernels_mapray.hip:
     // no returning adds, a leaner strip set-up) is a quarter faster (8192 x 181 beams x 0.025 m: 0.82 against 1.02 ms per 2048).
     const bool ev_ok = map_update_ev_available(v), ray_ok = map_update_ray_available(v);
-    const bool ev_first = v.mu_mode == 5 || (v.mu_mode == 0 && (v.dim <= 1024 || !ray_ok));
+    const bool ev_first = v.mu_mode == MU_EV || (v.mu_mode == MU_DEFAULT && (v.dim <= 1024 || !ray_ok));
     if (ev_first && ev_ok) return 1;
-    if ((v.mu_mode == 0 || v.mu_mode == 3) && ray_ok) return 2;
-    if (v.mu_mode == 0 && ev_ok) return 1;
+    if ((v.mu_mode == MU_DEFAULT || v.mu_mode == MU_RAY) && ray_ok) return 2;
+    if (v.mu_mode == MU_DEFAULT && ev_ok) return 1;
     return 0;
 }
 

@@ -252,7 +252,7 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
         {   // RBPF_MAP_KERNEL=window keeps the 128x128-window map update for every particle, =ray / =ev run that first kernel (and
             // windows behind it); default: the event-walk kernel, windows for what it gives back (tests, comparisons)
             const char* mk = getenv("RBPF_MAP_KERNEL");
-            v.mu_mode = (mk && std::string(mk) == "window") ? 1 : (mk && std::string(mk) == "ray") ? 3 : (mk && std::string(mk) == "ev") ? 5 : 0;
+            v.mu_mode = (mk && std::string(mk) == "window") ? MU_WINDOW : (mk && std::string(mk) == "ray") ? MU_RAY : (mk && std::string(mk) == "ev") ? MU_EV : MU_DEFAULT;
             const char* ms = getenv("RBPF_MATCH_STAGE");    // "slow": the matcher's field is staged bit by bit (tests)
             v.match_stage_slow = (ms && std::string(ms) == "slow") ? 1 : 0;
             const char* ws = getenv("RBPF_WSAFE");          // test knob: the weighting's guard band in cells (0 shows what the band is for)

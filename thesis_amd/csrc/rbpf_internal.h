@@ -34,6 +34,15 @@ static const int MAX_ITEMS_PER_PARTICLE = 64;
 // beam range classes, computed on the host from the float64 distance (rbpf_set_scan)
 enum { BF_WEIGHT = 1, BF_MATCH = 2, BF_LONG = 4, BF_MATCH_ADJ = 8 };
 
+// The map update's kernels (RBPF_MAP_KERNEL); each first kernel is followed by the 128x128-window kernel for the particles it gives back.
+enum MapKernelMode : int {
+    MU_DEFAULT,    // the event-walk kernel (kernels_mapev.hip) on grids with dim <= 1024, the global-index kernel (kernels_mapray.hip) on
+                   // finer ones, either where the other one is not available (e.g. more than 1536 beams)
+    MU_WINDOW,     // "window": 128x128 windows only (kernels_mapupdate.hip)
+    MU_RAY,        // "ray": the global-index kernel first
+    MU_EV,         // "ev": the event-walk kernel first
+};
+
 // Everything a kernel needs, passed by value.
 struct DevView {
     // configuration
@@ -73,9 +82,7 @@ struct DevView {
     double*  prop_prep;                // [P][24] proposal frame of the current scan update (kernels_propose.hip: U, A, mean, log c)
     double*  prop_samp;                // [P][256] its K samples: cos, sin, pose, motion probability, single-precision frame
     int32_t* mu_fallback;              // [P] != 0: the map-update kernel that ran first gave the particle back to the next one
-    int mu_mode;                       // 0 = event-walk kernel (kernels_mapev.hip; the global-index kernel of round 2, kernels_mapray.hip, where
-                                       // that one is not available: more than 1536 beams), then 128x128 windows for what it gave back;
-                                       // 1 = 128x128 windows only; 3 = global-index kernel, then windows; 5 = event-walk kernel, then windows
+    MapKernelMode mu_mode;             // which map-update kernels run (RBPF_MAP_KERNEL)
     uint32_t* ndt_occ; double* ndt_aux; // NDT stage: the matcher's staged field per particle, its grid optimum (kernels_match.hip)
     int ndt_refine;                    // rbpf_config.ndt_refine: NDT stage of matchScanCustom.m:32-50 (0 off, 1 reference rule, 2 always)
     int32_t* dup_of; int dups_valid;    // representative of each particle's group of exact duplicates since the last resample (kernels_resample.hip); valid until the next proposal

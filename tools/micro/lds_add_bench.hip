@@ -1,5 +1,5 @@
 // Developer microbenchmark (not part of the product): cycles per LDS wave-instruction for the access patterns the map
-// update uses.  One 1024-thread workgroup per CU, 160 KB LDS.  hipcc --offload-arch=gfx950 -O3 -o /tmp/ldsb lds_atomic_bench.hip
+// update uses.  One 1024-thread workgroup per CU, 160 KB LDS.  hipcc --offload-arch=gfx950 -O3 -o /tmp/ldsb lds_add_bench.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>

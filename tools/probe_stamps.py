@@ -1,5 +1,5 @@
 """Diagnostic: per-phase cycles of a map-update kernel under the bench's step (needs a stamped build:
-RBPF_STAMPS=mapray|mapfan python -m thesis_amd.build --force; RBPF_MAP_KERNEL picks the kernel).
+RBPF_STAMPS=mapev|mapray|mapupdate python -m thesis_amd.build --force; RBPF_MAP_KERNEL picks the kernel).
 usage: probe_stamps.py [particles] [warm steps] [measured steps]"""
 import os, sys
 import numpy as np
