@@ -230,12 +230,6 @@ int  rbpf_export_weights_early(rbpf_handle* h, void* d_global_weights_n_plus_1, 
 int  rbpf_resample_indices_global_early(rbpf_handle* h, const void* d_global_weights_n_plus_1, int32_t n_global, double u,
                                         void* stream);
 int  rbpf_resample_indices_global_wait(rbpf_handle* h, int32_t* idx_out, int32_t* did_resample, double* nan_branch_ranks);
-/* serialise n local particles (state + the written boxes of their tiles + occupancy masks) into d_buf;
- * meta_out[n * rbpf_pack_meta_width()] describes the layout for the receiver (host ints) */
-int32_t rbpf_pack_meta_width(rbpf_handle* h);
-int64_t rbpf_packed_particle_bytes(rbpf_handle* h);     /* upper bound of one particle's payload */
-int  rbpf_pack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, void* d_buf, int64_t cap_bytes,
-                         int32_t* meta_out, int64_t* bytes_out);
 /* local part of a global resample: new local particle j continues local particle new_src[j] (sorted ascending)
  * or, for new_src[j] = -1 (last), arrives from another rank and is installed by rbpf_unpack_particles; weights
  * restart at 1.0 (main.py:77-78) */
@@ -246,8 +240,12 @@ int  rbpf_unpack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, 
  * into d_raw ([n][rbpf_pack_raw_width()] int32, device) without waiting; the ranks exchange these records while they
  * are on the device and read their own and the incoming ones back in one copy; (2) records -> the layout rows of
  * rbpf_unpack_particles and the payload size (host only, no device work); (3) the pack with the records already on
- * the host (nothing waited for).  Same payload format as rbpf_pack_particles. */
+ * the host (nothing waited for): the particles' state, the written boxes of their tiles and their occupancy masks,
+ * serialised into d_buf. */
 int32_t rbpf_pack_raw_width(rbpf_handle* h);
+/* meta_out of rbpf_meta_from_raw, meta_in of rbpf_unpack_particles: [n][rbpf_pack_meta_width()] host ints that
+ * describe the payload layout for the receiver */
+int32_t rbpf_pack_meta_width(rbpf_handle* h);
 int  rbpf_gather_pack_meta(rbpf_handle* h, const int32_t* local_idx, int32_t n, void* d_raw);
 int  rbpf_meta_from_raw(rbpf_handle* h, const int32_t* raw, int32_t n, int32_t* meta_out, int64_t* bytes_out);
 int  rbpf_pack_particles_raw(rbpf_handle* h, const int32_t* local_idx, int32_t n, const int32_t* raw, void* d_buf,

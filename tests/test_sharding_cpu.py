@@ -51,8 +51,10 @@ def test_plan_migration_properties(world, p_local, seed):
 
 
 class NumpyShard:
-    """Test double of EngineShard: particles are (13 doubles, 48-byte map tag) records in numpy."""
-    meta_width = 4
+    """Test double of EngineShard: particles are (13 doubles, 48-byte map tag) records in numpy, migrated with the
+    three-step protocol (records exchanged before the pack: rbpf_gather_pack_meta / rbpf_meta_from_raw /
+    rbpf_pack_particles_raw)."""
+    raw_width = 5
 
     def __init__(self, states, tags):
         import torch
@@ -72,18 +74,29 @@ class NumpyShard:
         did, idx = orc.resample_indices(list(w.numpy()), u)
         return did, np.array(idx, dtype=np.int32)
 
-    def pack(self, local_idx):
-        n = len(local_idx)
+    def gather_pack_meta(self, local_idx):
+        rec = np.array([[int(li) + 1000, 176 // 16, 7, 8, 9] for li in local_idx], dtype=np.int32).reshape(-1)
+        return self.torch.from_numpy(rec) if len(rec) else self.torch.empty(0, dtype=self.torch.int32)
+
+    def meta_from_raw(self, raw, n):
+        raw = np.asarray(raw, dtype=np.int32).reshape(n, 5)
+        assert n == 0 or (np.all(raw[:, 2:] == [7, 8, 9]) and np.all(raw[:, 0] >= 1000))
         meta = np.zeros((n, 4), dtype=np.int32)
+        meta[:, 0] = 1
+        meta[:, 1] = raw[:, 1]
+        return meta
+
+    def pack_raw(self, local_idx, raw, nbytes):
+        assert [int(x) - 1000 for x in np.asarray(raw).reshape(-1, 5)[:, 0]] == [int(x) for x in local_idx]
         chunks = []
-        for i, li in enumerate(local_idx):
+        for li in local_idx:
             rec = np.zeros(176, dtype=np.uint8)
             rec[:104] = np.frombuffer(self.states[li].tobytes(), dtype=np.uint8)
             rec[128:176] = self.tags[li]
-            meta[i] = [1, 176 // 16, 0, 0]
             chunks.append(rec)
         pay = self.torch.from_numpy(np.concatenate(chunks)) if chunks else self.torch.empty(0, dtype=self.torch.uint8)
-        return meta, pay
+        assert pay.numel() == nbytes
+        return pay
 
     def empty_payload(self, n):
         return self.torch.empty(n, dtype=self.torch.uint8)
@@ -110,31 +123,7 @@ class NumpyShard:
         return self.states[i][:3]
 
 
-class NumpyShardRaw(NumpyShard):
-    """The same double with the three-step migration protocol of EngineShard (records exchanged before the pack:
-    rbpf_gather_pack_meta / rbpf_meta_from_raw / rbpf_pack_particles_raw), which ShardedResampler prefers."""
-    raw_width = 5
-
-    def gather_pack_meta(self, local_idx):
-        rec = np.array([[int(li) + 1000, 176 // 16, 7, 8, 9] for li in local_idx], dtype=np.int32).reshape(-1)
-        return self.torch.from_numpy(rec) if len(rec) else self.torch.empty(0, dtype=self.torch.int32)
-
-    def meta_from_raw(self, raw, n):
-        raw = np.asarray(raw, dtype=np.int32).reshape(n, 5)
-        assert n == 0 or (np.all(raw[:, 2:] == [7, 8, 9]) and np.all(raw[:, 0] >= 1000))
-        meta = np.zeros((n, 4), dtype=np.int32)
-        meta[:, 0] = 1
-        meta[:, 1] = raw[:, 1]
-        return meta
-
-    def pack_raw(self, local_idx, raw, nbytes):
-        assert [int(x) - 1000 for x in np.asarray(raw).reshape(-1, 5)[:, 0]] == [int(x) for x in local_idx]
-        _, pay = self.pack(local_idx)
-        assert pay.numel() == nbytes
-        return pay
-
-
-def _worker(rank, world, p_local, port, rounds, out_q, flavour="pack"):
+def _worker(rank, world, p_local, port, rounds, out_q):
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
@@ -144,7 +133,7 @@ def _worker(rank, world, p_local, port, rounds, out_q, flavour="pack"):
     rng = np.random.Generator(np.random.PCG64(42))
     states = rng.normal(size=(n, 13)); tags = rng.integers(0, 255, size=(n, 48)).astype(np.uint8)
     sl = slice(rank * p_local, (rank + 1) * p_local)
-    shard = (NumpyShardRaw if flavour == "raw" else NumpyShard)(list(states[sl]), list(tags[sl]))
+    shard = NumpyShard(list(states[sl]), list(tags[sl]))
     sr = ShardedResampler(rank, world, p_local)
     sr.attach(shard)
     history = []
@@ -160,14 +149,14 @@ def _worker(rank, world, p_local, port, rounds, out_q, flavour="pack"):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,p_local,flavour", [(2, 8, "pack"), (2, 33, "raw"), (4, 12, "raw"), (8, 5, "raw"), (8, 5, "pack")])
-def test_sharded_resample_gloo_matches_single_process(world, p_local, flavour):
+@pytest.mark.parametrize("world,p_local", [(2, 8), (2, 33), (4, 12), (8, 5)])
+def test_sharded_resample_gloo_matches_single_process(world, p_local):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
     rounds = 3
-    procs = [ctx.Process(target=_worker, args=(r, world, p_local, port, rounds, q, flavour)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, p_local, port, rounds, q)) for r in range(world)]
     for p in procs:
         p.start()
     results = [q.get(timeout=120) for _ in range(world)]

@@ -518,10 +518,6 @@ __global__ void resample_expand_kernel(int P, const int32_t* __restrict__ T, int
     if (j < P) resample_expand_one(P, T, idx, j);
 }
 __global__ __launch_bounds__(PLAN_THREADS) void resample_pair_kernel(PairArgs a) { resample_pair_stage(a); }
-__global__ void resample_gather_kernel(GatherArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < a.P) resample_gather_one(a, j);
-}
 __global__ __launch_bounds__(PLAN_THREADS) void sources_to_T_kernel(int P, const int32_t* __restrict__ idx, int32_t* __restrict__ T,
                                                                      int32_t* __restrict__ did) { sources_to_T_stage(P, idx, T, did); }
 
@@ -574,9 +570,6 @@ void launch_export_weights(const DevView& v, double* d_out, int n_global, const 
     (void)hipMemsetAsync(d_out, 0, (size_t)(n_global + (d_bad ? 1 : 0)) * 8, s);
     hipLaunchKernelGGL(export_weights_kernel, dim3((v.P + 255) / 256), dim3(256), 0, s, v.P, v.weight, v.global_id, d_out, n_global, d_bad);
 }
-void launch_sources_to_T(int P, const int32_t* d_idx, int32_t* d_T, int32_t* d_did, hipStream_t s) {
-    hipLaunchKernelGGL(sources_to_T_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, P, d_idx, d_T, d_did);
-}
 void launch_gather_meta(const DevView& v, const int32_t* d_local, int n, int32_t* d_out, hipStream_t s) {
     int tot = n * v.L * v.L;
     hipLaunchKernelGGL(gather_meta_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, v, d_local, n, d_out);
@@ -603,48 +596,25 @@ void launch_resample_indices(int P, const double* d_w, double u, double spread, 
     hipLaunchKernelGGL(resample_expand_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, d_T, d_idx);
 }
 
-// the whole local resample (main.py:46-79): plan, ancestors, slot pairing, state permutation, tile copies
+// the whole local resample (main.py:46-79): T and the ancestors, slot pairing, state permutation, tile copies.  The first
+// stage plans from the weights d_w; with d_w == nullptr (the local part of a global resample) it turns the sources already
+// in b.idx (sorted ascending, -1 = arrival, last) into T, and u, spread are unused.
 void launch_resample_local(const DevView& v, const ResampleBuffers& b, const double* d_w, double u, double spread, hipStream_t s) {
-    if (v.P > RS_FUSE_MAX) {
-        launch_resample_indices(v.P, d_w, u, spread, b.T, b.idx, b.did, v.err, s);
-        launch_resample_apply(v, b, s);
-        return;
-    }
+    const PairArgs pa{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err};
+    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
     // the state permutation moves 200 bytes per particle: through one CU it took as long as the three planning stages together
-    // (25 us of the fused kernel's 54 at 4096 particles), so beyond RS_GATHER_FUSE_MAX particles it is a launch of its own
+    // (25 us of the fused kernel's 54 at 4096 particles), so beyond RS_GATHER_FUSE_MAX particles it rides with the tile copies
     const bool fuse_gather = v.P <= RS_GATHER_FUSE_MAX;
-    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
-    FusedArgs f{RS_PLAN | RS_EXPAND | RS_PAIR | (fuse_gather ? RS_GATHER : 0), ResampleArgs{v.P, d_w, u, spread, b.T, b.did, v.err}, b.idx,
-                PairArgs{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err}, ga};
-    launch_resample_fused(f, s);
-    CopyArgs ca{v, b.jobs, b.n_jobs, b.pending_free, b.n_pending, fuse_gather ? 0 : 1, ga};
-    hipLaunchKernelGGL(resample_copy_kernel, dim3(512), dim3(COPY_BLOCK), 0, s, ca);
-    hipLaunchKernelGGL(resample_release_kernel, dim3(1), dim3(256), 0, s, v, b.pending_free, b.n_pending);
-}
-
-// the local part of a global resample: new_src (sorted sources, -1 = arrival) in b.idx -> T, slots, state, tile copies
-void launch_resample_apply_sources(const DevView& v, const ResampleBuffers& b, hipStream_t s) {
-    if (v.P > RS_FUSE_MAX) {
-        launch_sources_to_T(v.P, b.idx, b.T, b.did, s);
-        launch_resample_apply(v, b, s);
-        return;
+    if (v.P > RS_FUSE_MAX) {                                   // the stages one launch each
+        if (d_w) launch_resample_indices(v.P, d_w, u, spread, b.T, b.idx, b.did, v.err, s);
+        else hipLaunchKernelGGL(sources_to_T_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, v.P, b.idx, b.T, b.did);
+        hipLaunchKernelGGL(resample_pair_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, pa);
+    } else {
+        FusedArgs f{(d_w ? RS_PLAN | RS_EXPAND : RS_SRC2T) | RS_PAIR | (fuse_gather ? RS_GATHER : 0),
+                    ResampleArgs{v.P, d_w, u, spread, b.T, b.did, v.err}, b.idx, pa, ga};
+        launch_resample_fused(f, s);
     }
-    const bool fuse_gather = v.P <= RS_GATHER_FUSE_MAX;
-    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
-    FusedArgs f{RS_SRC2T | RS_PAIR | (fuse_gather ? RS_GATHER : 0), ResampleArgs{v.P, nullptr, 0.0, 0.0, b.T, b.did, v.err}, b.idx,
-                PairArgs{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err}, ga};
-    launch_resample_fused(f, s);
     CopyArgs ca{v, b.jobs, b.n_jobs, b.pending_free, b.n_pending, fuse_gather ? 0 : 1, ga};
-    hipLaunchKernelGGL(resample_copy_kernel, dim3(512), dim3(COPY_BLOCK), 0, s, ca);
-    hipLaunchKernelGGL(resample_release_kernel, dim3(1), dim3(256), 0, s, v, b.pending_free, b.n_pending);
-}
-
-void launch_resample_apply(const DevView& v, const ResampleBuffers& b, hipStream_t s) {
-    PairArgs pa{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err};
-    hipLaunchKernelGGL(resample_pair_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, pa);
-    GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight,
-                  b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
-    CopyArgs ca{v, b.jobs, b.n_jobs, b.pending_free, b.n_pending, 1, ga};          // (the state permutation rides with the tile copies)
     hipLaunchKernelGGL(resample_copy_kernel, dim3(512), dim3(COPY_BLOCK), 0, s, ca);
     hipLaunchKernelGGL(resample_release_kernel, dim3(1), dim3(256), 0, s, v, b.pending_free, b.n_pending);
 }

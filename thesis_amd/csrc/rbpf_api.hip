@@ -781,18 +781,28 @@ static void swap_state_buffers(rbpf_handle* h) {
     std::swap(v.cov, r.cov2); std::swap(v.weight, r.w2); std::swap(v.slot, r.slot2);
 }
 
+// the local resample of rbpf_resample (from the weights d_w) and rbpf_apply_resample_local (d_w == nullptr: from the
+// sources in rs.idx), timed; the permuted state becomes current and the kernels wrote the groups of exact duplicates
+// (identity if nothing was resampled; arrivals are their own representatives)
+static int resample_local(rbpf_handle* h, const double* d_w, double u, double spread) {
+    DevView& v = h->v;
+    h->prof_begin(2);
+    launch_resample_local(v, h->rs, d_w, u, spread, h->stream);
+    h->prof_end(2);
+    HIP_TRY(h, hipGetLastError());
+    swap_state_buffers(h);
+    v.dups_valid = h->dedup_enabled ? 1 : 0;
+    return RBPF_OK;
+}
+
 int rbpf_resample(rbpf_handle* h, double u, int32_t* idx_out, int32_t* did_resample) {
     if (!h) return RBPF_EINVAL;
     ON_DEVICE(h);
     DevView& v = h->v;
     if (u != u) u = internal_uniform(h);
     if (!(u >= 0.0 && u < 1.0)) return fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
-    h->prof_begin(2);
-    launch_resample_local(v, h->rs, v.weight, u, h->cfg.resample_spread, h->stream);
-    h->prof_end(2);
-    HIP_TRY(h, hipGetLastError());
-    swap_state_buffers(h);
-    v.dups_valid = h->dedup_enabled ? 1 : 0;            // the kernel wrote the groups of exact duplicates (identity if it did not resample)
+    int rc = resample_local(h, v.weight, u, h->cfg.resample_spread);
+    if (rc) return rc;
     if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, h->rs.idx, (size_t)v.P * 4, hipMemcpyDeviceToHost, h->stream));
     if (did_resample) HIP_TRY(h, hipMemcpyAsync(did_resample, h->rs.did, 4, hipMemcpyDeviceToHost, h->stream));
     if (idx_out || did_resample) return check_device_error(h);
@@ -833,15 +843,23 @@ int rbpf_export_weights_early(rbpf_handle* h, void* d_global, int32_t n_global, 
     return RBPF_OK;
 }
 
-int rbpf_resample_indices_global_early(rbpf_handle* h, const void* d_global, int32_t n_global, double u, void* aux_stream) {
-    if (!h || !d_global || n_global < 1) return RBPF_EINVAL;
-    ON_DEVICE(h);
+// queue the global ancestors of the n_global weights d_global (main.py:46-67) into d_gidx on stream s; did -> d_did
+static int queue_indices_global(rbpf_handle* h, const void* d_global, int32_t n_global, double u, int32_t* d_did, hipStream_t s) {
     if (!(u >= 0.0 && u < 1.0)) return fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
-    hipStream_t s = static_cast<hipStream_t>(aux_stream);
     int rc = scratch(h, &h->d_gT, &h->d_gT_cap, (size_t)n_global);
     if (rc) return rc;
     rc = scratch(h, &h->d_gidx, &h->d_gidx_cap, (size_t)n_global);
     if (rc) return rc;
+    launch_resample_indices(n_global, static_cast<const double*>(d_global), u, h->cfg.resample_spread, h->d_gT, h->d_gidx,
+                            d_did, h->v.err, s);
+    HIP_TRY(h, hipGetLastError());
+    return RBPF_OK;
+}
+
+int rbpf_resample_indices_global_early(rbpf_handle* h, const void* d_global, int32_t n_global, double u, void* aux_stream) {
+    if (!h || !d_global || n_global < 1) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    hipStream_t s = static_cast<hipStream_t>(aux_stream);
     const size_t need = (size_t)n_global * 4 + 16;
     if (need > h->h_early_bytes) {                       // pinned landing zone of the read-back
         if (h->h_early) HIP_TRY(h, hipHostFree(h->h_early));
@@ -850,9 +868,8 @@ int rbpf_resample_indices_global_early(rbpf_handle* h, const void* d_global, int
         HIP_TRY(h, hipHostMalloc(&h->h_early, need, hipHostMallocDefault));
         h->h_early_bytes = need;
     }
-    launch_resample_indices(n_global, static_cast<const double*>(d_global), u, h->cfg.resample_spread, h->d_gT, h->d_gidx,
-                            h->d_did_early, h->v.err, s);
-    HIP_TRY(h, hipGetLastError());
+    int rc = queue_indices_global(h, d_global, n_global, u, h->d_did_early, s);
+    if (rc) return rc;
     unsigned char* dst = static_cast<unsigned char*>(h->h_early);
     void* mapped = nullptr;
     if (hipHostGetDevicePointer(&mapped, dst, 0) == hipSuccess && mapped) {      // one kernel writes the landing zone directly
@@ -885,14 +902,8 @@ int rbpf_resample_indices_global(rbpf_handle* h, const void* d_global, int32_t n
                                  int32_t* did_resample) {
     if (!h || !d_global || !idx_out || !did_resample || n_global < 1) return RBPF_EINVAL;
     ON_DEVICE(h);
-    if (!(u >= 0.0 && u < 1.0)) return fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
-    int rc = scratch(h, &h->d_gT, &h->d_gT_cap, (size_t)n_global);
+    int rc = queue_indices_global(h, d_global, n_global, u, h->rs.did, h->stream);
     if (rc) return rc;
-    rc = scratch(h, &h->d_gidx, &h->d_gidx_cap, (size_t)n_global);
-    if (rc) return rc;
-    launch_resample_indices(n_global, static_cast<const double*>(d_global), u, h->cfg.resample_spread, h->d_gT, h->d_gidx,
-                            h->rs.did, h->v.err, h->stream);
-    HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(idx_out, h->d_gidx, (size_t)n_global * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(did_resample, h->rs.did, 4, hipMemcpyDeviceToHost, h->stream));
     return check_device_error(h);
@@ -917,26 +928,16 @@ int rbpf_apply_resample_local(rbpf_handle* h, const int32_t* new_src, const int3
     const bool by_kernel = hipHostGetDevicePointer(&mapped, slot, 0) == hipSuccess && mapped;
     if (by_kernel) launch_ingest2(static_cast<const int32_t*>(mapped), h->rs.idx, static_cast<const int32_t*>(mapped) + v.P, v.global_id, v.P, h->stream);
     else { (void)hipGetLastError(); HIP_TRY(h, hipMemcpyAsync(h->rs.idx, slot, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream)); }
-    h->prof_begin(2);
-    launch_resample_apply_sources(v, h->rs, h->stream);
-    h->prof_end(2);
-    HIP_TRY(h, hipGetLastError());
-    swap_state_buffers(h);
-    v.dups_valid = h->dedup_enabled ? 1 : 0;            // arrivals are their own representatives
+    int rc = resample_local(h, nullptr, 0.0, 0.0);
+    if (rc) return rc;
     if (!by_kernel) HIP_TRY(h, hipMemcpyAsync(v.global_id, slot + v.P, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream));
     h->ring_idx.submitted(h->stream);
     return RBPF_OK;                                     // no host synchronisation; device errors surface at the next check
 }
 
+// meta record of one particle: [0] tiles, [1] payload bytes / 16, then per lattice position (has, x0, x1, ya, yb, offset / 16)
 int32_t rbpf_pack_meta_width(rbpf_handle* h) { return h ? 2 + 6 * h->v.L * h->v.L : -1; }
 
-int64_t rbpf_packed_particle_bytes(rbpf_handle* h) {
-    if (!h) return -1;
-    const DevView& v = h->v;
-    return 128 + (int64_t)v.L * v.L * ((int64_t)v.dim * v.dim + (int64_t)v.dim * v.ow * 4);
-}
-
-// meta record of one particle: [0] tiles, [1] payload bytes / 16, then per lattice position (has, x0, x1, ya, yb, offset / 16)
 // job lists of the pack / unpack kernels go through one pinned buffer: the copy is asynchronous and the std::vector may
 // die on return; the event tells when the buffer may be overwritten
 static int stage_jobs(rbpf_handle* h, const void* src, size_t bytes) {
@@ -989,34 +990,7 @@ static int64_t layout_packed(const DevView& v, const int32_t* g, int n, const in
     return off;
 }
 
-int rbpf_pack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, void* d_buf, int64_t cap_bytes,
-                        int32_t* meta_out, int64_t* bytes_out) {
-    if (!h || n < 0 || !bytes_out || (n > 0 && (!local_idx || !d_buf || !meta_out))) return RBPF_EINVAL;
-    ON_DEVICE(h);
-    *bytes_out = 0;
-    if (n == 0) return RBPF_OK;
-    DevView& v = h->v;
-    const int LL = v.L * v.L;
-    for (int i = 0; i < n; ++i) if (local_idx[i] < 0 || local_idx[i] >= v.P) return fail(h, RBPF_EINVAL, "local index out of range");
-    int rc = scratch(h, &h->d_i32, &h->d_i32_cap, (size_t)n * (1 + 5 * LL));
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_i32, local_idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    launch_gather_meta(v, h->d_i32, n, h->d_i32 + n, h->stream);
-    std::vector<int32_t> g((size_t)n * LL * 5);
-    HIP_TRY(h, hipMemcpyAsync(g.data(), h->d_i32 + n, g.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    std::vector<PackJobHost> jobs;
-    const int64_t off = layout_packed(v, g.data(), n, local_idx, meta_out, &jobs);
-    if (off > cap_bytes) return fail(h, RBPF_ENOMEM, "pack buffer too small");
-    rc = stage_jobs(h, jobs.data(), jobs.size() * sizeof(PackJobHost));
-    if (rc) return rc;
-    launch_pack(v, h->d_jobs, (int)jobs.size(), d_buf, h->stream);
-    HIP_TRY(h, hipGetLastError());
-    *bytes_out = off;
-    return RBPF_OK;                                     // the buffer is filled in stream order: send it on the handle's stream
-}
-
-// ---- the same in three steps, with one host wait for a whole migration (thesis_amd/sharding.py) --------------------
+// ---- the pack in three steps, with one host wait for a whole migration (thesis_amd/sharding.py) --------------------
 // 1. rbpf_gather_pack_meta: the tile boxes of the departing particles, gathered into a device buffer (nothing waited
 //    for) - the ranks exchange these records while they are still on the device and read their own and the incoming
 //    ones back together;  2. rbpf_meta_from_raw: records -> the layout rows rbpf_unpack_particles takes (host only);

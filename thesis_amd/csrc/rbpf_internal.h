@@ -182,11 +182,8 @@ void launch_imu_update(const DevView& v, int model, double d0, double d1, double
                        const double* vel_noise, hipStream_t s);
 void launch_resample_indices(int P, const double* d_w, double u, double spread, int32_t* d_T, int32_t* d_idx,
                              int32_t* d_did, int32_t* d_err, hipStream_t s);
-void launch_resample_apply(const DevView& v, const ResampleBuffers& b, hipStream_t s);
 void launch_resample_local(const DevView& v, const ResampleBuffers& b, const double* d_w, double u, double spread, hipStream_t s);
-void launch_resample_apply_sources(const DevView& v, const ResampleBuffers& b, hipStream_t s);
 void launch_export_weights(const DevView& v, double* d_out, int n_global, const uint8_t* d_bad, hipStream_t s);
-void launch_sources_to_T(int P, const int32_t* d_idx, int32_t* d_T, int32_t* d_did, hipStream_t s);
 void launch_gather_meta(const DevView& v, const int32_t* d_local, int n, int32_t* d_out, hipStream_t s);
 void launch_pack(const DevView& v, const void* d_jobs, int n_jobs, void* d_buf, hipStream_t s);
 void launch_unpack(const DevView& v, const ResampleBuffers& b, const void* d_jobs, int n_jobs, const void* d_buf, hipStream_t s);

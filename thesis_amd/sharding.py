@@ -151,27 +151,7 @@ class EngineShard:
                                                                idx.ctypes.data_as(_I32), _c.byref(did)))
         return bool(did.value), idx
 
-    def pack(self, local_idx):
-        local_idx = np.ascontiguousarray(local_idx, dtype=np.int32)
-        n = len(local_idx)
-        meta = np.zeros((n, self.meta_width), dtype=np.int32)
-        if n == 0:
-            return meta, self.torch.empty(0, dtype=self.torch.uint8, device=self.device)
-        cap = n * int(self.e._lib.rbpf_packed_particle_bytes(self.e._h))
-        # worst-case capacity can be large: grow on demand from the actual bounding boxes instead
-        cap = min(cap, max(1 << 22, n * (1 << 20)))
-        while True:
-            buf = self.torch.empty(cap, dtype=self.torch.uint8, device=self.device)
-            nbytes = _c.c_int64()
-            rc = self.e._lib.rbpf_pack_particles(self.e._h, local_idx.ctypes.data_as(_I32), n, _vp(buf.data_ptr()), cap,
-                                                 meta.ctypes.data_as(_I32), _c.byref(nbytes))
-            if rc == -2 and cap < n * int(self.e._lib.rbpf_packed_particle_bytes(self.e._h)):
-                cap *= 4
-                continue
-            self.e._check(rc)
-            return meta, buf[:nbytes.value]
-
-    # the same in three steps with a single host wait (rbpf_gather_pack_meta / rbpf_meta_from_raw / rbpf_pack_particles_raw)
+    # the migration in three steps with a single host wait (rbpf_gather_pack_meta / rbpf_meta_from_raw / rbpf_pack_particles_raw)
     @property
     def raw_width(self):
         return int(self.e._lib.rbpf_pack_raw_width(self.e._h))
@@ -314,10 +294,10 @@ class ShardedResampler:
         """Call between scan_update_begin and scan_update_end: the weight export, the collective, the ancestor
         computation and its read-back are queued BEFORE the map update, so that the host gets the ancestors, plans the
         migration and queues the tile copies while the GPU runs the map update.  Falls back to nothing
-        (resample_finish does all the work) for shards without the early calls or a host-staged transport."""
+        (resample_finish does all the work) with a host-staged transport."""
         self._early, self._u = None, u
         sh = self.shard
-        if self.host_staged or not hasattr(sh, "weights_global_early"):
+        if self.host_staged:
             return
         t0 = time.perf_counter()
         wl = sh.weights_global_early(self.n_global)
@@ -358,64 +338,37 @@ class ShardedResampler:
             return False, None
         plan = plan_migration(idx, self.owner, self.local_of, self.world, self.p_local, rank=self.rank)
         t0 = self._tick("plan", t0)
-        r, W = self.rank, sh.meta_width
+        r = self.rank
         if plan.n_move == 0:                                                 # every rank sees the same plan: no exchange
             sh.apply_local(plan.new_src[r], plan.new_gid[r])
             t0 = self._tick("apply_local", t0)
             self._book(plan)
             self.stats["resamples"] += 1
             return True, idx
-        if hasattr(sh, "gather_pack_meta"):
-            # What leaves this rank, ordered by destination.  One host wait for the whole migration: the tile boxes of the
-            # departing particles are gathered on the device, exchanged between the ranks while still there (the counts per
-            # pair of ranks follow from the plan, which every rank holds), and read back together with the incoming ones.
-            n_out = [len(plan.send[r][d]) for d in range(self.world)]
-            n_in = [len(plan.send[q][r]) for q in range(self.world)]
-            leaving = np.concatenate([np.asarray(plan.send[r][d], dtype=np.int32) for d in range(self.world)]) if sum(n_out) else np.zeros(0, dtype=np.int32)
-            RW = sh.raw_width
-            raw_out = sh.gather_pack_meta(leaving)
-            raw_in = self._all_to_all(raw_out, [n * RW for n in n_out], [n * RW for n in n_in], torch.int32)
-            both = torch.cat([raw_out, raw_in]).cpu().numpy()                    # the wait
-            raw_out_h, raw_in_h = both[:sum(n_out) * RW], both[sum(n_out) * RW:]
-            meta_out, meta_in = sh.meta_from_raw(raw_out_h, sum(n_out)), sh.meta_from_raw(raw_in_h, sum(n_in))
-            ends_o, ends_i = np.cumsum(n_out), np.cumsum(n_in)
-            b_out = [int(meta_out[e - n:e, 1].astype(np.int64).sum()) * 16 for n, e in zip(n_out, ends_o)]
-            b_in = [int(meta_in[e - n:e, 1].astype(np.int64).sum()) * 16 for n, e in zip(n_in, ends_i)]
-            pay_send = sh.pack_raw(leaving, raw_out_h, sum(b_out))
-            # the departing particles are packed (stream order): the payload exchange starts, and beside it the local
-            # part - slot pairing, state permutation, tile copies of duplicated ancestors - may reuse their slots
-            if sum(b_out) + sum(b_in) > 0 or self.world > 1:
-                pay_recv, finish = self._all_to_all_begin(pay_send, b_out, b_in, torch.uint8)
-            else:
-                pay_recv, finish = sh.empty_payload(0), (lambda: None)
-            sh.apply_local(plan.new_src[r], plan.new_gid[r])
-            finish()
-        else:                                                                # shards with the one-call pack only (tests)
-            # pack what leaves this rank in ONE call, ordered by destination (one gather of the metadata, one kernel);
-            # the per-destination byte counts follow from the metadata rows (16-byte units in column 1)
-            n_out = [len(plan.send[r][d]) for d in range(self.world)]
-            leaving = np.concatenate([np.asarray(plan.send[r][d], dtype=np.int32) for d in range(self.world)]) if sum(n_out) else np.zeros(0, dtype=np.int32)
-            meta_all, pay_all = sh.pack(leaving)
-            ends = np.cumsum(n_out)
-            b_out = [int(meta_all[e - n:e, 1].astype(np.int64).sum()) * 16 for n, e in zip(n_out, ends)]
-            metas, payloads = [meta_all], [pay_all]
-            # the departing particles are packed (stream order): the local part - slot pairing, state permutation, tile
-            # copies of duplicated ancestors - can run now, while the host exchanges the metadata
-            sh.apply_local(plan.new_src[r], plan.new_gid[r])
-            n_in = [len(plan.send[q][r]) for q in range(self.world)]
-            if sum(n_out) + sum(n_in) > 0 or self.world > 1:
-                dev = payloads[0].device
-                meta_send = torch.from_numpy(np.concatenate(metas).reshape(-1)).to(dev)
-                meta_recv = self._all_to_all(meta_send, [n * W for n in n_out], [n * W for n in n_in], torch.int32)
-                meta_in = meta_recv.cpu().numpy().reshape(-1, W)
-                b_in, k = [], 0
-                for q in range(self.world):
-                    b_in.append(int(meta_in[k:k + n_in[q], 1].astype(np.int64).sum()) * 16)
-                    k += n_in[q]
-                pay_send = torch.cat(payloads) if sum(b_out) else sh.empty_payload(0)
-                pay_recv = self._all_to_all(pay_send, b_out, b_in, torch.uint8)
-            else:
-                meta_in, pay_recv = np.zeros((0, W), dtype=np.int32), sh.empty_payload(0)
+        # What leaves this rank, ordered by destination.  One host wait for the whole migration: the tile boxes of the
+        # departing particles are gathered on the device, exchanged between the ranks while still there (the counts per
+        # pair of ranks follow from the plan, which every rank holds), and read back together with the incoming ones.
+        n_out = [len(plan.send[r][d]) for d in range(self.world)]
+        n_in = [len(plan.send[q][r]) for q in range(self.world)]
+        leaving = np.concatenate([np.asarray(plan.send[r][d], dtype=np.int32) for d in range(self.world)]) if sum(n_out) else np.zeros(0, dtype=np.int32)
+        RW = sh.raw_width
+        raw_out = sh.gather_pack_meta(leaving)
+        raw_in = self._all_to_all(raw_out, [n * RW for n in n_out], [n * RW for n in n_in], torch.int32)
+        both = torch.cat([raw_out, raw_in]).cpu().numpy()                    # the wait
+        raw_out_h, raw_in_h = both[:sum(n_out) * RW], both[sum(n_out) * RW:]
+        meta_out, meta_in = sh.meta_from_raw(raw_out_h, sum(n_out)), sh.meta_from_raw(raw_in_h, sum(n_in))
+        ends_o, ends_i = np.cumsum(n_out), np.cumsum(n_in)
+        b_out = [int(meta_out[e - n:e, 1].astype(np.int64).sum()) * 16 for n, e in zip(n_out, ends_o)]
+        b_in = [int(meta_in[e - n:e, 1].astype(np.int64).sum()) * 16 for n, e in zip(n_in, ends_i)]
+        pay_send = sh.pack_raw(leaving, raw_out_h, sum(b_out))
+        # the departing particles are packed (stream order): the payload exchange starts, and beside it the local
+        # part - slot pairing, state permutation, tile copies of duplicated ancestors - may reuse their slots
+        if sum(b_out) + sum(b_in) > 0 or self.world > 1:
+            pay_recv, finish = self._all_to_all_begin(pay_send, b_out, b_in, torch.uint8)
+        else:
+            pay_recv, finish = sh.empty_payload(0), (lambda: None)
+        sh.apply_local(plan.new_src[r], plan.new_gid[r])
+        finish()
         arrivals = np.nonzero(plan.new_src[r] < 0)[0].astype(np.int32)
         sh.unpack(arrivals, meta_in, pay_recv)
         self._book(plan)
