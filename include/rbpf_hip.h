@@ -272,6 +272,29 @@ int  rbpf_get_dim(rbpf_handle* h, int32_t* out_dim);
 int  rbpf_get_odds_at(rbpf_handle* h, int32_t particle, const double* xy, int32_t n,
                       double* out_vals, uint8_t* out_none);
 
+/* ---- map read-out: dense rasters of one particle's map or of the whole filter ------------------------------------------
+ * Rasters are indexed in mosaic cells.  Tile (a, b) of the lattice (centre ((a-R) tile_len, (b-R) tile_len), as
+ * rbpf_get_tile) holds mosaic cells X = (a-R) dim + i - dim/2, Y = (b-R) dim + j - dim/2 in its storage cell (i, j)
+ * (dim/2 in integer division).  For even dim, (X, Y) is the "cell units" point of get_occupied_points
+ * (hybridmap.py:303-313).  A box is int32 box4 = {x0, x1, y0, y1}, half-open; an output is row-major
+ * [x1-x0][y1-y0], indexed [X-x0][Y-y0] (as cell[x*dim + y]).  Cells outside every tile of a particle, or outside the
+ * lattice, hold log-odds 0 (a fresh tile, gridmap.py:26-35).  Neither call changes any engine state; both return
+ * RBPF_ESTATE between rbpf_scan_update_begin and rbpf_scan_update_end. */
+#define RBPF_RENDER_DEVICE_OUT 1u  /* outputs are device pointers, written in stream order, no host wait */
+/* smallest box holding the written cells (tile_bbox) of every tile of `particle`, or of all particles (-1);
+ * {0, 0, 0, 0} when there is none */
+int  rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4);
+/* particle >= 0: cells = its int8 lattice values (units of quantum); prob, occ_frac and weights NULL.
+ * particle == -1: cells NULL, prob and / or occ_frac; weights NULL (uniform) or P host float64, finite, >= 0, with a
+ * positive sum:   prob[c]     = sum_p w_p sigma(v_p(c) quantum) / sum_p w_p,   sigma(o) = e^o / (1 + e^o) (get_pr_at,
+ *                               hybridmap.py:74-83; 0.5 where no particle has a tile),
+ *                 occ_frac[c] = sum_p w_p [v_p(c) > occupied_threshold / quantum] / sum_p w_p   (gridmap.py:153),
+ * summed in float64 in a fixed order and rounded to float32 once: bit-identical from call to call.  A box of more than
+ * 2^31 cells or a wrong NULL pattern is RBPF_EINVAL, and nothing is written.  Without RBPF_RENDER_DEVICE_OUT the outputs
+ * are host arrays, complete on return. */
+int  rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* weights,
+                     uint32_t flags, int8_t* cells, float* prob, float* occ_frac);
+
 #ifdef __cplusplus
 }
 #endif

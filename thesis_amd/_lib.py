@@ -12,6 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librbpf_hip.so")
 
 RBPF_OK = 0
+RBPF_EINVAL, RBPF_ENOMEM, RBPF_EDEVICE, RBPF_ESTATE, RBPF_ERANGE = -1, -2, -3, -4, -5
+RBPF_RENDER_DEVICE_OUT = 1
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
 
 
@@ -101,6 +103,8 @@ PROTOTYPES = {
     "rbpf_set_tile": (C.c_int, [_H, C.c_int32, C.c_double, C.c_double, _B]),
     "rbpf_get_dim": (C.c_int, [_H, _I]),
     "rbpf_get_odds_at": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _U]),
+    "rbpf_map_extent": (C.c_int, [_H, C.c_int32, _I]),
+    "rbpf_render_map": (C.c_int, [_H, C.c_int32, _I, _D, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

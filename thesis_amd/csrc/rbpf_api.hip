@@ -322,10 +322,12 @@ int rbpf_destroy(rbpf_handle* h) {
     if (h->early_n > 0 || h->h_early) wait_ev(h->ev_early);
     if (h->h_jobs_used) wait_ev(h->ev_jobs);
     if (h->ev_weights_valid) wait_ev(h->ev_weights);
+    if (h->ev_render_used) wait_ev(h->ev_render);
     for (rbpf_handle::PinnedRing* r : {&h->ring_scan, &h->ring_last, &h->ring_idx})
         for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->used[i]) wait_ev(r->ev[i]);
     for (void* p : h->allocs) (void)hipFree(p);
-    for (void* p : {(void*)h->d_guess, (void*)h->d_prs, (void*)h->d_w, (void*)h->d_gT, (void*)h->d_gidx, (void*)h->d_i32, (void*)h->d_jobs})
+    for (void* p : {(void*)h->d_guess, (void*)h->d_prs, (void*)h->d_w, (void*)h->d_gT, (void*)h->d_gidx, (void*)h->d_i32, (void*)h->d_jobs,
+                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out})
         if (p) (void)hipFree(p);
     if (h->h_jobs) (void)hipHostFree(h->h_jobs);
     if (h->h_early) (void)hipHostFree(h->h_early);
@@ -333,7 +335,7 @@ int rbpf_destroy(rbpf_handle* h) {
         if (r->base) (void)hipHostFree(r->base);
         for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
     }
-    for (hipEvent_t ev : {h->ev_weights, h->ev_jobs, h->ev_early}) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : {h->ev_weights, h->ev_jobs, h->ev_early, h->ev_render}) if (ev) (void)hipEventDestroy(ev);
     for (int k = 0; k < rbpf_handle::N_KERN; ++k) for (int e = 0; e < 2; ++e) for (auto& ev : h->ring[k][e]) if (ev) (void)hipEventDestroy(ev);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     (void)hipGetLastError();
@@ -1270,6 +1272,162 @@ int rbpf_get_odds_at(rbpf_handle* h, int32_t particle, const double* xy, int32_t
     int rc = check_device_error(h);
     hipFree(d_xy); hipFree(d_v); hipFree(d_n);
     return rc;
+}
+
+}  // extern "C"
+
+// ---- map read-out (kernels_render.hip) -----------------------------------------------------------------------------------
+// grows a render buffer; the old one may still be read by queued work, so the stream drains first
+template <typename T>
+static int render_buffer(rbpf_handle* h, T** ptr, size_t* cap, size_t n) {
+    if (*cap >= n) return RBPF_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return scratch(h, ptr, cap, n);
+}
+
+extern "C" {
+
+int rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!box4) return fail(h, RBPF_EINVAL, "box4 is NULL");
+    if (particle < -1 || particle >= h->v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map read-out between rbpf_scan_update_begin and rbpf_scan_update_end");
+    int rc = render_buffer(h, &h->d_render_out, &h->d_render_out_cap, 16);
+    if (rc) return rc;
+    int32_t* d_box = reinterpret_cast<int32_t*>(h->d_render_out);
+    const int32_t init[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
+    int32_t m[4];
+    HIP_TRY(h, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    launch_map_extent(h->v, particle, d_box, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(m, d_box, sizeof(m), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (m[0] > m[1]) { box4[0] = box4[1] = box4[2] = box4[3] = 0; return RBPF_OK; }
+    box4[0] = m[0]; box4[1] = m[1] + 1; box4[2] = m[2]; box4[3] = m[3] + 1;   // inclusive -> half-open
+    return RBPF_OK;
+}
+
+// The box cut at tile seams into jobs: 16 rows at a time, columns in 256-cell blocks aligned to 16 inside the tile.
+static void render_jobs(const DevView& v, const int32_t* box, std::vector<RenderJob>& jobs) {
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2;          // mosaic X + off = a * dim + i
+    auto fdiv = [dim](long long u) { return u >= 0 ? u / dim : -((-u + dim - 1) / dim); };
+    struct Rows { long long a, i, n, ox; };
+    struct Cols { long long b, j0, jlo, jhi, oy; };
+    std::vector<Rows> rows;
+    std::vector<Cols> cols;
+    for (long long u = box[0] + off, e = box[1] + off; u < e;) {
+        const long long a = fdiv(u), i = u - a * dim, n = std::min(std::min(16LL, dim - i), e - u);
+        rows.push_back({a, i, n, u - off - box[0]});
+        u += n;
+    }
+    for (long long u = box[2] + off, e = box[3] + off; u < e;) {
+        const long long b = fdiv(u), jlo = u - b * dim, j0 = jlo & ~15LL, jhi = std::min(std::min(j0 + 256, dim), e - b * dim);
+        cols.push_back({b, j0, jlo, jhi, b * dim + j0 - off - box[2]});
+        u = b * dim + jhi;
+    }
+    jobs.clear();
+    jobs.reserve(rows.size() * cols.size());
+    for (const Rows& r : rows)
+        for (const Cols& c : cols) {
+            const bool in = r.a >= 0 && r.a < v.L && c.b >= 0 && c.b < v.L;
+            jobs.push_back({in ? (int32_t)(r.a * v.L + c.b) : -1, (int32_t)r.i, (int32_t)c.j0, (int32_t)r.n, (int32_t)c.jlo,
+                            (int32_t)c.jhi, (int32_t)r.ox, (int32_t)c.oy});
+        }
+}
+
+int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* weights, uint32_t flags,
+                    int8_t* cells, float* prob, float* occ_frac) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4) return fail(h, RBPF_EINVAL, "box4 is NULL");
+    if (flags & ~RBPF_RENDER_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
+    const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
+    if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
+    if (particle >= 0 && (!cells || prob || occ_frac || weights))
+        return fail(h, RBPF_EINVAL, "one particle: cells only (prob, occ_frac and weights must be NULL)");
+    if (particle < 0 && (cells || (!prob && !occ_frac)))
+        return fail(h, RBPF_EINVAL, "whole filter: prob and / or occ_frac (cells must be NULL)");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map read-out between rbpf_scan_update_begin and rbpf_scan_update_end");
+    // particles are summed in groups of C (kernels_render.hip); the weight sum is formed in the same order
+    const int P = v.P, C = std::max(8, (P + 63) / 64), ngroups = (P + C - 1) / C;
+    double S = 0.0;
+    if (particle < 0) {
+        if (weights)
+            for (int p = 0; p < P; ++p)
+                if (!std::isfinite(weights[p]) || weights[p] < 0.0) return fail(h, RBPF_EINVAL, "weights must be finite and >= 0");
+        for (int g = 0; g < ngroups; ++g) {
+            double sg = 0.0;
+            for (int p = g * C; p < std::min(P, (g + 1) * C); ++p) sg += weights ? weights[p] : 1.0;
+            S += sg;
+        }
+        if (!(S > 0.0) || !std::isfinite(S)) return fail(h, RBPF_EINVAL, "weights must have a positive, finite sum");
+    }
+    if (ncell == 0) return RBPF_OK;
+    std::vector<RenderJob> jobs;
+    render_jobs(v, box4, jobs);
+    if (jobs.size() > ((size_t)1 << 24)) return fail(h, RBPF_ENOMEM, "box too large to render in one call");
+    const bool dev_out = (flags & RBPF_RENDER_DEVICE_OUT) != 0;
+    const int n_out = (prob != nullptr) + (occ_frac != nullptr);
+    const size_t lut_b = particle < 0 ? 256 * 8 : 0, w_b = particle < 0 ? (size_t)P * 8 : 0, job_b = jobs.size() * sizeof(RenderJob);
+    const size_t out_b = particle >= 0 ? (size_t)ncell : (size_t)ncell * 4 * n_out;
+    // a small box has too few jobs to fill the GPU: split the particle groups into G chunks along grid.y (RBPF_RENDER_SPLIT=G
+    // forces a split, a test knob); the group sums then go through d_render_part
+    int G = 1;
+    if (particle < 0 && ngroups > 1) {
+        const long long waves = 4LL * (long long)jobs.size();
+        G = (int)std::min<long long>(ngroups, (2048 + waves - 1) / waves);
+        if (const char* e = getenv("RBPF_RENDER_SPLIT")) G = std::max(1, std::min(ngroups, atoi(e)));
+        if ((size_t)ngroups * ncell * n_out * 8 > ((size_t)256 << 20)) G = 1;
+    }
+    int rc = render_buffer(h, &h->d_render, &h->d_render_cap, lut_b + w_b + job_b);
+    if (!rc && G > 1) rc = render_buffer(h, &h->d_render_part, &h->d_render_part_cap, (size_t)ngroups * ncell * n_out);
+    if (!rc && !dev_out) rc = render_buffer(h, &h->d_render_out, &h->d_render_out_cap, out_b);
+    if (rc) return rc;
+    if (h->ev_render_used) HIP_TRY(h, hipEventSynchronize(h->ev_render));   // the last upload may still read h_render
+    h->h_render.resize(lut_b + w_b + job_b);
+    unsigned char* st = h->h_render.data();
+    if (particle < 0) {
+        double* lut = reinterpret_cast<double*>(st);
+        for (int k = 0; k < 256; ++k) {                 // get_pr_at, hybridmap.py:74-83
+            const double e = exp((double)(int8_t)k * v.quantum);
+            lut[k] = e / (1.0 + e);
+        }
+        double* w = lut + 256;
+        for (int p = 0; p < P; ++p) w[p] = weights ? weights[p] : 1.0;
+    }
+    memcpy(st + lut_b + w_b, jobs.data(), job_b);
+    if (!h->ev_render) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_render, hipEventDisableTiming));
+    HIP_TRY(h, hipMemcpyAsync(h->d_render, st, lut_b + w_b + job_b, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev_render, h->stream));
+    h->ev_render_used = true;
+    const RenderJob* d_jobs = reinterpret_cast<const RenderJob*>(h->d_render + lut_b + w_b);
+    if (particle >= 0) {
+        int8_t* out = dev_out ? cells : reinterpret_cast<int8_t*>(h->d_render_out);
+        launch_render_cells(v, particle, d_jobs, (int)jobs.size(), ny, out, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        if (!dev_out) HIP_TRY(h, hipMemcpyAsync(cells, out, (size_t)ncell, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        RenderFilter f;
+        f.jobs = d_jobs;
+        f.lut = reinterpret_cast<const double*>(h->d_render);
+        f.w = f.lut + 256;
+        f.S = S; f.C = C; f.ngroups = ngroups; f.ny = ny; f.ncell = (size_t)ncell;
+        float* o = reinterpret_cast<float*>(h->d_render_out);
+        f.prob = !prob ? nullptr : dev_out ? prob : o;
+        f.occ = !occ_frac ? nullptr : dev_out ? occ_frac : o + (prob ? ncell : 0);
+        f.part_p = prob ? h->d_render_part : nullptr;
+        f.part_o = occ_frac ? h->d_render_part + (prob ? (size_t)ngroups * ncell : 0) : nullptr;
+        launch_render_filter(v, f, (int)jobs.size(), G, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        if (!dev_out && prob) HIP_TRY(h, hipMemcpyAsync(prob, f.prob, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+        if (!dev_out && occ_frac) HIP_TRY(h, hipMemcpyAsync(occ_frac, f.occ, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (!dev_out) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
 }
 
 }  // extern "C"

@@ -108,6 +108,25 @@ enum { ST_RAY_CELLS = 0, ST_CELLS_WRITTEN = 1, ST_GATHERS = 2, ST_SLOW_CELLS = 3
        ST_NDT_RUNS = 16, ST_NDT_EVALS = 17, ST_NDT_ACCEPTED = 18, ST_MATCH_SHARED = 19, ST_MAP_WINDOWS = 20,
        ST_FB_BOUND = 21, ST_FB_TABLES = 22, ST_MAP_EVENTS = 23, ST_EV_OVERFLOWS = 24, ST_COUNT = 28 };   // ST_FALLBACK_REASONS (7) counts reason 1 (geometry / index map)
 
+// map rendering (kernels_render.hip): one workgroup per job, up to 16 storage rows x 256 storage columns of one lattice tile
+struct RenderJob {
+    int32_t pos;                       // lattice position a * L + b, or -1 outside the lattice
+    int32_t i0, j0;                    // tile-local row and column of the job's first lane (j0 % 16 == 0)
+    int32_t ni, jlo, jhi;              // rows i0 .. i0 + ni - 1, tile-local columns [jlo, jhi) lie in the box
+    int32_t ox, oy;                    // output row and column of (i0, j0): X - x0, Y - y0 (oy < 0 when jlo > j0)
+};
+struct RenderFilter {
+    const RenderJob* jobs;
+    const double* lut;                 // [256] sigma(int8(k) * quantum) on the host, float64
+    const double* w;                   // [P] particle weights
+    double S;                          // sum of w, in the kernels' order (groups of C)
+    int C, ngroups;                    // particles per group, groups
+    long long ny;                      // output columns (y1 - y0)
+    size_t ncell;                      // output cells
+    float *prob, *occ;                 // outputs (either may be null)
+    double *part_p, *part_o;           // [ngroups][ncell] group sums of a split render
+};
+
 }  // namespace rbpf
 
 struct rbpf_handle {
@@ -146,6 +165,11 @@ struct rbpf_handle {
     unsigned long long resample_draws = 0;
     int32_t* d_gT = nullptr; size_t d_gT_cap = 0; int32_t* d_gidx = nullptr; size_t d_gidx_cap = 0;
     int32_t* d_i32 = nullptr; size_t d_i32_cap = 0; unsigned char* d_jobs = nullptr; size_t d_jobs_cap = 0;
+    // map rendering: LUT, weights and jobs of the last render (staged through h_render, reusable once ev_render completed),
+    // the group sums of a split render, the outputs of a render to host memory
+    unsigned char* d_render = nullptr; size_t d_render_cap = 0; double* d_render_part = nullptr; size_t d_render_part_cap = 0;
+    unsigned char* d_render_out = nullptr; size_t d_render_out_cap = 0;
+    std::vector<unsigned char> h_render; hipEvent_t ev_render = nullptr; bool ev_render_used = false;
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
     std::vector<hipEvent_t> ring[N_KERN][2];
@@ -209,4 +233,8 @@ void launch_match_inputs(const DevView& v, int particle, const double* guess3, d
                          uint32_t* d_mask, int* d_row_cnt, double* d_ref, int cap_ref, double* d_curr, int win,
                          double match_max, hipStream_t s);
 size_t raycast_lds_bytes(int B, int reach);
+void launch_map_extent(const DevView& v, int particle, int32_t* d_box4, hipStream_t s);   // particle -1: all; d_box4 preset
+void launch_render_cells(const DevView& v, int particle, const RenderJob* d_jobs, int n_jobs, long long ny, int8_t* d_out,
+                         hipStream_t s);
+void launch_render_filter(const DevView& v, const RenderFilter& f, int n_jobs, int G, hipStream_t s);   // G particle chunks
 }  // namespace rbpf

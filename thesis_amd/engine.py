@@ -86,6 +86,7 @@ class ParticleEngine:
         self.dim = d.value
         self.n_beams = 0
         self._borrowed_stream = False
+        self._stream_ptr = None
         _LIVE.add(self)
 
     # -- plumbing ------------------------------------------------------------------------------------
@@ -100,6 +101,7 @@ class ParticleEngine:
             if self._borrowed_stream:
                 self._lib.rbpf_release_stream(self._h)
                 self._borrowed_stream = False
+                self._stream_ptr = None
             self._lib.rbpf_destroy(self._h)
             self._h = C.c_void_p()
         _LIVE.discard(self)
@@ -116,11 +118,13 @@ class ParticleEngine:
         """Work on the caller's stream from now on (borrowed: never destroyed by the engine)."""
         self._check(self._lib.rbpf_set_stream(self._h, C.c_void_p(stream_ptr)))
         self._borrowed_stream = True
+        self._stream_ptr = stream_ptr
 
     def release_stream(self):
         """Give a borrowed stream back; the engine works on a stream of its own again."""
         self._check(self._lib.rbpf_release_stream(self._h))
         self._borrowed_stream = False
+        self._stream_ptr = None
 
     def synchronize(self):
         self._check(self._lib.rbpf_synchronize(self._h))
@@ -327,6 +331,66 @@ class ParticleEngine:
                 off += n
                 e.set_tile(int(p), c, cells)
         return e
+
+    # -- map read-out (include/rbpf_hip.h: rbpf_map_extent, rbpf_render_map; thesis_amd/mapio.py) -----------------------
+    def map_extent(self, particle: Optional[int] = None) -> Optional[Tuple[int, int, int, int]]:
+        """(x0, x1, y0, y1), half-open, in mosaic cells: the smallest box holding the written cells of every tile of
+        `particle`, or of all particles (None); None when there is none."""
+        box = np.empty(4, dtype=np.int32)
+        self._check(self._lib.rbpf_map_extent(self._h, -1 if particle is None else int(particle), _ip(box)))
+        return None if box[0] == box[1] else tuple(int(b) for b in box)
+
+    def render_map(self, particle=None, box=None, weights=None, device: bool = False,
+                   fields=("prob", "occ_frac")) -> "MapRaster":
+        """A dense raster of one particle's map (`particle` an index, or "best": the first argmax of weights()) or of the
+        whole filter (None).  `box` = (x0, x1, y0, y1) in mosaic cells, default map_extent(particle).  The whole filter
+        gives the weighted mean occupancy probability `prob` and the weight share `occ_frac` that calls a cell occupied
+        (`fields` picks them); `weights`: None (uniform), P values, or "resample" (resample_weights of weights()).
+        device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
+        from .mapio import MapRaster, resample_weights
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        w = None
+        if isinstance(weights, str):
+            if weights != "resample":
+                raise ValueError(f"unknown weights {weights!r}")
+            w = resample_weights(self.weights())
+        elif weights is not None:
+            w = _f64(weights)
+            if w.shape != (self.P,):
+                raise ValueError(f"weights must have shape ({self.P},)")
+        if box is None:
+            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        nx, ny = int(b[1]) - int(b[0]), int(b[3]) - int(b[2])
+        shape = (max(nx, 0), max(ny, 0))                 # a box with x1 < x0 or y1 < y0 is the library's to refuse
+        want = [p >= 0, p < 0 and "prob" in fields, p < 0 and "occ_frac" in fields]
+        dtypes = ("int8", "float32", "float32")
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [torch.empty(shape, dtype=getattr(torch, d), device=dev) if k else None for k, d in zip(want, dtypes)]
+            ptrs = [None if o is None else C.c_void_p(o.data_ptr()) for o in outs]
+        else:
+            outs = [np.empty(shape, dtype=d) if k else None for k, d in zip(want, dtypes)]
+            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
+        if not (device and nx >= 0 and ny >= 0 and nx * ny == 0):   # an empty tensor has no data pointer
+            if device and not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+            self._check(self._lib.rbpf_render_map(self._h, p, _ip(b), None if w is None else _dp(w),
+                                                  _lib.RBPF_RENDER_DEVICE_OUT if device else 0, *ptrs))
+            if device and not same_stream:
+                self.synchronize()
+        return MapRaster(x0=int(b[0]), y0=int(b[2]), cell_size=float(self.cfg.cell_size), quantum=float(self.cfg.quantum),
+                         dim=self.dim, tile_len=float(self.cfg.tile_len_m), cells=outs[0], prob=outs[1], occ_frac=outs[2])
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)

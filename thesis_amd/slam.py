@@ -49,6 +49,10 @@ class HybridMapView:
             ys.append(((j - dim / 2) * self._cell_size + cy) / self._cell_size)
         return (np.concatenate(xs) if xs else np.empty(0)), (np.concatenate(ys) if ys else np.empty(0))
 
+    def render(self, box=None):
+        """This particle's map as one dense int8 raster (ParticleEngine.render_map, thesis_amd/mapio.py)."""
+        return self._pf.engine.render_map(self._i, box=box)
+
     def is_occ_at(self, x, y) -> bool:                # gridmap.py:255-260 through the tile that holds (x, y)
         o = self.get_odds_at((x, y))
         return o is not None and o > self._pf.engine.cfg.occupied_threshold
@@ -139,6 +143,10 @@ class ParticleFilter:
         if did and self.keep_history:
             self._poses.append(self.engine.poses()); self._ancestors.append(idx)
         return did
+
+    def render_map(self, particle=None, box=None, weights=None, device: bool = False, fields=("prob", "occ_frac")):
+        """The map of one particle ("best": the heaviest) or of the whole filter (ParticleEngine.render_map)."""
+        return self.engine.render_map(particle, box=box, weights=weights, device=device, fields=fields)
 
     def _record(self, anc):
         if self.keep_history:
