@@ -196,6 +196,13 @@ int  rbpf_match_scan(rbpf_handle* h, const double* curr_xy, int32_t n_curr, cons
 /* matcher inputs built from particle p's map (hybridmap.py:210-242), test/inspection entry */
 int  rbpf_match_inputs(rbpf_handle* h, int32_t particle, const double* guess3, double* curr_xy,
                        int32_t* n_curr, double* ref_xy, int32_t* n_ref, int32_t cap_ref);
+/* out[P][13]: pose, 3x3 covariance, score of every particle as the last built-in matcher of rbpf_scan_update(_begin)
+ * wrote them; a duplicate particle the matcher skipped gets its representative's row (the row the proposal read).
+ * RBPF_ESTATE if no built-in match ran, or if match_override or a resample came after it.  Test/inspection entry. */
+int  rbpf_match_results(rbpf_handle* h, double* out);
+/* s[i], c[i] = __sincosf(x[i]) on the device, compiled with the matcher's grid stage: the sines and cosines it rotates the
+ * beams by.  Test/inspection entry. */
+int  rbpf_native_sincosf(rbpf_handle* h, const float* x, int32_t n, float* s, float* c);
 
 /* ---- a8+a9: resample (main.py:46-79) ---------------------------------------------------------- */
 /* u in [0,1) replaces np.random.random() (main.py:59); NaN => internal Philox draw.

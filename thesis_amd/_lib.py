@@ -78,6 +78,8 @@ PROTOTYPES = {
     "rbpf_scan_update_end": (C.c_int, [_H]),
     "rbpf_match_scan": (C.c_int, [_H, _D, C.c_int32, _D, C.c_int32, _D, C.c_int32, _D, _D, _D, _D]),
     "rbpf_match_inputs": (C.c_int, [_H, C.c_int32, _D, _D, _I, _D, _I, C.c_int32]),
+    "rbpf_match_results": (C.c_int, [_H, _D]),
+    "rbpf_native_sincosf": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rbpf_resample": (C.c_int, [_H, C.c_double, _I, _I]),
     "rbpf_export_weights": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "rbpf_resample_indices_global": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, _I, _I]),

@@ -183,7 +183,8 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
     s.cx8 = s.fy4 + cap4; s.cy8 = s.cx8 + cap8;
     s.sc = reinterpret_cast<int*>(s.cy8 + cap8);
     __shared__ double s_g[3], s_rng[2];
-    __shared__ int s_org[2], s_nb, s_best, s_bestc;
+    __shared__ int s_org[2], s_nb, s_best;
+    __shared__ unsigned long long s_bestc;   // tie-break key: distance in the high word, candidate index in the low word
     __shared__ unsigned s_def[32], s_slowg;  // per region word: defect columns of the index map; words not inside one mapped tile
     __shared__ double s_mom[10], s_wmom[MBLOCK / 64][10];
     __shared__ int s_tab[49];
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
     // ---- guess, search window (robot.py:62-65), region origin ----------------------------------------------
     if (tid == 0) {
         match_frame_from(a, pre, s_g, s_rng, s_org);
-        s_nb = 0; s_best = INT_MIN; s_bestc = 0; s_slowg = 0;
+        s_nb = 0; s_best = INT_MIN; s_bestc = 0ull; s_slowg = 0;
         for (int i = 0; i < 10; ++i) s_mom[i] = 0.0;
     }
     if (!a.single) {
@@ -480,11 +481,11 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
     // ---- coarse level -------------------------------------------------------------------------------------------
     // work item = (rotation, beam slice): a beam is rotated once and looked up for every x translation (a shift by whole
     // coarse cells) and, through the byte lanes, for 8 y translations per LDS read; slices add their sums with atomics
-    int g_best = INT_MIN, g_key = INT_MAX;                               // best score so far and its tie-break key (uniform)
+    int g_best = INT_MIN; unsigned long long g_key = ~0ull;              // best score so far and its tie-break key (uniform)
     for (int r0 = 0; r0 < nr; r0 += RG) {
     const int nrg = min(RG, nr - r0), n_words = nrg * rot_words;
     for (int i = tid; i < n_words; i += MBLOCK) sc2[i] = 0;             // candidate sums are accumulated with atomics
-    if (tid == 0) { s_best = INT_MIN; s_bestc = INT_MAX; }
+    if (tid == 0) { s_best = INT_MIN; s_bestc = ~0ull; }
     __syncthreads();
     {
         const int MAXTX = 7;
@@ -510,8 +511,10 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
                     const int cu0 = ((int)floorf(cs * bxs - sn * bys + fx) + (t0 - max(ktx, 0)) * M_COARSE) >> 2;   // x translation t looks at coarse row cu0 + t
                     const int cw0 = (int)floorf(sn * bxs + cs * bys + ty0) >> 2;             // candidate j looks at coarse column cw0 + j
                     // the 7 rows are 7 consecutive words of one column of overlapping words (which holds all 8 candidates);
-                    // rows outside the region are zero rows, a beam outside altogether reads the zero rows of column 0
-                    const bool ok = cw0 >= 0 && cw0 + 7 < NC4 && (unsigned)(cu0 + CRS_PAD) < (unsigned)(NC4 + CRS_PAD);
+                    // rows outside the region are zero rows, a beam outside altogether reads the zero rows of column 0.
+                    // Columns past the region's last are zero bits of the last word: only a pass that starts below column 0
+                    // is dropped whole
+                    const bool ok = cw0 >= 0 && cw0 < NC4 && (unsigned)(cu0 + CRS_PAD) < (unsigned)(NC4 + CRS_PAD);
                     const uint32_t sh = (uint32_t)(cw0 & 15);
                     int ci = (cw0 >> 4) * RS + (CRS_PAD + cu0);
                     ci = ok ? ci : 0;
@@ -556,12 +559,13 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
         for (int hf = 0; hf < 2; ++hf) {
             const int iy = iy0 + 2 * hf, sco = hf ? (int)(val >> 16) : (int)(val & 0xFFFFu);
             if (iy < nty && sco == best_group) {
-                // ties: the candidate closest to the guess, then the lowest index (deterministic)
+                // ties: the candidate closest to the guess, then the lowest index (deterministic); the index over all
+                // rotations can pass 2^16 in a wide stateless window, so the key is 64 bits wide
                 const int rt = (w >> 2) / NP;                                    // (rotation in the group) * ntx + x translation
                 const int ir = r0 + rt / ntx, itx = rt % ntx;
                 const int cnd = (ir * ntx + itx) * nty + iy;                     // index over all rotations
                 int dr = ir - a.n_coarse_rot, dx = itx - max(ktx, 0), dy = iy - max(kty, 0);
-                int key = ((dr * dr + dx * dx + dy * dy) << 16) | cnd;
+                const unsigned long long key = ((unsigned long long)(dr * dr + dx * dx + dy * dy) << 32) | (uint32_t)cnd;
                 atomicMin(&s_bestc, key);
             }
         }
@@ -572,7 +576,7 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
     }
     if (tid == 0) s_bestc = g_key;
     __syncthreads();
-    const int cbest = s_bestc & 0xFFFF;
+    const int cbest = (int)(uint32_t)s_bestc;
     const int cir = cbest / (ntx * nty) - a.n_coarse_rot, cit = cbest % (ntx * nty);
     const int ctx = (cit / nty - max(ktx, 0)) * M_COARSE, cty = (cit % nty - max(kty, 0)) * M_COARSE;
     __syncthreads();
@@ -649,19 +653,19 @@ __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
         atomicMax(&s_best, s.sc[cnd]);
     }
     __syncthreads();
-    if (tid == 0) s_bestc = INT_MAX;
+    if (tid == 0) s_bestc = ~0ull;
     __syncthreads();
     const int best = s_best;
     for (int cnd = tid; cnd < n_fine; cnd += MBLOCK) {
         if (s.sc[cnd] == best) {
             const int ir = cnd / (FT * FT) - M_FINE_R, ix = (cnd / FT) % FT - M_FINE_T, iy = cnd % FT - M_FINE_T;
             int dr = cir * M_COARSE + ir, dx = ctx + ix, dy = cty + iy;
-            int key = (min(dr * dr + dx * dx + dy * dy, 32767) << 16) | cnd;
+            const unsigned long long key = ((unsigned long long)(dr * dr + dx * dx + dy * dy) << 32) | (uint32_t)cnd;
             atomicMin(&s_bestc, key);
         }
     }
     __syncthreads();
-    const int fbest = s_bestc & 0xFFFF;
+    const int fbest = (int)(uint32_t)s_bestc;
     const double bth = (double)(cir * M_COARSE + (fbest / (FT * FT) - M_FINE_R)) * a.d0;
     const double bdx = (double)(ctx + (fbest / FT) % FT - M_FINE_T) * a.mcs, bdy = (double)(cty + fbest % FT - M_FINE_T) * a.mcs;
 
@@ -1089,6 +1093,19 @@ int match_max_coarse(int n_coarse_rot, double max_range_m, double mcs) {
 int match_per_rot(double max_range_m, double mcs) {          // coarse candidates of one rotation, at most
     int k = (int)ceil(max_range_m / mcs / M_COARSE);
     return (2 * k + 1) * (2 * k + 1);
+}
+
+// __sincosf of given angles, compiled in this translation unit with match_kernel's flags: the values its two search levels
+// rotate the beams by (rbpf_native_sincosf, a test entry)
+__global__ void native_sincosf_kernel(const float* x, int n, float* s, float* c) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float sn, cs;
+    __sincosf(x[i], &sn, &cs);
+    s[i] = sn; c[i] = cs;
+}
+void launch_native_sincosf(const float* d_x, int n, float* d_s, float* d_c, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(native_sincosf_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_x, n, d_s, d_c);
 }
 
 // t0 / t1 (or nullptr): timing events that take the kernel's own start and end (carried by its dispatch: hipExtLaunchKernelGGL)

@@ -627,6 +627,7 @@ static int run_matcher(rbpf_handle* h, int32_t adj, const double* last_scan_xy, 
     auto take_events = [&](int k) { t0 = t1 = nullptr; if (!((h->prof_mask >> k) & 1u)) return; const int slot = h->ring_n[k] % rbpf_handle::RING;
                                     t0 = h->ring[k][0][slot]; t1 = h->ring[k][1][slot]; h->begin_used[k][slot] = t0; h->last_end = nullptr; h->ring_n[k]++; };
     take_events(3);
+    h->match_rows = v.dups_valid ? 2 : 1;
     const bool ndt = launch_match_particles(v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
                                             h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, 1, h->stream, t0, t1);
     if (ndt) {
@@ -655,6 +656,7 @@ int rbpf_scan_update_begin(rbpf_handle* h, int32_t adj, const double* last_scan_
     DevView& v = h->v;
     const size_t P = v.P;
     if (match_override) {
+        h->match_rows = 0;
         HIP_TRY(h, hipMemcpyAsync(h->d_match, match_override, 13 * P * 8, hipMemcpyHostToDevice, h->stream));
     } else {
         int rc = run_matcher(h, adj, last_scan_xy, n_last);
@@ -768,6 +770,40 @@ int rbpf_match_inputs(rbpf_handle* h, int32_t particle, const double* guess3, do
     return rc;
 }
 
+// the rows the last built-in matcher wrote (pose, covariance, score per particle); a duplicate the matcher skipped gets its
+// representative's row, the one the proposal read
+int rbpf_match_results(rbpf_handle* h, double* out) {
+    if (!h || !out) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (h->match_rows == 0) return fail(h, RBPF_ESTATE, "no built-in match since the last match_override / resample");
+    const int P = h->v.P;
+    std::vector<int32_t> dup(P);
+    if (h->match_rows == 2) HIP_TRY(h, hipMemcpyAsync(dup.data(), h->v.dup_of, (size_t)P * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_match, (size_t)P * 13 * 8, hipMemcpyDeviceToHost, h->stream));
+    int rc = check_device_error(h);
+    if (rc) return rc;
+    if (h->match_rows == 2)
+        for (int p = 0; p < P; ++p) if (dup[p] != p) memcpy(out + (size_t)p * 13, out + (size_t)dup[p] * 13, 13 * 8);
+    return RBPF_OK;
+}
+
+// __sincosf on the device, as the grid stage of the matcher evaluates it
+int rbpf_native_sincosf(rbpf_handle* h, const float* x, int32_t n, float* s, float* c) {
+    if (!h || n < 0 || (n > 0 && (!x || !s || !c))) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (n == 0) return RBPF_OK;
+    float* d = nullptr;
+    HIP_TRY(h, hipMalloc((void**)&d, (size_t)n * 12));
+    HIP_TRY(h, hipMemcpyAsync(d, x, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    launch_native_sincosf(d, n, d + n, d + 2 * (size_t)n, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(s, d + n, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(c, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    int rc = check_device_error(h);
+    (void)hipFree(d);
+    return rc;
+}
+
 // ---- resample (main.py:46-79) -------------------------------------------------------------------------------
 static double internal_uniform(rbpf_handle* h) {
     uint64_t z = h->cfg.seed + 0x9E3779B97F4A7C15ull * (++h->resample_draws);   // splitmix64
@@ -794,6 +830,7 @@ static int resample_local(rbpf_handle* h, const double* d_w, double u, double sp
     HIP_TRY(h, hipGetLastError());
     swap_state_buffers(h);
     v.dups_valid = h->dedup_enabled ? 1 : 0;
+    if (h->match_rows == 2) h->match_rows = 0;      // the duplicate groups the matcher skipped are overwritten
     return RBPF_OK;
 }
 

@@ -161,6 +161,7 @@ struct rbpf_handle {
     int mN = 0, mds = 1, mncr = 0; double mmcs = 0, md0 = 0; size_t mlds = 0;
     double* d_last_xy = nullptr; float* d_tmp_sel = nullptr;
     int n_last_dev = -1;                       // points of the device-resident previous scan (rbpf_refresh_last_scan), -1 = none
+    int match_rows = 0;                        // d_match: 0 not written by the built-in matcher, 1 its rows, 2 its rows with duplicates skipped (dup_of)
     double* d_match = nullptr; uint8_t* d_bad = nullptr; double* d_guess_full = nullptr;
     unsigned long long resample_draws = 0;
     int32_t* d_gT = nullptr; size_t d_gT_cap = 0; int32_t* d_gidx = nullptr; size_t d_gidx_cap = 0;
@@ -232,6 +233,7 @@ void launch_match_single(const DevView& v, const double* d_ref, int n_ref, const
 void launch_match_inputs(const DevView& v, int particle, const double* guess3, double* d_all_curr, int* d_counts,
                          uint32_t* d_mask, int* d_row_cnt, double* d_ref, int cap_ref, double* d_curr, int win,
                          double match_max, hipStream_t s);
+void launch_native_sincosf(const float* d_x, int n, float* d_s, float* d_c, hipStream_t s);
 size_t raycast_lds_bytes(int B, int reach);
 void launch_map_extent(const DevView& v, int particle, int32_t* d_box4, hipStream_t s);   // particle -1: all; d_box4 preset
 void launch_render_cells(const DevView& v, int particle, const RenderJob* d_jobs, int n_jobs, long long ny, int8_t* d_out,

@@ -233,6 +233,21 @@ class ParticleEngine:
         self._check(self._lib.rbpf_match_inputs(self._h, particle, _dp(g), _dp(curr), C.byref(nc), _dp(ref), C.byref(nr), cap_ref))
         return curr[:nc.value].copy(), ref[:min(nr.value, cap_ref)].copy()
 
+    def match_results(self) -> np.ndarray:
+        """[P, 13] pose, covariance (row-major 3x3) and score of every particle as the last built-in matcher wrote them
+        (a duplicate particle gets its representative's row).  Test/inspection entry."""
+        out = np.empty((self.P, 13))
+        self._check(self._lib.rbpf_match_results(self._h, _dp(out)))
+        return out
+
+    def native_sincosf(self, x) -> Tuple[np.ndarray, np.ndarray]:
+        """The device's __sincosf of float32 angles, as the matcher's grid stage evaluates it.  Test/inspection entry."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        s, c = np.empty_like(x), np.empty_like(x)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.rbpf_native_sincosf(self._h, x.ctypes.data_as(fp), len(x), s.ctypes.data_as(fp), c.ctypes.data_as(fp)))
+        return s, c
+
     def resample(self, u: float = float("nan")) -> Tuple[bool, np.ndarray]:
         idx = np.empty(self.P, dtype=np.int32)
         did = C.c_int32()
