@@ -302,6 +302,25 @@ int  rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4);
 int  rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* weights,
                      uint32_t flags, int8_t* cells, float* prob, float* occ_frac);
 
+/* ---- map loading: a dense raster into the particles' tiles; localization with the maps held fixed ---------------------
+ * rbpf_load_map writes the int8 lattice values `cells` (units of quantum, in [min_odds_emp, max_odds_occ] / quantum) of
+ * the box box4 = {x0, x1, y0, y1} into `particle` (>= 0) or into every particle (-1).  box4 and the raster layout are
+ * those of rbpf_render_map: mosaic cells, half-open, [x1-x0][y1-y0] row-major.  Cells inside the box are replaced; cells
+ * outside it keep their values.  Missing lattice tiles come from the free pool (zero-filled); every touched tile's
+ * written box grows to hold (box n tile), and its occupancy bits are recomputed.  Groups of exact duplicates made by the
+ * last resample are dissolved (the next matcher runs once per particle).  All or nothing: a value out of range, a box
+ * that leaves the lattice or holds more than 2^31 cells is RBPF_EINVAL; too few free tiles for the whole request is
+ * RBPF_ENOMEM (the message gives the number needed); a call between rbpf_scan_update_begin and _end is RBPF_ESTATE.  In
+ * each case nothing is written.  Complete on return. */
+#define RBPF_LOAD_DEVICE_IN 1u     /* cells is a device pointer, read in stream order (validated on the device) */
+int  rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* cells, uint32_t flags);
+/* Map updates on (1, the default) or off (0).  Off, rbpf_scan_update(_end) leaves every map unchanged: the NaN-branch
+ * weight increment (robot.py:73-78) is taken on the unchanged map, and the proposal's random stream still advances one
+ * step per scan update (rbpf_get_rng_state).  This is localization in a known map.  An explicit rbpf_map_update writes
+ * in either mode. */
+int  rbpf_set_map_updates(rbpf_handle* h, int32_t on);
+int  rbpf_get_map_updates(rbpf_handle* h, int32_t* on);
+
 #ifdef __cplusplus
 }
 #endif

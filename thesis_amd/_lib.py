@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "librbpf_hip.so")
 RBPF_OK = 0
 RBPF_EINVAL, RBPF_ENOMEM, RBPF_EDEVICE, RBPF_ESTATE, RBPF_ERANGE = -1, -2, -3, -4, -5
 RBPF_RENDER_DEVICE_OUT = 1
+RBPF_LOAD_DEVICE_IN = 1
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
 
 
@@ -107,6 +108,9 @@ PROTOTYPES = {
     "rbpf_get_odds_at": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _U]),
     "rbpf_map_extent": (C.c_int, [_H, C.c_int32, _I]),
     "rbpf_render_map": (C.c_int, [_H, C.c_int32, _I, _D, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbpf_load_map": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_uint32]),
+    "rbpf_set_map_updates": (C.c_int, [_H, C.c_int32]),
+    "rbpf_get_map_updates": (C.c_int, [_H, _I]),
 }
 
 _lib = None

@@ -327,7 +327,7 @@ int rbpf_destroy(rbpf_handle* h) {
         for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->used[i]) wait_ev(r->ev[i]);
     for (void* p : h->allocs) (void)hipFree(p);
     for (void* p : {(void*)h->d_guess, (void*)h->d_prs, (void*)h->d_w, (void*)h->d_gT, (void*)h->d_gidx, (void*)h->d_i32, (void*)h->d_jobs,
-                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out})
+                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out, (void*)h->d_load})
         if (p) (void)hipFree(p);
     if (h->h_jobs) (void)hipHostFree(h->h_jobs);
     if (h->h_early) (void)hipHostFree(h->h_early);
@@ -688,9 +688,29 @@ int rbpf_scan_update_end(rbpf_handle* h) {
     ON_DEVICE(h);
     if (!h->scan_begun) return fail(h, RBPF_ESTATE, "rbpf_scan_update_begin has not been called");
     h->scan_begun = false;
+    if (!h->map_updates) {
+        // localization: the maps stay as they are; the NaN-branch increment (robot.py:73-78) on the unchanged map.  The
+        // step still counts: scan_updates is the Philox stream of the next proposal
+        launch_bad_weight(h->v, h->d_bad, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        h->scan_updates++;
+        return RBPF_OK;
+    }
     // HybridMap.update at the new mean pose (robot.py:115), then - in the same launch - the robot.py:73-78 weight
     // increment of the particles on the NaN-covariance branch, on their updated maps
     return run_map_update(h, h->d_bad);
+}
+
+int rbpf_set_map_updates(rbpf_handle* h, int32_t on) {
+    if (!h) return RBPF_EINVAL;
+    h->map_updates = on != 0;
+    return RBPF_OK;
+}
+
+int rbpf_get_map_updates(rbpf_handle* h, int32_t* on) {
+    if (!h || !on) return RBPF_EINVAL;
+    *on = h->map_updates ? 1 : 0;
+    return RBPF_OK;
 }
 
 // matchScanCustom(curr, ref, guess, cells_per_m, pose_range) -> pose, cov, score  (hybridmap.py:244-251)
@@ -1345,8 +1365,9 @@ int rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4) {
     return RBPF_OK;
 }
 
-// The box cut at tile seams into jobs: 16 rows at a time, columns in 256-cell blocks aligned to 16 inside the tile.
-static void render_jobs(const DevView& v, const int32_t* box, std::vector<RenderJob>& jobs) {
+// The box cut at tile seams into jobs: 16 rows at a time, columns in 256-cell blocks aligned to `align` (16, or 32 for the
+// loader's occupancy words) inside the tile.
+static void render_jobs(const DevView& v, const int32_t* box, std::vector<RenderJob>& jobs, long long align = 16) {
     const long long dim = v.dim, off = (long long)v.R * dim + dim / 2;          // mosaic X + off = a * dim + i
     auto fdiv = [dim](long long u) { return u >= 0 ? u / dim : -((-u + dim - 1) / dim); };
     struct Rows { long long a, i, n, ox; };
@@ -1359,7 +1380,7 @@ static void render_jobs(const DevView& v, const int32_t* box, std::vector<Render
         u += n;
     }
     for (long long u = box[2] + off, e = box[3] + off; u < e;) {
-        const long long b = fdiv(u), jlo = u - b * dim, j0 = jlo & ~15LL, jhi = std::min(std::min(j0 + 256, dim), e - b * dim);
+        const long long b = fdiv(u), jlo = u - b * dim, j0 = jlo & ~(align - 1), jhi = std::min(std::min(j0 + 256, dim), e - b * dim);
         cols.push_back({b, j0, jlo, jhi, b * dim + j0 - off - box[2]});
         u = b * dim + jhi;
     }
@@ -1465,6 +1486,84 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     }
     if (!dev_out) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RBPF_OK;
+}
+
+// ---- map loading (kernels_load.hip) ---------------------------------------------------------------------------------------
+int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* cells, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    DevView& v = h->v;
+    if (!box4 || !cells) return fail(h, RBPF_EINVAL, "box4 or cells is NULL");
+    if (flags & ~RBPF_LOAD_DEVICE_IN) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map load between rbpf_scan_update_begin and rbpf_scan_update_end");
+    if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
+    const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
+    if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    if (ncell > 0 && (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge))
+        return fail(h, RBPF_EINVAL, "box leaves the tile lattice (raise lattice_radius)");
+    const bool dev_in = (flags & RBPF_LOAD_DEVICE_IN) != 0;
+    if (!dev_in)   // the reference's cells never leave [min_odds_emp, max_odds_occ] (gridmap.py:86-117); the map kernels rely on it
+        for (long long i = 0; i < ncell; ++i)
+            if (cells[i] < v.cc.vmin || cells[i] > v.cc.vmax) return fail(h, RBPF_EINVAL, "cell value outside [min_odds_emp, max_odds_occ]");
+    if (ncell == 0) return RBPF_OK;
+    // the lattice positions the box touches, with (box n tile) in tile-local cells
+    std::vector<LoadTile> tiles;
+    {
+        const long long a_lo = (box4[0] + off) / dim, a_hi = (box4[1] - 1 + off) / dim;
+        const long long b_lo = (box4[2] + off) / dim, b_hi = (box4[3] - 1 + off) / dim;
+        for (long long a = a_lo; a <= a_hi; ++a)
+            for (long long b = b_lo; b <= b_hi; ++b)
+                tiles.push_back({(int32_t)(a * v.L + b), (int32_t)std::max(0LL, box4[0] + off - a * dim),
+                                 (int32_t)std::min(dim - 1, box4[1] - 1 + off - a * dim), (int32_t)std::max(0LL, box4[2] + off - b * dim),
+                                 (int32_t)std::min(dim - 1, box4[3] - 1 + off - b * dim)});
+    }
+    std::vector<RenderJob> jobs;
+    render_jobs(v, box4, jobs, 32);
+    if (jobs.size() > ((size_t)1 << 24)) return fail(h, RBPF_ENOMEM, "box too large to load in one call");
+    // count the missing tiles before anything is allocated: one read of free_top, the slots and their tile_tab rows
+    const int p_lo = particle < 0 ? 0 : particle, p_hi = particle < 0 ? v.P : particle + 1, np = p_hi - p_lo;
+    const size_t LL = (size_t)v.L * v.L;
+    {
+        std::vector<int32_t> slot(np), tab((size_t)v.P * LL);
+        int32_t top = 0;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipMemcpy(&top, v.free_top, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(slot.data(), v.slot + p_lo, (size_t)np * 4, hipMemcpyDeviceToHost));
+        if (particle < 0) HIP_TRY(h, hipMemcpy(tab.data(), v.tile_tab, tab.size() * 4, hipMemcpyDeviceToHost));
+        else HIP_TRY(h, hipMemcpy(tab.data() + (size_t)slot[0] * LL, v.tile_tab + (size_t)slot[0] * LL, LL * 4, hipMemcpyDeviceToHost));
+        long long need = 0;
+        for (int q = 0; q < np; ++q)
+            for (const LoadTile& lt : tiles) need += tab[(size_t)slot[q] * LL + lt.pos] < 0;
+        if (need > top)
+            return fail(h, RBPF_ENOMEM, "map load needs " + std::to_string(need) + " free tiles, the pool has " + std::to_string(top));
+    }
+    // device staging: [flag, padded to 16] [tiles] [jobs] [the raster, host input only]
+    const size_t tiles_b = (tiles.size() * sizeof(LoadTile) + 15) & ~(size_t)15, jobs_b = jobs.size() * sizeof(RenderJob);
+    const size_t meta_b = 16 + tiles_b + ((jobs_b + 15) & ~(size_t)15);
+    int rc = render_buffer(h, &h->d_load, &h->d_load_cap, meta_b + (dev_in ? 0 : (size_t)ncell));
+    if (rc) return rc;
+    std::vector<unsigned char> st(meta_b, 0);
+    memcpy(st.data() + 16, tiles.data(), tiles.size() * sizeof(LoadTile));
+    memcpy(st.data() + 16 + tiles_b, jobs.data(), jobs_b);
+    HIP_TRY(h, hipMemcpyAsync(h->d_load, st.data(), meta_b, hipMemcpyHostToDevice, h->stream));
+    if (!dev_in) HIP_TRY(h, hipMemcpyAsync(h->d_load + meta_b, cells, (size_t)ncell, hipMemcpyHostToDevice, h->stream));
+    LoadArgs a;
+    a.bad = reinterpret_cast<int32_t*>(h->d_load);
+    a.tiles = reinterpret_cast<const LoadTile*>(h->d_load + 16); a.n_tiles = (int)tiles.size();
+    a.jobs = reinterpret_cast<const RenderJob*>(h->d_load + 16 + tiles_b);
+    a.cells = dev_in ? cells : reinterpret_cast<const int8_t*>(h->d_load + meta_b);
+    a.ny = ny; a.ncell = ncell; a.p_lo = p_lo; a.p_hi = p_hi;
+    if (dev_in) launch_load_validate(v, a, h->stream);
+    launch_load_map(v, a, (int)jobs.size(), h->stream);
+    HIP_TRY(h, hipGetLastError());
+    int32_t bad = 0;
+    HIP_TRY(h, hipMemcpyAsync(&bad, a.bad, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (bad) return fail(h, RBPF_EINVAL, "cell value outside [min_odds_emp, max_odds_occ]");
+    v.dups_valid = 0;                   // a duplicate's map may differ from its representative's now
+    return check_device_error(h);
 }
 
 }  // extern "C"

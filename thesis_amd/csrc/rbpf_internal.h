@@ -126,6 +126,17 @@ struct RenderFilter {
     float *prob, *occ;                 // outputs (either may be null)
     double *part_p, *part_o;           // [ngroups][ncell] group sums of a split render
 };
+// map loading (kernels_load.hip): the box cut into RenderJobs whose column blocks start at multiples of 32 (one occupancy word
+// per lane pair), and the lattice positions it touches with (box n tile) in tile-local cells, inclusive
+struct LoadTile { int32_t pos, i0, i1, j0, j1; };
+struct LoadArgs {
+    const RenderJob* jobs;
+    const LoadTile* tiles; int n_tiles;
+    const int8_t* cells;               // raster [nx][ny] (device)
+    long long ny, ncell;
+    int p_lo, p_hi;                    // particles [p_lo, p_hi)
+    int32_t* bad;                      // [1] != 0: validation found a value out of range - the alloc and write kernels do nothing
+};
 
 }  // namespace rbpf
 
@@ -171,6 +182,8 @@ struct rbpf_handle {
     unsigned char* d_render = nullptr; size_t d_render_cap = 0; double* d_render_part = nullptr; size_t d_render_part_cap = 0;
     unsigned char* d_render_out = nullptr; size_t d_render_out_cap = 0;
     std::vector<unsigned char> h_render; hipEvent_t ev_render = nullptr; bool ev_render_used = false;
+    unsigned char* d_load = nullptr; size_t d_load_cap = 0;   // map loading: flag, touched tiles, jobs, host raster
+    bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
     std::vector<hipEvent_t> ring[N_KERN][2];
@@ -239,4 +252,6 @@ void launch_map_extent(const DevView& v, int particle, int32_t* d_box4, hipStrea
 void launch_render_cells(const DevView& v, int particle, const RenderJob* d_jobs, int n_jobs, long long ny, int8_t* d_out,
                          hipStream_t s);
 void launch_render_filter(const DevView& v, const RenderFilter& f, int n_jobs, int G, hipStream_t s);   // G particle chunks
+void launch_load_validate(const DevView& v, const LoadArgs& a, hipStream_t s);
+void launch_load_map(const DevView& v, const LoadArgs& a, int n_jobs, hipStream_t s);   // tile allocation, then the cells
 }  // namespace rbpf

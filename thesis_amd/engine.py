@@ -300,6 +300,60 @@ class ParticleEngine:
         self._check(self._lib.rbpf_set_tile(self._h, particle, float(centre[0]), float(centre[1]),
                                             cells.ctypes.data_as(C.POINTER(C.c_int8))))
 
+    # -- map loading and localization (include/rbpf_hip.h: rbpf_load_map, rbpf_set_map_updates) --------------------------
+    def load_map(self, raster, particle: Optional[int] = None):
+        """Writes the int8 lattice values `raster.cells` (a MapRaster, as render_map or mapio.read_occupancy_map give it)
+        into `particle`'s map, or into every particle's (None).  Cells inside the raster's box are replaced, every other
+        cell keeps its value; missing tiles come from the pool.  `cells` is a numpy array, or an int8 torch tensor on the
+        engine's device (read on the GPU, in torch's stream order).  All or nothing: on an error no map changes."""
+        cfg = self.cfg
+        for name, have, want in (("cell_size", raster.cell_size, cfg.cell_size), ("quantum", raster.quantum, cfg.quantum),
+                                 ("tile_len", raster.tile_len, float(cfg.tile_len_m)), ("dim", raster.dim, self.dim)):
+            if abs(float(have) - float(want)) > 1e-9 * abs(float(want)):
+                raise ValueError(f"raster {name} = {have!r} differs from the engine's {want!r}")
+        if raster.cells is None:
+            raise ValueError("the raster has no int8 cells (a whole-filter render has prob / occ_frac): convert them with "
+                             "thesis_amd.mapio.cells_from_probability first")
+        p = -1 if particle is None else int(particle)
+        cells, flags, cur, same_stream = raster.cells, 0, None, False
+        if hasattr(cells, "data_ptr"):                   # a torch tensor
+            import torch
+            dev = torch.device("cuda", int(cfg.device))
+            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
+                raise ValueError(f"a tensor raster must be 2-D int8 on {dev}")
+            cells = cells.contiguous()
+            shape, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr()), _lib.RBPF_LOAD_DEVICE_IN
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+        else:
+            a = np.asarray(cells)
+            if a.ndim != 2:
+                raise ValueError("raster cells must be 2-D [nx][ny]")
+            if a.dtype != np.int8:
+                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
+                    raise ValueError("raster cells must be int8 lattice values")
+            cells = np.ascontiguousarray(a, dtype=np.int8)
+            shape, ptr = cells.shape, C.c_void_p(cells.ctypes.data)
+        b = np.array([raster.x0, raster.x0 + shape[0], raster.y0, raster.y0 + shape[1]], dtype=np.int32)
+        if shape[0] * shape[1] == 0:
+            ptr = C.c_void_p(1)                          # an empty box writes nothing; the library only checks the box
+        if cur is not None and not same_stream:
+            cur.synchronize()                            # the tensor was written in torch's stream order
+        self._check(self._lib.rbpf_load_map(self._h, p, _ip(b), ptr, flags))
+        del cells                                        # kept alive until the call returned (it is complete on return)
+
+    @property
+    def map_updates(self) -> bool:
+        """True (default): every scan update writes the maps.  False: localization in the maps as they are; the NaN
+        branch's weight is taken on the unchanged map and the random streams advance as with updates on."""
+        on = C.c_int32()
+        self._check(self._lib.rbpf_get_map_updates(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @map_updates.setter
+    def map_updates(self, on: bool):
+        self._check(self._lib.rbpf_set_map_updates(self._h, int(bool(on))))
+
     # -- checkpoint (SURVEY 8f rank 3: a portable replacement of the reference's shelve pickles, main.py:183-210) ----
     CHECKPOINT_VERSION = 1
 
@@ -319,7 +373,7 @@ class ParticleEngine:
         cfg = {k: (list(getattr(self.cfg, k)) if k == "vel_noise" else getattr(self.cfg, k)) for k, _ in self.cfg._fields_}
         np.savez_compressed(path, version=np.array(self.CHECKPOINT_VERSION), config=np.array(json.dumps(cfg)),
                             poses=self.poses(), covs=self.covs(), weights=self.weights(),
-                            rng_state=np.array([su.value, rd.value], dtype=np.uint64),
+                            rng_state=np.array([su.value, rd.value], dtype=np.uint64), map_updates=np.array(int(self.map_updates)),
                             tile_owner=np.array(owner, dtype=np.int32), tile_centre=np.array(centre, dtype=np.float64).reshape(-1, 2),
                             tile_box=np.array(box, dtype=np.int32).reshape(-1, 4),
                             tile_cells=np.concatenate(chunks) if chunks else np.empty(0, dtype=np.int8))
@@ -338,6 +392,7 @@ class ParticleEngine:
                     device=device, seed=cfg["seed"], **over)
             e.set_state(d["poses"], d["covs"], d["weights"])
             e._check(e._lib.rbpf_set_rng_state(e._h, int(d["rng_state"][0]), int(d["rng_state"][1])))
+            e.map_updates = bool(int(d["map_updates"])) if "map_updates" in d.files else True   # absent in older checkpoints
             off = 0
             for p, c, b in zip(d["tile_owner"], d["tile_centre"], d["tile_box"]):
                 n = int((b[1] - b[0]) * (b[3] - b[2]))

@@ -78,3 +78,114 @@ def write_occupancy_map(stem: str, raster: MapRaster, occupied_thresh: float = 0
         f.write(f"occupied_thresh: {float(occupied_thresh)!r}\n")
         f.write(f"free_thresh: {float(free_thresh)!r}\n")
     return pgm, yml
+
+
+def cells_from_probability(p, quantum: float, vmin: float, vmax: float) -> np.ndarray:
+    """int8 lattice values of occupancy probabilities: clip(rint(logit(p) / quantum)) to [vmin, vmax] / quantum (log-odds
+    bounds, e.g. min_odds_emp and max_odds_occ).  The way to load a whole-filter `prob` raster into particles."""
+    p = np.asarray(_host(p), dtype=np.float64)
+    lo, hi = int(np.rint(vmin / quantum)), int(np.rint(vmax / quantum))
+    if not (-128 <= lo <= 0 <= hi <= 127):
+        raise ValueError(f"[vmin, vmax] / quantum = [{lo}, {hi}] must hold 0 and fit int8")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        o = np.log(p) - np.log1p(-p)                     # +-inf at p = 1 / 0: clipped below
+    if np.isnan(o).any():
+        raise ValueError("probabilities must lie in [0, 1]")
+    return np.clip(np.rint(o / quantum), lo, hi).astype(np.int8)
+
+
+def _read_pgm(path: str) -> np.ndarray:
+    """An 8-bit binary (P5) PGM image as uint8 [rows][columns]; `#` comments in the header are skipped."""
+    with open(path, "rb") as f:
+        data = f.read()
+    fields, pos = [], 0
+    while len(fields) < 4:
+        while pos < len(data) and (data[pos:pos + 1].isspace() or data[pos:pos + 1] == b"#"):
+            if data[pos:pos + 1] == b"#":                # a comment runs to the end of its line
+                while pos < len(data) and data[pos:pos + 1] not in (b"\n", b"\r"):
+                    pos += 1
+            pos += 1
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace() and data[end:end + 1] != b"#":
+            end += 1
+        if end == pos:
+            raise ValueError(f"{path}: truncated PGM header")
+        fields.append(data[pos:end])
+        pos = end
+        if len(fields) == 1 and fields[0] != b"P5":
+            raise ValueError(f"{path}: not a binary PGM (P5) image (magic {fields[0][:8]!r})")
+    pos += 1                                             # the single whitespace byte after maxval
+    try:
+        w, h, maxval = int(fields[1]), int(fields[2]), int(fields[3])
+    except ValueError:
+        raise ValueError(f"{path}: malformed PGM header") from None
+    if maxval != 255:
+        raise ValueError(f"{path}: maxval {maxval}, only 8-bit images (255) are read")
+    img = np.frombuffer(data, dtype=np.uint8, count=w * h, offset=pos) if len(data) - pos >= w * h else None
+    if img is None:
+        raise ValueError(f"{path}: {w} x {h} pixels announced, {len(data) - pos} bytes present")
+    return img.reshape(h, w)
+
+
+def _read_yaml(path: str) -> dict:
+    """The flat `key: value` YAML of an occupancy map (numbers, strings, one-line [lists]); `#` starts a comment."""
+    out = {}
+    for line in open(path):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        if ":" not in line:
+            raise ValueError(f"{path}: cannot read line {line!r}")
+        k, v = (x.strip() for x in line.split(":", 1))
+        if v.startswith("[") and v.endswith("]"):
+            out[k] = [float(x) for x in v[1:-1].split(",") if x.strip()]
+        else:
+            v = v.strip("\"'")
+            try:
+                out[k] = float(v)
+            except ValueError:
+                out[k] = v
+    return out
+
+
+def read_occupancy_map(yaml_path: str, quantum: float, vmin: float, vmax: float, mode: str = "scale", *,
+                       cell_size: float = 0.05, tile_len: float = 40.0) -> MapRaster:
+    """Reads a map in the common PGM + YAML format into a MapRaster with int8 `cells` (units of `quantum`), ready for
+    ParticleEngine.load_map.  x0 = origin x / resolution, y0 = origin y / resolution; image row 0 is the largest Y.
+    mode "scale": the pixel's probability through cells_from_probability (write_occupancy_map's output round-trips
+    exactly); "trinary": above occupied_thresh -> vmax, below free_thresh -> vmin, else 0 (for maps of other tools).
+    Refused: a resolution other than `cell_size`, an origin off the cell grid, a non-zero yaw."""
+    if mode not in ("scale", "trinary"):
+        raise ValueError(f"unknown mode {mode!r}")
+    meta = _read_yaml(yaml_path)
+    for k in ("image", "resolution", "origin"):
+        if k not in meta:
+            raise ValueError(f"{yaml_path}: no {k!r}")
+    res = float(meta["resolution"])
+    if abs(res - cell_size) > 1e-9 * cell_size:
+        raise ValueError(f"{yaml_path}: resolution {res!r} differs from the cell size {cell_size!r} (maps are not resampled)")
+    origin = list(meta["origin"])
+    if len(origin) != 3:
+        raise ValueError(f"{yaml_path}: origin must be [x, y, yaw]")
+    if origin[2] != 0.0:
+        raise ValueError(f"{yaml_path}: origin yaw {origin[2]!r}: only unrotated maps are read")
+    x0f, y0f = origin[0] / res, origin[1] / res
+    x0, y0 = int(round(x0f)), int(round(y0f))
+    if abs(x0f - x0) > 1e-6 or abs(y0f - y0) > 1e-6:
+        raise ValueError(f"{yaml_path}: origin ({origin[0]!r}, {origin[1]!r}) is not a whole number of cells")
+    img_path = str(meta["image"])
+    if not os.path.isabs(img_path):
+        img_path = os.path.join(os.path.dirname(os.path.abspath(yaml_path)), img_path)
+    pix = _read_pgm(img_path).astype(np.float64)
+    p = pix / 255.0 if int(meta.get("negate", 0)) else (255.0 - pix) / 255.0
+    p = np.ascontiguousarray(p[::-1, :].T)               # [X - x0][Y - y0]
+    if mode == "scale":
+        cells = cells_from_probability(p, quantum, vmin, vmax)
+    else:
+        occ_t, free_t = float(meta.get("occupied_thresh", 0.65)), float(meta.get("free_thresh", 0.196))
+        cells = np.zeros(p.shape, dtype=np.int8)
+        cells[p > occ_t] = int(np.rint(vmax / quantum))
+        cells[p < free_t] = int(np.rint(vmin / quantum))
+    dim = int(round(tile_len / cell_size))
+    return MapRaster(x0=x0, y0=y0, cell_size=float(cell_size), quantum=float(quantum), dim=dim, tile_len=float(tile_len),
+                     cells=cells)

@@ -118,10 +118,11 @@ class ParticleFilter:
     """NUM_PARTICLES robots (main.py:44,87) as one batched engine."""
 
     def __init__(self, n_particles: int, angles, motion_model: str = "velocity", *, cell_size: float = 0.05,
-                 keep_history: bool = True, seed: int = 42, **engine_options):
+                 keep_history: bool = True, seed: int = 42, map_updates: bool = True, **engine_options):
         self.angles = np.ascontiguousarray(angles, dtype=np.float64)
         self.engine = ParticleEngine(n_particles, max_beams=len(self.angles), cell_size=cell_size, seed=seed,
                                      pool_tiles=engine_options.pop("pool_tiles", 4 * n_particles + 16), **engine_options)
+        self.engine.map_updates = map_updates        # False: localization in a map given by load_map
         self.motion_model = motion_model
         self.particles = [Robot(self, i) for i in range(n_particles)]
         self.keep_history = keep_history
@@ -147,6 +148,18 @@ class ParticleFilter:
     def render_map(self, particle=None, box=None, weights=None, device: bool = False, fields=("prob", "occ_frac")):
         """The map of one particle ("best": the heaviest) or of the whole filter (ParticleEngine.render_map)."""
         return self.engine.render_map(particle, box=box, weights=weights, device=device, fields=fields)
+
+    def load_map(self, raster, particle=None):
+        """A prior map (a MapRaster with int8 cells, e.g. mapio.read_occupancy_map) into one particle or into all (None)."""
+        self.engine.load_map(raster, particle)
+
+    @property
+    def map_updates(self) -> bool:
+        return self.engine.map_updates
+
+    @map_updates.setter
+    def map_updates(self, on: bool):
+        self.engine.map_updates = on
 
     def _record(self, anc):
         if self.keep_history:
