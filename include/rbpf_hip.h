@@ -321,6 +321,25 @@ int  rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const 
 int  rbpf_set_map_updates(rbpf_handle* h, int32_t on);
 int  rbpf_get_map_updates(rbpf_handle* h, int32_t* on);
 
+/* ---- scan casting: what a lidar at a pose would see in a particle's map ------------------------------------------------
+ * particle >= 0: all n_poses poses (x, y, theta) are cast in that particle's map.  particle == -1: n_poses must equal P
+ * and pose n is cast in particle n's map.  Beam b of pose n leaves (x, y) in direction theta + angles[b] (sensor frame, x
+ * forward, as rbpf_set_scan) and walks the supercover (4-connected) sequence of mosaic cells it crosses, in float64 (the
+ * walk is spelled out in DESIGN.md 3.7): the first cell with cell * quantum > occupied_threshold ends it.
+ *   ranges[n_poses][n_beams]  metres from the origin to the point where the ray ENTERS the hit cell (0 when it starts in
+ *                             an occupied cell); max_range where status is not 1
+ *   status[n_poses][n_beams]  1 hit; 0 nothing occupied within max_range; 2 the ray (or its origin) left the tile lattice
+ *                             before either.  May be NULL.
+ * A lattice position without a tile and a cell outside its tile's written box are free.  Independent of rbpf_set_scan: any
+ * n_beams >= 1, n_poses * n_beams < 2^31, no scan needs to be set.  cos and sin of theta and of the angles are host libm
+ * values.  A NULL poses_n3, angles or ranges, a non-finite pose or angle, max_range not finite or not > 0, a bad particle,
+ * n_poses != P with particle == -1 or an unknown flag is RBPF_EINVAL, checked before anything is queued: nothing is
+ * written.  The call changes no engine state (maps, particles, random streams, counters).  It runs on the handle's
+ * stream; without RBPF_CAST_DEVICE_OUT the outputs are host arrays, complete on return. */
+#define RBPF_CAST_DEVICE_OUT 1u    /* ranges / status are device pointers, written in stream order, no host wait */
+int  rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* angles,
+                     int32_t n_beams, double max_range, uint32_t flags, double* ranges, uint8_t* status);
+
 #ifdef __cplusplus
 }
 #endif

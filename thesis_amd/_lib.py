@@ -15,6 +15,7 @@ RBPF_OK = 0
 RBPF_EINVAL, RBPF_ENOMEM, RBPF_EDEVICE, RBPF_ESTATE, RBPF_ERANGE = -1, -2, -3, -4, -5
 RBPF_RENDER_DEVICE_OUT = 1
 RBPF_LOAD_DEVICE_IN = 1
+RBPF_CAST_DEVICE_OUT = 1
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
 
 
@@ -111,6 +112,7 @@ PROTOTYPES = {
     "rbpf_load_map": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_uint32]),
     "rbpf_set_map_updates": (C.c_int, [_H, C.c_int32]),
     "rbpf_get_map_updates": (C.c_int, [_H, _I]),
+    "rbpf_cast_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

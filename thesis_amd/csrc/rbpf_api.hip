@@ -323,11 +323,12 @@ int rbpf_destroy(rbpf_handle* h) {
     if (h->h_jobs_used) wait_ev(h->ev_jobs);
     if (h->ev_weights_valid) wait_ev(h->ev_weights);
     if (h->ev_render_used) wait_ev(h->ev_render);
+    if (h->ev_cast_used) wait_ev(h->ev_cast);
     for (rbpf_handle::PinnedRing* r : {&h->ring_scan, &h->ring_last, &h->ring_idx})
         for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->used[i]) wait_ev(r->ev[i]);
     for (void* p : h->allocs) (void)hipFree(p);
     for (void* p : {(void*)h->d_guess, (void*)h->d_prs, (void*)h->d_w, (void*)h->d_gT, (void*)h->d_gidx, (void*)h->d_i32, (void*)h->d_jobs,
-                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out, (void*)h->d_load})
+                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out, (void*)h->d_load, (void*)h->d_cast})
         if (p) (void)hipFree(p);
     if (h->h_jobs) (void)hipHostFree(h->h_jobs);
     if (h->h_early) (void)hipHostFree(h->h_early);
@@ -335,7 +336,7 @@ int rbpf_destroy(rbpf_handle* h) {
         if (r->base) (void)hipHostFree(r->base);
         for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
     }
-    for (hipEvent_t ev : {h->ev_weights, h->ev_jobs, h->ev_early, h->ev_render}) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : {h->ev_weights, h->ev_jobs, h->ev_early, h->ev_render, h->ev_cast}) if (ev) (void)hipEventDestroy(ev);
     for (int k = 0; k < rbpf_handle::N_KERN; ++k) for (int e = 0; e < 2; ++e) for (auto& ev : h->ring[k][e]) if (ev) (void)hipEventDestroy(ev);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     (void)hipGetLastError();
@@ -1564,6 +1565,59 @@ int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const i
     if (bad) return fail(h, RBPF_EINVAL, "cell value outside [min_odds_emp, max_odds_occ]");
     v.dups_valid = 0;                   // a duplicate's map may differ from its representative's now
     return check_device_error(h);
+}
+
+// ---- scan casting (kernels_cast.hip) --------------------------------------------------------------------------------------
+int rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* angles,
+                    int32_t n_beams, double max_range, uint32_t flags, double* ranges, uint8_t* status) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!poses_n3 || !angles || !ranges) return fail(h, RBPF_EINVAL, "poses, angles or ranges is NULL");
+    if (flags & ~RBPF_CAST_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (n_poses < 0 || n_beams < 1 || (long long)n_poses * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_poses >= 0, n_beams >= 1 and n_poses * n_beams < 2^31 are required");
+    if (particle < 0 && n_poses != v.P) return fail(h, RBPF_EINVAL, "particle -1 casts pose n in particle n's map: n_poses must equal n_particles");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    for (long long k = 0; k < 3LL * n_poses; ++k)
+        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    if (n_poses == 0) return RBPF_OK;
+    const bool dev_out = (flags & RBPF_CAST_DEVICE_OUT) != 0;
+    const size_t rays = (size_t)n_poses * n_beams;
+    const size_t in_b = (size_t)n_poses * 32 + (size_t)n_beams * 16, out_b = dev_out ? 0 : rays * 8 + (status ? rays : 0);
+    int rc = render_buffer(h, &h->d_cast, &h->d_cast_cap, in_b + out_b);
+    if (rc) return rc;
+    if (h->ev_cast_used) HIP_TRY(h, hipEventSynchronize(h->ev_cast));     // the last upload may still read h_cast
+    h->h_cast.resize(in_b);
+    double* st = reinterpret_cast<double*>(h->h_cast.data());
+    for (int n = 0; n < n_poses; ++n) {                                    // host libm, as rbpf_set_scan
+        st[4 * (size_t)n] = poses_n3[3 * (size_t)n]; st[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
+        st[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); st[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
+    }
+    double* sb = st + 4 * (size_t)n_poses;
+    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    if (!h->ev_cast) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_cast, hipEventDisableTiming));
+    HIP_TRY(h, hipMemcpyAsync(h->d_cast, st, in_b, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev_cast, h->stream));
+    h->ev_cast_used = true;
+    CastArgs a;
+    a.pose4 = reinterpret_cast<const double*>(h->d_cast);
+    a.beam2 = a.pose4 + 4 * (size_t)n_poses;
+    a.n_poses = n_poses; a.B = n_beams; a.particle = particle;
+    a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as lookup_cell_fast forms it
+    a.tlim = max_range * a.inv; a.max_range = max_range;
+    a.ranges = dev_out ? ranges : reinterpret_cast<double*>(h->d_cast + in_b);
+    a.status = !status ? nullptr : dev_out ? status : h->d_cast + in_b + rays * 8;
+    launch_cast_scans(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(ranges, a.ranges, rays * 8, hipMemcpyDeviceToHost, h->stream));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, a.status, rays, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
 }
 
 }  // extern "C"

@@ -137,6 +137,15 @@ struct LoadArgs {
     int p_lo, p_hi;                    // particles [p_lo, p_hi)
     int32_t* bad;                      // [1] != 0: validation found a value out of range - the alloc and write kernels do nothing
 };
+// scan casting (kernels_cast.hip): ray r = pose * B + beam; the trigonometry is done on the host
+struct CastArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
+    const double* beam2;               // [B][2] cos(angle), sin(angle)
+    int n_poses, B;
+    int particle;                      // >= 0: every pose in this particle's map; -1: pose n in particle n's
+    double inv, tlim, max_range;       // cells per metre (dim / tile_len), max_range * inv, max_range
+    double* ranges; uint8_t* status;   // [n_poses][B]; status may be null
+};
 
 }  // namespace rbpf
 
@@ -183,6 +192,8 @@ struct rbpf_handle {
     unsigned char* d_render_out = nullptr; size_t d_render_out_cap = 0;
     std::vector<unsigned char> h_render; hipEvent_t ev_render = nullptr; bool ev_render_used = false;
     unsigned char* d_load = nullptr; size_t d_load_cap = 0;   // map loading: flag, touched tiles, jobs, host raster
+    // scan casting: poses, beams and (for host outputs) ranges and status; staged through h_cast, reusable once ev_cast completed
+    unsigned char* d_cast = nullptr; size_t d_cast_cap = 0; std::vector<unsigned char> h_cast; hipEvent_t ev_cast = nullptr; bool ev_cast_used = false;
     bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
@@ -254,4 +265,5 @@ void launch_render_cells(const DevView& v, int particle, const RenderJob* d_jobs
 void launch_render_filter(const DevView& v, const RenderFilter& f, int n_jobs, int G, hipStream_t s);   // G particle chunks
 void launch_load_validate(const DevView& v, const LoadArgs& a, hipStream_t s);
 void launch_load_map(const DevView& v, const LoadArgs& a, int n_jobs, hipStream_t s);   // tile allocation, then the cells
+void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
 }  // namespace rbpf

@@ -462,6 +462,48 @@ class ParticleEngine:
         return MapRaster(x0=int(b[0]), y0=int(b[2]), cell_size=float(self.cfg.cell_size), quantum=float(self.cfg.quantum),
                          dim=self.dim, tile_len=float(self.cfg.tile_len_m), cells=outs[0], prob=outs[1], occ_frac=outs[2])
 
+    # -- scan casting (include/rbpf_hip.h: rbpf_cast_scans; thesis_amd/datasets/mapsim.py) ------------------------------------
+    def cast_scans(self, poses, angles, particle=None, max_range: Optional[float] = None, device: bool = False,
+                   return_status: bool = False):
+        """What a lidar with beam directions `angles` [B] (sensor frame) would see from `poses` [N, 3] (or [3]) in a
+        particle's map: `particle` an index, "best" (the first argmax of weights()) or None (pose n in particle n's map,
+        N == P; e.g. poses()).  Returns ranges [N, B] in metres, max_range (default cfg.weight_max_range) where nothing
+        occupied was met; with return_status also status [N, B] uint8 (1 hit, 0 none within max_range, 2 left the tile
+        lattice).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        ps = _f64(poses)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        a = _f64(angles)
+        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1:
+            raise ValueError("poses must be [N, 3] (or [3]) and angles 1-D")
+        shape = (ps.shape[0], a.shape[0])
+        mr = float(self.cfg.weight_max_range if max_range is None else max_range)
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            r = torch.empty(shape, dtype=torch.float64, device=dev)
+            st = torch.empty(shape, dtype=torch.uint8, device=dev) if return_status else None
+            ptrs = [C.c_void_p(r.data_ptr() or 1), None if st is None else C.c_void_p(st.data_ptr() or 1)]   # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            r = np.empty(shape, dtype=np.float64)
+            st = np.empty(shape, dtype=np.uint8) if return_status else None
+            ptrs = [C.c_void_p(r.ctypes.data), None if st is None else C.c_void_p(st.ctypes.data)]
+        self._check(self._lib.rbpf_cast_scans(self._h, p, _dp(ps), shape[0], _dp(a), shape[1], mr,
+                                              _lib.RBPF_CAST_DEVICE_OUT if device else 0, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        return (r, st) if return_status else r
+
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)
         vals = np.empty(len(pts))
