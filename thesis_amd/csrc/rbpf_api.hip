@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <limits>
 
-#include "rbpf_internal.h"
+#include "rbpf_host.h"
 
 using namespace rbpf;
 
@@ -44,11 +44,10 @@ static int fail(rbpf_handle* h, int code, const std::string& msg) {
 
 template <typename T>
 static int dev_alloc(rbpf_handle* h, T** out, size_t n) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+    h->allocs.emplace_back();
+    hipError_t e = h->allocs.back().reserve(n * sizeof(T));
     if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return RBPF_ENOMEM; }
-    h->allocs.push_back(p);
-    *out = static_cast<T*>(p);
+    *out = h->allocs.back().as<T>();
     return RBPF_OK;
 }
 #define ALLOC(h, ptr, n) do { int rc_ = dev_alloc(h, &(ptr), (n)); if (rc_) return rc_; } while (0)
@@ -69,16 +68,7 @@ static int check_device_error(rbpf_handle* h) {
     return RBPF_OK;
 }
 
-template <typename T>
-static int scratch(rbpf_handle* h, T** ptr, size_t* cap, size_t n) {
-    if (*cap >= n) return RBPF_OK;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    size_t want = std::max<size_t>(n, 1024);
-    HIP_TRY(h, hipMalloc((void**)ptr, want * sizeof(T)));
-    *cap = want;
-    return RBPF_OK;
-}
+static bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && strcmp(e, value) == 0; }
 
 extern "C" {
 
@@ -195,7 +185,7 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
                 h->ring[k][e].resize(rbpf_handle::RING);
                 // timing only: no system-scope fence when the event completes (it would flush the caches between the
                 // kernels it brackets and slow the very thing it measures)
-                for (auto& ev : h->ring[k][e]) HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableSystemFence));
+                for (auto& ev : h->ring[k][e]) HIP_TRY(h, h->events.create(&ev, hipEventDisableSystemFence));
                 h->begin_used[k].assign(rbpf_handle::RING, nullptr);
             }
         const size_t P = v.P, LL = (size_t)v.L * v.L, cells = (size_t)dim * dim;
@@ -231,13 +221,9 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
             v.bflags = d + 3 * MBP * 8 + 4 * MBP * 4;
             v.wsel_x = reinterpret_cast<const float*>(d + 3 * MBP * 8 + 4 * MBP * 4 + MBP); v.wsel_y = v.wsel_x + MBW;
             v.wsel_idx = reinterpret_cast<const uint16_t*>(v.wsel_y + MBW);
-            rbpf_handle::PinnedRing* rings[3] = {&h->ring_scan, &h->ring_last, &h->ring_idx};
-            const size_t bytes[3] = {h->scan_bytes, MB * 16, (size_t)P * 8};
-            for (int r = 0; r < 3; ++r) {
-                rings[r]->slot_bytes = (bytes[r] + 255) & ~(size_t)255;
-                HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&rings[r]->base), rings[r]->slot_bytes * rbpf_handle::PinnedRing::N, hipHostMallocDefault));
-                for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) HIP_TRY(h, hipEventCreateWithFlags(&rings[r]->ev[i], hipEventDisableTiming | hipEventDisableSystemFence));   // guards host memory the copy only reads
-            }
+            HIP_TRY(h, h->rings[R_SCAN].create(h->scan_bytes));
+            HIP_TRY(h, h->rings[R_LAST].create(MB * 16));
+            HIP_TRY(h, h->rings[R_IDX].create((size_t)P * 8));
         }
         ALLOC(h, v.upd_pose, 3 * P);
         ALLOC(h, v.prop_prep, 24 * P);
@@ -246,31 +232,25 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
         ALLOC(h, v.mu_fallback, P); HIP_TRY(h, hipMemset(v.mu_fallback, 0, P * 4));
         ALLOC(h, h->d_did_early, 1);
         HIP_TRY(h, hipMemset(h->d_did_early, 0, 4));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_weights, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_early, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_jobs, hipEventDisableTiming | hipEventDisableSystemFence));
+        HIP_TRY(h, h->events.create(&h->ev_weights, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
         {   // RBPF_MAP_KERNEL=window keeps the 128x128-window map update for every particle, =ray / =ev run that first kernel (and
             // windows behind it); default: the event-walk kernel, windows for what it gives back (tests, comparisons)
-            const char* mk = getenv("RBPF_MAP_KERNEL");
-            v.mu_mode = (mk && std::string(mk) == "window") ? MU_WINDOW : (mk && std::string(mk) == "ray") ? MU_RAY : (mk && std::string(mk) == "ev") ? MU_EV : MU_DEFAULT;
-            const char* ms = getenv("RBPF_MATCH_STAGE");    // "slow": the matcher's field is staged bit by bit (tests)
-            v.match_stage_slow = (ms && std::string(ms) == "slow") ? 1 : 0;
+            v.mu_mode = env_is("RBPF_MAP_KERNEL", "window") ? MU_WINDOW : env_is("RBPF_MAP_KERNEL", "ray") ? MU_RAY : env_is("RBPF_MAP_KERNEL", "ev") ? MU_EV : MU_DEFAULT;
+            v.match_stage_slow = env_is("RBPF_MATCH_STAGE", "slow") ? 1 : 0;    // the matcher's field is staged bit by bit (tests)
             const char* ws = getenv("RBPF_WSAFE");          // test knob: the weighting's guard band in cells (0 shows what the band is for)
             v.wsafe_override = ws ? (float)atof(ws) : -1.0f;
-            const char* we = getenv("RBPF_WEIGHT_ENTRY");   // "f64": rbpf_weight_samples runs the float64 kernel (comparison)
-            v.weight_entry_f64 = (we && std::string(we) == "f64") ? 1 : 0;
+            v.weight_entry_f64 = env_is("RBPF_WEIGHT_ENTRY", "f64") ? 1 : 0;   // rbpf_weight_samples runs the float64 kernel (comparison)
             v.ndt_refine = h->cfg.ndt_refine;
-            const char* dd = getenv("RBPF_MATCH_DEDUP");     // "0": every particle runs the matcher, duplicates included (tests)
-            h->dedup_enabled = !(dd && std::string(dd) == "0");
+            h->dedup_enabled = !env_is("RBPF_MATCH_DEDUP", "0");   // "0": every particle runs the matcher, duplicates included (tests)
         }
         ALLOC(h, v.dup_of, P); v.dups_valid = 0;
         ALLOC(h, h->d_last_xy, 2 * (size_t)c.max_beams); ALLOC(h, h->d_tmp_sel, 2 * (size_t)c.max_beams);
-        if (raycast_lds_bytes(c.max_beams, v.reach) > 160 * 1024) return fail(h, RBPF_EINVAL, "max_beams too large for the LDS window layout");
+        if (raycast_lds_bytes(c.max_beams, v.reach) > LDS_LIMIT) return fail(h, RBPF_EINVAL, "max_beams too large for the LDS window layout");
         match_geometry(c, c.cell_size, h->mN, h->mds, h->mmcs, h->md0, h->mncr);
         h->mlds = match_lds_bytes(h->mN, c.max_beams, match_max_coarse(h->mncr, 0.7, h->mmcs), match_per_rot(0.7, h->mmcs));
-        if (h->mlds > 160 * 1024) return fail(h, RBPF_EINVAL, "matcher region does not fit in LDS for this cell_size");
+        if (h->mlds > LDS_LIMIT) return fail(h, RBPF_EINVAL, "matcher region does not fit in LDS for this cell_size");
         if (c.ndt_refine && ndt_cells(h->mmcs) >= 2) {         // the matcher hands its staged field to the NDT kernel
-            if (ndt_lds_bytes(h->mN, c.max_beams) > 160 * 1024) return fail(h, RBPF_EINVAL, "NDT stage: matcher region does not fit in LDS");
+            if (ndt_lds_bytes(h->mN, c.max_beams) > LDS_LIMIT) return fail(h, RBPF_EINVAL, "NDT stage: matcher region does not fit in LDS");
             ALLOC(h, v.ndt_occ, P * (size_t)h->mN * (h->mN / 32)); ALLOC(h, v.ndt_aux, 5 * P);
         }
         ALLOC(h, h->d_match, 13 * P); ALLOC(h, h->d_bad, P); ALLOC(h, h->d_guess_full, P * (size_t)c.n_samples * 3);
@@ -299,7 +279,6 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
         HIP_TRY(h, hipMemcpy(v.free_stack, fs.data(), (size_t)v.pool_tiles * 4, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(v.free_top, &top, 4, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(v.tile_bbox, bb.data(), bb.size() * 4, hipMemcpyHostToDevice));
-        // the ray-cast kernel needs more than the default 64 KiB of dynamic LDS
         return RBPF_OK;
     };
     rc = build();
@@ -309,35 +288,22 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
 }
 
 // Teardown order: (1) everything queued on the handle's stream has finished; (2) every event that guards host memory
-// a kernel or a copy may still touch has completed - the early read-back and the pinned rings can be in use by work on
-// ANOTHER stream (rbpf_resample_indices_global_early takes one); (3) device memory, pinned memory, events; (4) the
+// a kernel or a copy may still touch has completed (every Staging, the rings' slots included, and ev_weights) - the early
+// read-back and the pinned rings can be in use by work on ANOTHER stream (rbpf_resample_indices_global_early takes one);
+// (3) device memory (dev_alloc's, then every DevBuf), host staging memory, events, each kind in one loop; (4) the
 // stream, only if the handle created it.  A borrowed stream (rbpf_set_stream) is synchronised once and otherwise left
 // alone: it belongs to the caller and may already be gone when a late destructor runs.
 int rbpf_destroy(rbpf_handle* h) {
     if (!h) return RBPF_OK;
     ON_DEVICE(h);
-    if (h->stream || h->own_stream) { if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError(); }
-    else if (hipStreamSynchronize(nullptr) != hipSuccess) (void)hipGetLastError();       // borrowed null stream
-    auto wait_ev = [](hipEvent_t ev) { if (ev && hipEventSynchronize(ev) != hipSuccess) (void)hipGetLastError(); };
-    if (h->early_n > 0 || h->h_early) wait_ev(h->ev_early);
-    if (h->h_jobs_used) wait_ev(h->ev_jobs);
-    if (h->ev_weights_valid) wait_ev(h->ev_weights);
-    if (h->ev_render_used) wait_ev(h->ev_render);
-    if (h->ev_cast_used) wait_ev(h->ev_cast);
-    for (rbpf_handle::PinnedRing* r : {&h->ring_scan, &h->ring_last, &h->ring_idx})
-        for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->used[i]) wait_ev(r->ev[i]);
-    for (void* p : h->allocs) (void)hipFree(p);
-    for (void* p : {(void*)h->d_guess, (void*)h->d_prs, (void*)h->d_w, (void*)h->d_gT, (void*)h->d_gidx, (void*)h->d_i32, (void*)h->d_jobs,
-                    (void*)h->d_render, (void*)h->d_render_part, (void*)h->d_render_out, (void*)h->d_load, (void*)h->d_cast})
-        if (p) (void)hipFree(p);
-    if (h->h_jobs) (void)hipHostFree(h->h_jobs);
-    if (h->h_early) (void)hipHostFree(h->h_early);
-    for (rbpf_handle::PinnedRing* r : {&h->ring_scan, &h->ring_last, &h->ring_idx}) {
-        if (r->base) (void)hipHostFree(r->base);
-        for (int i = 0; i < rbpf_handle::PinnedRing::N; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
-    }
-    for (hipEvent_t ev : {h->ev_weights, h->ev_jobs, h->ev_early, h->ev_render, h->ev_cast}) if (ev) (void)hipEventDestroy(ev);
-    for (int k = 0; k < rbpf_handle::N_KERN; ++k) for (int e = 0; e < 2; ++e) for (auto& ev : h->ring[k][e]) if (ev) (void)hipEventDestroy(ev);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError();          // nullptr: a borrowed null stream
+    h->each_staging([](Staging& s) { if (s.wait() != hipSuccess) (void)hipGetLastError(); });
+    if (h->ev_weights_valid && hipEventSynchronize(h->ev_weights) != hipSuccess) (void)hipGetLastError();
+    for (Block& b : h->allocs) b.release();
+    for (Block& b : h->buf) b.release();
+    h->each_staging([](Staging& s) { s.release(); });
+    h->each_staging([](Staging& s) { s.destroy_event(); });
+    h->events.destroy();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     (void)hipGetLastError();
     delete h;
@@ -364,7 +330,7 @@ int rbpf_release_stream(rbpf_handle* h) {
     ON_DEVICE(h);
     if (h->own_stream) return RBPF_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->early_n > 0) HIP_TRY(h, hipEventSynchronize(h->ev_early));
+    if (h->early_n > 0) HIP_TRY(h, h->stage[S_EARLY].wait());
     h->stream = nullptr;
     HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
@@ -463,17 +429,14 @@ int rbpf_get_counters(rbpf_handle* h, rbpf_counters* out) {
 // the scan block from sensor-frame end points: range classes, compacted matcher lists, one upload
 static int upload_scan_points(rbpf_handle* h, const double* px, const double* py, int32_t B) {
     const rbpf_config& c = h->cfg;
-    const size_t MBP = ((size_t)c.max_beams + 15) & ~(size_t)15;
-    unsigned char* slot = static_cast<unsigned char*>(h->ring_scan.acquire());
-    double* sx = reinterpret_cast<double*>(slot);
-    double* sy = sx + MBP;
-    double* sc = sy + MBP;
-    float* mx = reinterpret_cast<float*>(slot + 3 * MBP * 8);               // compacted beam lists for the matcher
-    float* my = mx + MBP; float* ax = my + MBP; float* ay = ax + MBP;       // (float32, sensor frame)
-    uint8_t* fl = slot + 3 * MBP * 8 + 4 * MBP * 4;
-    const size_t MBW = ((size_t)c.max_beams + 63) & ~(size_t)63;
-    float* wx = reinterpret_cast<float*>(fl + MBP); float* wy = wx + MBW;   // the weighting's beams (kernels_propose.hip, weight_beams)
-    uint16_t* wi = reinterpret_cast<uint16_t*>(wy + MBW);
+    DevView& v = h->v;
+    unsigned char* slot = static_cast<unsigned char*>(h->rings[R_SCAN].acquire());
+    double *sx = h->in_slot(slot, v.bx), *sy = h->in_slot(slot, v.by), *sc = h->in_slot(slot, v.bscale);
+    float *mx = h->in_slot(slot, v.msel_x), *my = h->in_slot(slot, v.msel_y);       // compacted beam lists for the matcher
+    float *ax = h->in_slot(slot, v.asel_x), *ay = h->in_slot(slot, v.asel_y);       // (float32, sensor frame)
+    uint8_t* fl = h->in_slot(slot, v.bflags);
+    float *wx = h->in_slot(slot, v.wsel_x), *wy = h->in_slot(slot, v.wsel_y);       // the weighting's beams (kernels_propose.hip, weight_beams)
+    uint16_t* wi = h->in_slot(slot, v.wsel_idx);
     const float w_inv_cs = (float)((double)h->v.dim / h->v.tile_len), w_lim = 1.5f * (float)h->v.dim;
     int nm = 0, na = 0, nw = 0;
     for (int i = 0; i < B; ++i) {
@@ -495,14 +458,8 @@ static int upload_scan_points(rbpf_handle* h, const double* px, const double* py
         }
     }
     for (int i = nw; i < ((nw + 63) & ~63); ++i) { wx[i] = NAN; wy[i] = 0.0f; wi[i] = 0; }
-    DevView& v = h->v;
     v.n_msel = nm; v.n_asel = na; v.n_wsel = nw;
-    {   // pinned and device-mapped: a kernel pulls the block over (no copy-engine latency in the stream); DMA otherwise
-        void* mapped = nullptr;
-        if (hipHostGetDevicePointer(&mapped, slot, 0) == hipSuccess && mapped) launch_ingest(mapped, h->d_scan, h->scan_bytes, h->stream);
-        else { (void)hipGetLastError(); HIP_TRY(h, hipMemcpyAsync(h->d_scan, slot, h->scan_bytes, hipMemcpyHostToDevice, h->stream)); }
-    }
-    h->ring_scan.submitted(h->stream);
+    HIP_TRY(h, h->rings[R_SCAN].upload(h->d_scan, h->scan_bytes, h->stream));
     v.B = B;
     h->have_scan = true;
     return RBPF_OK;
@@ -539,32 +496,22 @@ int rbpf_imu_update(rbpf_handle* h, int32_t model, const double* d, double dt_ti
 }
 
 // ---- a4 test entry --------------------------------------------------------------------------------------
-static int ensure_sample_buffers(rbpf_handle* h, size_t n) {
-    if (h->d_guess_n >= n) return RBPF_OK;
-    if (h->d_guess) { hipFree(h->d_guess); hipFree(h->d_prs); hipFree(h->d_w); h->d_guess = nullptr; }
-    HIP_TRY(h, hipMalloc((void**)&h->d_guess, n * 3 * 8));
-    HIP_TRY(h, hipMalloc((void**)&h->d_prs, n * 8));
-    HIP_TRY(h, hipMalloc((void**)&h->d_w, n * 8));
-    h->d_guess_n = n;
-    return RBPF_OK;
-}
-
 int rbpf_weight_samples(rbpf_handle* h, const double* guesses, const double* prs, int32_t K, double* out_w) {
     if (!h || !guesses || !prs || !out_w) return RBPF_EINVAL;
     ON_DEVICE(h);
     if (!h->have_scan) return fail(h, RBPF_ESTATE, "rbpf_set_scan has not been called");
     if (K < 1 || K > 32) return fail(h, RBPF_EINVAL, "n_samples must be in 1..32");
     const size_t n = (size_t)h->v.P * K;
-    int rc = ensure_sample_buffers(h, n);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_guess, guesses, n * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_prs, prs, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, h->reserve(B_SAMPLES, n * 5 * 8));
+    double *d_guess = h->buf[B_SAMPLES].as<double>(), *d_prs = d_guess + 3 * n, *d_w = d_prs + n;
+    HIP_TRY(h, hipMemcpyAsync(d_guess, guesses, n * 3 * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_prs, prs, n * 8, hipMemcpyHostToDevice, h->stream));
     h->prof_begin(1);
-    if (h->v.weight_entry_f64 || K > 32) launch_weight_samples(h->v, h->d_guess, h->d_prs, K, h->d_w, h->stream);
-    else launch_weight_samples_product(h->v, h->d_guess, h->d_prs, K, h->d_w, h->stream);   // the look-ups of every scan step (kernels_propose.hip)
+    if (h->v.weight_entry_f64) launch_weight_samples(h->v, d_guess, d_prs, K, d_w, h->stream);
+    else launch_weight_samples_product(h->v, d_guess, d_prs, K, d_w, h->stream);   // the look-ups of every scan step (kernels_propose.hip)
     h->prof_end(1);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out_w, h->d_w, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_w, d_w, n * 8, hipMemcpyDeviceToHost, h->stream));
     return check_device_error(h);
 }
 
@@ -573,12 +520,9 @@ static int run_map_update(rbpf_handle* h, const uint8_t* d_bad = nullptr) {
     DevView& v = h->v;
     // The map update's timing events ride on the first kernel's dispatch (its own start and end: the dominant kernel, without
     // the follow-up launch that usually finds nothing to do) - two event records and their barriers less in the stream per step.
-    if (((h->prof_mask >> 0) & 1u) && map_update_first_kernel(v) != 0) {
-        const int slot = h->ring_n[0] % rbpf_handle::RING;
-        hipEvent_t t0 = h->ring[0][0][slot], t1 = h->ring[0][1][slot];
-        launch_map_update_fused(v, d_bad, h->stream, t0, t1);
-        h->begin_used[0][slot] = t0; h->last_end = nullptr; h->ring_n[0]++;
-    } else {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (map_update_first_kernel(v) != 0 && h->prof_take(0, t0, t1)) launch_map_update_fused(v, d_bad, h->stream, t0, t1);
+    else {
         h->prof_begin(0);
         launch_map_update_fused(v, d_bad, h->stream);
         h->prof_end(0);
@@ -618,21 +562,19 @@ static int run_matcher(rbpf_handle* h, int32_t adj, const double* last_scan_xy, 
     } else if (adj && (n_last < 0 || n_last > h->cfg.max_beams))
         return fail(h, RBPF_EINVAL, "adj = 1 needs last_scan_xy with at most max_beams points");
     if (adj && last_scan_xy) {
-        void* slot = h->ring_last.acquire();
+        void* slot = h->rings[R_LAST].acquire();
         memcpy(slot, last_scan_xy, (size_t)n_last * 16);
         HIP_TRY(h, hipMemcpyAsync(h->d_last_xy, slot, (size_t)n_last * 16, hipMemcpyHostToDevice, h->stream));
-        h->ring_last.submitted(h->stream);
+        h->rings[R_LAST].submitted(h->stream);
     }
     // both stages are one kernel each: their timing events ride on the dispatch and take the kernel's own start and end
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    auto take_events = [&](int k) { t0 = t1 = nullptr; if (!((h->prof_mask >> k) & 1u)) return; const int slot = h->ring_n[k] % rbpf_handle::RING;
-                                    t0 = h->ring[k][0][slot]; t1 = h->ring[k][1][slot]; h->begin_used[k][slot] = t0; h->last_end = nullptr; h->ring_n[k]++; };
-    take_events(3);
+    h->prof_take(3, t0, t1);
     h->match_rows = v.dups_valid ? 2 : 1;
     const bool ndt = launch_match_particles(v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
                                             h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, 1, h->stream, t0, t1);
     if (ndt) {
-        take_events(4);
+        h->prof_take(4, t0, t1);
         launch_match_particles(v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
                                h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, 2, h->stream, t0, t1);
     }
@@ -731,24 +673,23 @@ int rbpf_match_scan(rbpf_handle* h, const double* curr_xy, int32_t n_curr, const
     if (ncr < 0) ncr = 0;
     size_t lds = match_lds_bytes(N, h->cfg.max_beams, match_max_coarse(ncr, std::max(pose_range3[0], pose_range3[1]), mcs),
                                  match_per_rot(std::max(pose_range3[0], pose_range3[1]), mcs));
-    if (lds > 160 * 1024) return fail(h, RBPF_EINVAL, "matcher region does not fit in LDS for this resolution");
+    if (lds > LDS_LIMIT) return fail(h, RBPF_EINVAL, "matcher region does not fit in LDS for this resolution");
     std::vector<float> sel(2 * (size_t)h->cfg.max_beams, 0.f);
     for (int i = 0; i < n_curr; ++i) { sel[i] = (float)curr_xy[2 * i]; sel[h->cfg.max_beams + i] = (float)curr_xy[2 * i + 1]; }
-    double *d_ref = nullptr, *d_out = nullptr, *d_aux = nullptr; uint32_t* d_occ = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d_ref, std::max<size_t>((size_t)n_ref, 1) * 16));
-    HIP_TRY(h, hipMalloc((void**)&d_out, 13 * 8));
-    if (c.ndt_refine && ndt_cells(mcs) >= 2 && ndt_lds_bytes(N, h->cfg.max_beams) <= 160 * 1024) {
-        HIP_TRY(h, hipMalloc((void**)&d_occ, (size_t)N * (N / 32) * 4));
-        HIP_TRY(h, hipMalloc((void**)&d_aux, 5 * 8));
+    DevTemp d_ref, d_out, d_occ, d_aux;
+    HIP_TRY(h, d_ref.reserve((size_t)n_ref * 16));
+    HIP_TRY(h, d_out.reserve(13 * 8));
+    if (c.ndt_refine && ndt_cells(mcs) >= 2 && ndt_lds_bytes(N, h->cfg.max_beams) <= LDS_LIMIT) {
+        HIP_TRY(h, d_occ.reserve((size_t)N * (N / 32) * 4));
+        HIP_TRY(h, d_aux.reserve(5 * 8));
     }
     HIP_TRY(h, hipMemcpyAsync(h->d_tmp_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, h->stream));
-    if (n_ref) HIP_TRY(h, hipMemcpyAsync(d_ref, ref_xy, (size_t)n_ref * 16, hipMemcpyHostToDevice, h->stream));
-    launch_match_single(h->v, d_ref, n_ref, guess3, pose_range3, h->d_tmp_sel, h->d_tmp_sel + h->cfg.max_beams, n_curr, d_out,
-                        N, ds, mcs, d0, ncr, h->cfg.max_beams, lds, d_occ, d_aux, h->stream);
+    if (n_ref) HIP_TRY(h, hipMemcpyAsync(d_ref.p, ref_xy, (size_t)n_ref * 16, hipMemcpyHostToDevice, h->stream));
+    launch_match_single(h->v, d_ref.as<double>(), n_ref, guess3, pose_range3, h->d_tmp_sel, h->d_tmp_sel + h->cfg.max_beams, n_curr,
+                        d_out.as<double>(), N, ds, mcs, d0, ncr, h->cfg.max_beams, lds, d_occ.as<uint32_t>(), d_aux.as<double>(), h->stream);
     double out[13];
-    HIP_TRY(h, hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
     int rc = check_device_error(h);
-    (void)hipFree(d_ref); (void)hipFree(d_out); (void)hipFree(d_occ); (void)hipFree(d_aux);
     if (rc) return rc;
     // matchScanCustom.m:19,52-57 validity gate
     const double PI = 3.141592653589793;
@@ -769,25 +710,24 @@ int rbpf_match_inputs(rbpf_handle* h, int32_t particle, const double* guess3, do
     DevView& v = h->v;
     if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
     const size_t LL = (size_t)v.L * v.L, mask_words = LL * v.dim * v.ow, n_rows = (size_t)v.L * v.dim;
-    double *d_all = nullptr, *d_ref = nullptr, *d_curr = nullptr; int* d_counts = nullptr; uint32_t* d_mask = nullptr; int* d_rows = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d_all, (size_t)v.B * 16)); HIP_TRY(h, hipMalloc((void**)&d_curr, (size_t)v.B * 16));
-    HIP_TRY(h, hipMalloc((void**)&d_ref, std::max<size_t>(cap_ref, 1) * 16)); HIP_TRY(h, hipMalloc((void**)&d_counts, 16));
-    HIP_TRY(h, hipMalloc((void**)&d_mask, mask_words * 4)); HIP_TRY(h, hipMalloc((void**)&d_rows, n_rows * 4));
-    HIP_TRY(h, hipMemsetAsync(d_mask, 0, mask_words * 4, h->stream));
-    HIP_TRY(h, hipMemsetAsync(d_counts, 0, 16, h->stream));
+    DevTemp d_all, d_ref, d_curr, d_counts, d_mask, d_rows;
+    HIP_TRY(h, d_all.reserve((size_t)v.B * 16)); HIP_TRY(h, d_curr.reserve((size_t)v.B * 16));
+    HIP_TRY(h, d_ref.reserve((size_t)cap_ref * 16)); HIP_TRY(h, d_counts.reserve(16));
+    HIP_TRY(h, d_mask.reserve(mask_words * 4)); HIP_TRY(h, d_rows.reserve(n_rows * 4));
+    HIP_TRY(h, hipMemsetAsync(d_mask.p, 0, mask_words * 4, h->stream));
+    HIP_TRY(h, hipMemsetAsync(d_counts.p, 0, 16, h->stream));
     const int win = (int)(1.8 / h->cfg.cell_size);                 // gridmap.py:143
-    launch_match_inputs(v, particle, guess3, d_all, d_counts, d_mask, d_rows, d_ref, cap_ref, d_curr, win,
-                        h->cfg.match_max_range, h->stream);
+    launch_match_inputs(v, particle, guess3, d_all.as<double>(), d_counts.as<int>(), d_mask.as<uint32_t>(), d_rows.as<int>(),
+                        d_ref.as<double>(), cap_ref, d_curr.as<double>(), win, h->cfg.match_max_range, h->stream);
     int counts[3] = {0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(counts, d_counts, 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(counts, d_counts.p, 12, hipMemcpyDeviceToHost, h->stream));
     int rc = check_device_error(h);
     if (rc == RBPF_OK) {
         *n_curr = counts[1]; *n_ref = counts[2];
-        if (counts[1] > 0) HIP_TRY(h, hipMemcpy(curr_xy, d_curr, (size_t)counts[1] * 16, hipMemcpyDeviceToHost));
+        if (counts[1] > 0) HIP_TRY(h, hipMemcpy(curr_xy, d_curr.p, (size_t)counts[1] * 16, hipMemcpyDeviceToHost));
         int nr = std::min(counts[2], cap_ref);
-        if (nr > 0) HIP_TRY(h, hipMemcpy(ref_xy, d_ref, (size_t)nr * 16, hipMemcpyDeviceToHost));
+        if (nr > 0) HIP_TRY(h, hipMemcpy(ref_xy, d_ref.p, (size_t)nr * 16, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_all); (void)hipFree(d_curr); (void)hipFree(d_ref); (void)hipFree(d_counts); (void)hipFree(d_mask); (void)hipFree(d_rows);
     return rc;
 }
 
@@ -813,16 +753,15 @@ int rbpf_native_sincosf(rbpf_handle* h, const float* x, int32_t n, float* s, flo
     if (!h || n < 0 || (n > 0 && (!x || !s || !c))) return RBPF_EINVAL;
     ON_DEVICE(h);
     if (n == 0) return RBPF_OK;
-    float* d = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d, (size_t)n * 12));
+    DevTemp tmp;
+    HIP_TRY(h, tmp.reserve((size_t)n * 12));
+    float* d = tmp.as<float>();
     HIP_TRY(h, hipMemcpyAsync(d, x, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     launch_native_sincosf(d, n, d + n, d + 2 * (size_t)n, h->stream);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(s, d + n, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(c, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    int rc = check_device_error(h);
-    (void)hipFree(d);
-    return rc;
+    return check_device_error(h);
 }
 
 // ---- resample (main.py:46-79) -------------------------------------------------------------------------------
@@ -903,15 +842,13 @@ int rbpf_export_weights_early(rbpf_handle* h, void* d_global, int32_t n_global, 
     return RBPF_OK;
 }
 
-// queue the global ancestors of the n_global weights d_global (main.py:46-67) into d_gidx on stream s; did -> d_did
+// queue the global ancestors of the n_global weights d_global (main.py:46-67) into B_GIDX on stream s; did -> d_did
 static int queue_indices_global(rbpf_handle* h, const void* d_global, int32_t n_global, double u, int32_t* d_did, hipStream_t s) {
     if (!(u >= 0.0 && u < 1.0)) return fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
-    int rc = scratch(h, &h->d_gT, &h->d_gT_cap, (size_t)n_global);
-    if (rc) return rc;
-    rc = scratch(h, &h->d_gidx, &h->d_gidx_cap, (size_t)n_global);
-    if (rc) return rc;
-    launch_resample_indices(n_global, static_cast<const double*>(d_global), u, h->cfg.resample_spread, h->d_gT, h->d_gidx,
-                            d_did, h->v.err, s);
+    HIP_TRY(h, h->reserve(B_GT, (size_t)n_global * 4));
+    HIP_TRY(h, h->reserve(B_GIDX, (size_t)n_global * 4));
+    launch_resample_indices(n_global, static_cast<const double*>(d_global), u, h->cfg.resample_spread, h->buf[B_GT].as<int32_t>(),
+                            h->buf[B_GIDX].as<int32_t>(), d_did, h->v.err, s);
     HIP_TRY(h, hipGetLastError());
     return RBPF_OK;
 }
@@ -920,27 +857,22 @@ int rbpf_resample_indices_global_early(rbpf_handle* h, const void* d_global, int
     if (!h || !d_global || n_global < 1) return RBPF_EINVAL;
     ON_DEVICE(h);
     hipStream_t s = static_cast<hipStream_t>(aux_stream);
-    const size_t need = (size_t)n_global * 4 + 16;
-    if (need > h->h_early_bytes) {                       // pinned landing zone of the read-back
-        if (h->h_early) HIP_TRY(h, hipHostFree(h->h_early));
-        // a kernel writes it through its device address, the host reads it after ev_early, which is created WITHOUT
-        // hipEventDisableSystemFence and so releases at system scope: plain pinned memory is enough
-        HIP_TRY(h, hipHostMalloc(&h->h_early, need, hipHostMallocDefault));
-        h->h_early_bytes = need;
-    }
+    // the landing zone of the read-back: a kernel writes it through its device address, the host reads it after the
+    // staging's event, which is created WITHOUT hipEventDisableSystemFence and so releases at system scope: plain pinned
+    // memory is enough
+    Staging& land = h->stage[S_EARLY];
+    HIP_TRY(h, land.reserve((size_t)n_global * 4 + 16));
     int rc = queue_indices_global(h, d_global, n_global, u, h->d_did_early, s);
     if (rc) return rc;
-    unsigned char* dst = static_cast<unsigned char*>(h->h_early);
-    void* mapped = nullptr;
-    if (hipHostGetDevicePointer(&mapped, dst, 0) == hipSuccess && mapped) {      // one kernel writes the landing zone directly
-        launch_readback(mapped, static_cast<const double*>(d_global) + n_global, h->d_did_early, h->d_gidx, n_global, s);
+    const int32_t* d_gidx = h->buf[B_GIDX].as<int32_t>();
+    if (void* mapped = land.mapped()) {                  // one kernel writes the landing zone directly
+        launch_readback(mapped, static_cast<const double*>(d_global) + n_global, h->d_did_early, d_gidx, n_global, s);
     } else {
-        (void)hipGetLastError();
-        HIP_TRY(h, hipMemcpyAsync(dst, static_cast<const double*>(d_global) + n_global, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(dst + 8, h->d_did_early, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(dst + 16, h->d_gidx, (size_t)n_global * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(land.p, static_cast<const double*>(d_global) + n_global, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(land.p + 8, h->d_did_early, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(land.p + 16, d_gidx, (size_t)n_global * 4, hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(h, hipEventRecord(h->ev_early, s));
+    HIP_TRY(h, land.submitted(s));
     h->early_n = n_global;
     return RBPF_OK;                                      // nothing waited for: what is queued behind it keeps the GPU busy
 }
@@ -949,8 +881,8 @@ int rbpf_resample_indices_global_wait(rbpf_handle* h, int32_t* idx_out, int32_t*
     if (!h || !idx_out || !did_resample || !nan_branch_ranks) return RBPF_EINVAL;
     ON_DEVICE(h);
     if (h->early_n <= 0) return fail(h, RBPF_ESTATE, "rbpf_resample_indices_global_early has not been called");
-    HIP_TRY(h, hipEventSynchronize(h->ev_early));        // only up to the read-back, not the work queued after it
-    const unsigned char* src = static_cast<const unsigned char*>(h->h_early);
+    HIP_TRY(h, h->stage[S_EARLY].wait());                // only up to the read-back, not the work queued after it
+    const unsigned char* src = h->stage[S_EARLY].p;
     memcpy(nan_branch_ranks, src, 8);
     memcpy(did_resample, src + 8, 4);
     memcpy(idx_out, src + 16, (size_t)h->early_n * 4);
@@ -964,7 +896,7 @@ int rbpf_resample_indices_global(rbpf_handle* h, const void* d_global, int32_t n
     ON_DEVICE(h);
     int rc = queue_indices_global(h, d_global, n_global, u, h->rs.did, h->stream);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(idx_out, h->d_gidx, (size_t)n_global * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(idx_out, h->buf[B_GIDX].p, (size_t)n_global * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(did_resample, h->rs.did, 4, hipMemcpyDeviceToHost, h->stream));
     return check_device_error(h);
 }
@@ -979,40 +911,32 @@ int rbpf_apply_resample_local(rbpf_handle* h, const int32_t* new_src, const int3
         if (!ok) return fail(h, RBPF_EINVAL, "new_src must be sorted ascending with -1 entries last");
     }
     for (int j = 0; j < v.P; ++j) if (new_src[j] >= v.P) return fail(h, RBPF_EINVAL, "new_src out of range");
-    int32_t* slot = static_cast<int32_t*>(h->ring_idx.acquire());   // pinned: the caller's arrays are free on return
+    int32_t* slot = static_cast<int32_t*>(h->rings[R_IDX].acquire());   // pinned: the caller's arrays are free on return
     memcpy(slot, new_src, (size_t)v.P * 4);
     memcpy(slot + v.P, new_global_id, (size_t)v.P * 4);
     // both index vectors go over in one kernel from the pinned, device-mapped slot (nothing below reads global_id:
     // only the weight export does, after this call)
-    void* mapped = nullptr;
-    const bool by_kernel = hipHostGetDevicePointer(&mapped, slot, 0) == hipSuccess && mapped;
-    if (by_kernel) launch_ingest2(static_cast<const int32_t*>(mapped), h->rs.idx, static_cast<const int32_t*>(mapped) + v.P, v.global_id, v.P, h->stream);
-    else { (void)hipGetLastError(); HIP_TRY(h, hipMemcpyAsync(h->rs.idx, slot, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream)); }
+    const int32_t* mapped = static_cast<const int32_t*>(h->rings[R_IDX].mapped());
+    if (mapped) launch_ingest2(mapped, h->rs.idx, mapped + v.P, v.global_id, v.P, h->stream);
+    else HIP_TRY(h, hipMemcpyAsync(h->rs.idx, slot, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream));
     int rc = resample_local(h, nullptr, 0.0, 0.0);
     if (rc) return rc;
-    if (!by_kernel) HIP_TRY(h, hipMemcpyAsync(v.global_id, slot + v.P, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream));
-    h->ring_idx.submitted(h->stream);
+    if (!mapped) HIP_TRY(h, hipMemcpyAsync(v.global_id, slot + v.P, (size_t)v.P * 4, hipMemcpyHostToDevice, h->stream));
+    h->rings[R_IDX].submitted(h->stream);
     return RBPF_OK;                                     // no host synchronisation; device errors surface at the next check
 }
 
 // meta record of one particle: [0] tiles, [1] payload bytes / 16, then per lattice position (has, x0, x1, ya, yb, offset / 16)
 int32_t rbpf_pack_meta_width(rbpf_handle* h) { return h ? 2 + 6 * h->v.L * h->v.L : -1; }
 
-// job lists of the pack / unpack kernels go through one pinned buffer: the copy is asynchronous and the std::vector may
-// die on return; the event tells when the buffer may be overwritten
+// job lists of the pack / unpack kernels go through one pinned buffer (S_JOBS -> B_JOBS): the copy is asynchronous and the
+// std::vector may die on return; the staging's event tells when the buffer may be overwritten
 static int stage_jobs(rbpf_handle* h, const void* src, size_t bytes) {
-    if (h->h_jobs_used) HIP_TRY(h, hipEventSynchronize(h->ev_jobs));
-    if (bytes > h->h_jobs_bytes) {
-        if (h->h_jobs) HIP_TRY(h, hipHostFree(h->h_jobs));
-        h->h_jobs_bytes = std::max<size_t>(bytes * 2, 1 << 16);
-        HIP_TRY(h, hipHostMalloc(&h->h_jobs, h->h_jobs_bytes, hipHostMallocDefault));
-    }
-    memcpy(h->h_jobs, src, bytes);
-    int rc = scratch(h, &h->d_jobs, &h->d_jobs_cap, bytes);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_jobs, h->h_jobs, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->ev_jobs, h->stream));
-    h->h_jobs_used = true;
+    Staging& st = h->stage[S_JOBS];
+    HIP_TRY(h, st.begin(bytes));
+    memcpy(st.p, src, bytes);
+    HIP_TRY(h, h->reserve(B_JOBS, bytes));
+    HIP_TRY(h, st.upload(h->buf[B_JOBS].p, bytes, h->stream));
     return RBPF_OK;
 }
 
@@ -1064,15 +988,11 @@ int rbpf_gather_pack_meta(rbpf_handle* h, const int32_t* local_idx, int32_t n, v
     DevView& v = h->v;
     if (n > v.P) return fail(h, RBPF_EINVAL, "more departing particles than particles");
     for (int i = 0; i < n; ++i) if (local_idx[i] < 0 || local_idx[i] >= v.P) return fail(h, RBPF_EINVAL, "local index out of range");
-    int rc = scratch(h, &h->d_i32, &h->d_i32_cap, (size_t)v.P + 4);
-    if (rc) return rc;
-    int32_t* slot = static_cast<int32_t*>(h->ring_idx.acquire());          // pinned: the caller's array is free on return
-    memcpy(slot, local_idx, (size_t)n * 4);
-    void* mapped = nullptr;
-    if (hipHostGetDevicePointer(&mapped, slot, 0) == hipSuccess && mapped) launch_ingest(mapped, h->d_i32, (size_t)n * 4, h->stream);
-    else { (void)hipGetLastError(); HIP_TRY(h, hipMemcpyAsync(h->d_i32, slot, (size_t)n * 4, hipMemcpyHostToDevice, h->stream)); }
-    h->ring_idx.submitted(h->stream);
-    launch_gather_meta(v, h->d_i32, n, static_cast<int32_t*>(d_raw), h->stream);
+    HIP_TRY(h, h->reserve(B_I32, ((size_t)v.P + 4) * 4));
+    int32_t* d_idx = h->buf[B_I32].as<int32_t>();
+    memcpy(h->rings[R_IDX].acquire(), local_idx, (size_t)n * 4);           // pinned: the caller's array is free on return
+    HIP_TRY(h, h->rings[R_IDX].upload(d_idx, (size_t)n * 4, h->stream));
+    launch_gather_meta(v, d_idx, n, static_cast<int32_t*>(d_raw), h->stream);
     HIP_TRY(h, hipGetLastError());
     return RBPF_OK;
 }
@@ -1096,7 +1016,7 @@ int rbpf_pack_particles_raw(rbpf_handle* h, const int32_t* local_idx, int32_t n,
     if (off > cap_bytes) return fail(h, RBPF_ENOMEM, "pack buffer too small");
     int rc = stage_jobs(h, jobs.data(), jobs.size() * sizeof(PackJobHost));
     if (rc) return rc;
-    launch_pack(v, h->d_jobs, (int)jobs.size(), d_buf, h->stream);
+    launch_pack(v, h->buf[B_JOBS].p, (int)jobs.size(), d_buf, h->stream);
     HIP_TRY(h, hipGetLastError());
     *bytes_out = off;
     return RBPF_OK;
@@ -1123,7 +1043,7 @@ int rbpf_unpack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, c
     }
     int rc = stage_jobs(h, jobs.data(), jobs.size() * sizeof(UnpackJobHost));
     if (rc) return rc;
-    launch_unpack(v, h->rs, h->d_jobs, (int)jobs.size(), d_buf, h->stream);
+    launch_unpack(v, h->rs, h->buf[B_JOBS].p, (int)jobs.size(), d_buf, h->stream);
     HIP_TRY(h, hipGetLastError());
     return RBPF_OK;                                     // no host synchronisation; device errors surface at the next check
 }
@@ -1319,41 +1239,26 @@ int rbpf_get_odds_at(rbpf_handle* h, int32_t particle, const double* xy, int32_t
     ON_DEVICE(h);
     if (particle < 0 || particle >= h->v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
     if (n == 0) return RBPF_OK;
-    double *d_xy = nullptr, *d_v = nullptr; uint8_t* d_n = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&d_xy, (size_t)n * 16));
-    HIP_TRY(h, hipMalloc((void**)&d_v, (size_t)n * 8));
-    HIP_TRY(h, hipMalloc((void**)&d_n, (size_t)n));
-    hipMemcpyAsync(d_xy, xy, (size_t)n * 16, hipMemcpyHostToDevice, h->stream);
-    launch_get_odds(h->v, particle, d_xy, n, d_v, d_n, h->stream);
-    hipMemcpyAsync(out_vals, d_v, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
-    hipMemcpyAsync(out_none, d_n, (size_t)n, hipMemcpyDeviceToHost, h->stream);
-    int rc = check_device_error(h);
-    hipFree(d_xy); hipFree(d_v); hipFree(d_n);
-    return rc;
+    DevTemp d_xy, d_v, d_n;
+    HIP_TRY(h, d_xy.reserve((size_t)n * 16));
+    HIP_TRY(h, d_v.reserve((size_t)n * 8));
+    HIP_TRY(h, d_n.reserve((size_t)n));
+    HIP_TRY(h, hipMemcpyAsync(d_xy.p, xy, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+    launch_get_odds(h->v, particle, d_xy.as<double>(), n, d_v.as<double>(), d_n.p, h->stream);
+    HIP_TRY(h, hipMemcpyAsync(out_vals, d_v.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_none, d_n.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    return check_device_error(h);
 }
-
-}  // extern "C"
 
 // ---- map read-out (kernels_render.hip) -----------------------------------------------------------------------------------
-// grows a render buffer; the old one may still be read by queued work, so the stream drains first
-template <typename T>
-static int render_buffer(rbpf_handle* h, T** ptr, size_t* cap, size_t n) {
-    if (*cap >= n) return RBPF_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return scratch(h, ptr, cap, n);
-}
-
-extern "C" {
-
 int rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4) {
     if (!h) return RBPF_EINVAL;
     ON_DEVICE(h);
     if (!box4) return fail(h, RBPF_EINVAL, "box4 is NULL");
     if (particle < -1 || particle >= h->v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
     if (h->scan_begun) return fail(h, RBPF_ESTATE, "map read-out between rbpf_scan_update_begin and rbpf_scan_update_end");
-    int rc = render_buffer(h, &h->d_render_out, &h->d_render_out_cap, 16);
-    if (rc) return rc;
-    int32_t* d_box = reinterpret_cast<int32_t*>(h->d_render_out);
+    HIP_TRY(h, h->reserve(B_RENDER_OUT, 16));
+    int32_t* d_box = h->buf[B_RENDER_OUT].as<int32_t>();
     const int32_t init[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
     int32_t m[4];
     HIP_TRY(h, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
@@ -1434,7 +1339,7 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     const size_t lut_b = particle < 0 ? 256 * 8 : 0, w_b = particle < 0 ? (size_t)P * 8 : 0, job_b = jobs.size() * sizeof(RenderJob);
     const size_t out_b = particle >= 0 ? (size_t)ncell : (size_t)ncell * 4 * n_out;
     // a small box has too few jobs to fill the GPU: split the particle groups into G chunks along grid.y (RBPF_RENDER_SPLIT=G
-    // forces a split, a test knob); the group sums then go through d_render_part
+    // forces a split, a test knob); the group sums then go through B_RENDER_PART
     int G = 1;
     if (particle < 0 && ngroups > 1) {
         const long long waves = 4LL * (long long)jobs.size();
@@ -1442,13 +1347,11 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
         if (const char* e = getenv("RBPF_RENDER_SPLIT")) G = std::max(1, std::min(ngroups, atoi(e)));
         if ((size_t)ngroups * ncell * n_out * 8 > ((size_t)256 << 20)) G = 1;
     }
-    int rc = render_buffer(h, &h->d_render, &h->d_render_cap, lut_b + w_b + job_b);
-    if (!rc && G > 1) rc = render_buffer(h, &h->d_render_part, &h->d_render_part_cap, (size_t)ngroups * ncell * n_out);
-    if (!rc && !dev_out) rc = render_buffer(h, &h->d_render_out, &h->d_render_out_cap, out_b);
-    if (rc) return rc;
-    if (h->ev_render_used) HIP_TRY(h, hipEventSynchronize(h->ev_render));   // the last upload may still read h_render
-    h->h_render.resize(lut_b + w_b + job_b);
-    unsigned char* st = h->h_render.data();
+    HIP_TRY(h, h->reserve(B_RENDER, lut_b + w_b + job_b));
+    if (G > 1) HIP_TRY(h, h->reserve(B_RENDER_PART, (size_t)ngroups * ncell * n_out * 8));
+    if (!dev_out) HIP_TRY(h, h->reserve(B_RENDER_OUT, out_b));
+    HIP_TRY(h, h->stage[S_RENDER].begin(lut_b + w_b + job_b));              // the last upload may still read it
+    unsigned char* st = h->stage[S_RENDER].p;
     if (particle < 0) {
         double* lut = reinterpret_cast<double*>(st);
         for (int k = 0; k < 256; ++k) {                 // get_pr_at, hybridmap.py:74-83
@@ -1459,27 +1362,26 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
         for (int p = 0; p < P; ++p) w[p] = weights ? weights[p] : 1.0;
     }
     memcpy(st + lut_b + w_b, jobs.data(), job_b);
-    if (!h->ev_render) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_render, hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpyAsync(h->d_render, st, lut_b + w_b + job_b, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->ev_render, h->stream));
-    h->ev_render_used = true;
-    const RenderJob* d_jobs = reinterpret_cast<const RenderJob*>(h->d_render + lut_b + w_b);
+    const Block& d_in = h->buf[B_RENDER];
+    HIP_TRY(h, h->stage[S_RENDER].upload(d_in.p, lut_b + w_b + job_b, h->stream));
+    const RenderJob* d_jobs = d_in.as<const RenderJob>(lut_b + w_b);
     if (particle >= 0) {
-        int8_t* out = dev_out ? cells : reinterpret_cast<int8_t*>(h->d_render_out);
+        int8_t* out = dev_out ? cells : h->buf[B_RENDER_OUT].as<int8_t>();
         launch_render_cells(v, particle, d_jobs, (int)jobs.size(), ny, out, h->stream);
         HIP_TRY(h, hipGetLastError());
         if (!dev_out) HIP_TRY(h, hipMemcpyAsync(cells, out, (size_t)ncell, hipMemcpyDeviceToHost, h->stream));
     } else {
         RenderFilter f;
         f.jobs = d_jobs;
-        f.lut = reinterpret_cast<const double*>(h->d_render);
+        f.lut = d_in.as<const double>();
         f.w = f.lut + 256;
         f.S = S; f.C = C; f.ngroups = ngroups; f.ny = ny; f.ncell = (size_t)ncell;
-        float* o = reinterpret_cast<float*>(h->d_render_out);
+        float* o = h->buf[B_RENDER_OUT].as<float>();
+        double* part = h->buf[B_RENDER_PART].as<double>();
         f.prob = !prob ? nullptr : dev_out ? prob : o;
         f.occ = !occ_frac ? nullptr : dev_out ? occ_frac : o + (prob ? ncell : 0);
-        f.part_p = prob ? h->d_render_part : nullptr;
-        f.part_o = occ_frac ? h->d_render_part + (prob ? (size_t)ngroups * ncell : 0) : nullptr;
+        f.part_p = prob ? part : nullptr;
+        f.part_o = occ_frac ? part + (prob ? (size_t)ngroups * ncell : 0) : nullptr;
         launch_render_filter(v, f, (int)jobs.size(), G, h->stream);
         HIP_TRY(h, hipGetLastError());
         if (!dev_out && prob) HIP_TRY(h, hipMemcpyAsync(prob, f.prob, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1543,18 +1445,20 @@ int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const i
     // device staging: [flag, padded to 16] [tiles] [jobs] [the raster, host input only]
     const size_t tiles_b = (tiles.size() * sizeof(LoadTile) + 15) & ~(size_t)15, jobs_b = jobs.size() * sizeof(RenderJob);
     const size_t meta_b = 16 + tiles_b + ((jobs_b + 15) & ~(size_t)15);
-    int rc = render_buffer(h, &h->d_load, &h->d_load_cap, meta_b + (dev_in ? 0 : (size_t)ncell));
-    if (rc) return rc;
-    std::vector<unsigned char> st(meta_b, 0);
-    memcpy(st.data() + 16, tiles.data(), tiles.size() * sizeof(LoadTile));
-    memcpy(st.data() + 16 + tiles_b, jobs.data(), jobs_b);
-    HIP_TRY(h, hipMemcpyAsync(h->d_load, st.data(), meta_b, hipMemcpyHostToDevice, h->stream));
-    if (!dev_in) HIP_TRY(h, hipMemcpyAsync(h->d_load + meta_b, cells, (size_t)ncell, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, h->reserve(B_LOAD, meta_b + (dev_in ? 0 : (size_t)ncell)));
+    const Block& d_load = h->buf[B_LOAD];
+    Staging& st = h->stage[S_LOAD];
+    HIP_TRY(h, st.begin(meta_b));
+    memset(st.p, 0, meta_b);
+    memcpy(st.p + 16, tiles.data(), tiles.size() * sizeof(LoadTile));
+    memcpy(st.p + 16 + tiles_b, jobs.data(), jobs_b);
+    HIP_TRY(h, st.upload(d_load.p, meta_b, h->stream));
+    if (!dev_in) HIP_TRY(h, hipMemcpyAsync(d_load.p + meta_b, cells, (size_t)ncell, hipMemcpyHostToDevice, h->stream));
     LoadArgs a;
-    a.bad = reinterpret_cast<int32_t*>(h->d_load);
-    a.tiles = reinterpret_cast<const LoadTile*>(h->d_load + 16); a.n_tiles = (int)tiles.size();
-    a.jobs = reinterpret_cast<const RenderJob*>(h->d_load + 16 + tiles_b);
-    a.cells = dev_in ? cells : reinterpret_cast<const int8_t*>(h->d_load + meta_b);
+    a.bad = d_load.as<int32_t>();
+    a.tiles = d_load.as<const LoadTile>(16); a.n_tiles = (int)tiles.size();
+    a.jobs = d_load.as<const RenderJob>(16 + tiles_b);
+    a.cells = dev_in ? cells : d_load.as<const int8_t>(meta_b);
     a.ny = ny; a.ncell = ncell; a.p_lo = p_lo; a.p_hi = p_hi;
     if (dev_in) launch_load_validate(v, a, h->stream);
     launch_load_map(v, a, (int)jobs.size(), h->stream);
@@ -1588,29 +1492,25 @@ int rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, in
     const bool dev_out = (flags & RBPF_CAST_DEVICE_OUT) != 0;
     const size_t rays = (size_t)n_poses * n_beams;
     const size_t in_b = (size_t)n_poses * 32 + (size_t)n_beams * 16, out_b = dev_out ? 0 : rays * 8 + (status ? rays : 0);
-    int rc = render_buffer(h, &h->d_cast, &h->d_cast_cap, in_b + out_b);
-    if (rc) return rc;
-    if (h->ev_cast_used) HIP_TRY(h, hipEventSynchronize(h->ev_cast));     // the last upload may still read h_cast
-    h->h_cast.resize(in_b);
-    double* st = reinterpret_cast<double*>(h->h_cast.data());
+    HIP_TRY(h, h->reserve(B_CAST, in_b + out_b));
+    const Block& d_cast = h->buf[B_CAST];
+    HIP_TRY(h, h->stage[S_CAST].begin(in_b));                              // the last upload may still read it
+    double* st = reinterpret_cast<double*>(h->stage[S_CAST].p);
     for (int n = 0; n < n_poses; ++n) {                                    // host libm, as rbpf_set_scan
         st[4 * (size_t)n] = poses_n3[3 * (size_t)n]; st[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
         st[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); st[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
     }
     double* sb = st + 4 * (size_t)n_poses;
     for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
-    if (!h->ev_cast) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_cast, hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpyAsync(h->d_cast, st, in_b, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(h->ev_cast, h->stream));
-    h->ev_cast_used = true;
+    HIP_TRY(h, h->stage[S_CAST].upload(d_cast.p, in_b, h->stream));
     CastArgs a;
-    a.pose4 = reinterpret_cast<const double*>(h->d_cast);
+    a.pose4 = d_cast.as<const double>();
     a.beam2 = a.pose4 + 4 * (size_t)n_poses;
     a.n_poses = n_poses; a.B = n_beams; a.particle = particle;
     a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as lookup_cell_fast forms it
     a.tlim = max_range * a.inv; a.max_range = max_range;
-    a.ranges = dev_out ? ranges : reinterpret_cast<double*>(h->d_cast + in_b);
-    a.status = !status ? nullptr : dev_out ? status : h->d_cast + in_b + rays * 8;
+    a.ranges = dev_out ? ranges : d_cast.as<double>(in_b);
+    a.status = !status ? nullptr : dev_out ? status : d_cast.p + in_b + rays * 8;
     launch_cast_scans(v, a, h->stream);
     HIP_TRY(h, hipGetLastError());
     if (dev_out) return RBPF_OK;

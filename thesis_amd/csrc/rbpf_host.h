@@ -1,0 +1,167 @@
+// rbpf_host.h -- host side of librbpf_hip.so (rbpf_api.hip only): the types that own memory and events, and the handle
+// built from them.  An entry point never allocates, frees or creates an event itself: it asks one of these types, and
+// rbpf_destroy releases each kind in one loop.
+#pragma once
+#include <stdlib.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "rbpf_internal.h"
+
+static const size_t LDS_LIMIT = 160 * 1024;    // LDS of one gfx950 workgroup
+
+// Grow-only memory of one kind.  Contents are not kept when it grows; a failed growth leaves {nullptr, 0}.
+enum MemKind { MEM_DEVICE, MEM_PINNED, MEM_PAGEABLE };
+struct Block {
+    MemKind kind = MEM_DEVICE;
+    unsigned char* p = nullptr; size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (p && cap >= bytes) return hipSuccess;
+        release();
+        const size_t want = kind == MEM_PINNED ? std::max<size_t>(bytes * 2, 1 << 16) : std::max<size_t>(bytes, 4096);   // pinning is slow: grow rarely
+        hipError_t e = hipSuccess;
+        if (kind == MEM_DEVICE) e = hipMalloc(reinterpret_cast<void**>(&p), want);
+        else if (kind == MEM_PINNED) e = hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault);
+        else if (!(p = static_cast<unsigned char*>(malloc(want)))) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) cap = want; else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (kind == MEM_DEVICE) (void)hipFree(p); else if (kind == MEM_PINNED) (void)hipHostFree(p); else free(p);
+        p = nullptr; cap = 0;
+    }
+    template <typename T> T* as(size_t byte_offset = 0) const { return reinterpret_cast<T*>(p + byte_offset); }
+};
+// the handle's device scratch: samples of rbpf_weight_samples; table and ancestors of the global resample; departing particles
+// and job list of a migration; LUT, weights and jobs of the last render, the group sums of a split render, the outputs of a
+// render to host memory; flag, touched tiles, jobs and host raster of a map load; poses, beams and host outputs of a cast
+enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_COUNT };
+
+// A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
+// early error return cannot pull memory from under queued work.
+struct DevTemp : Block { DevTemp() = default; DevTemp(const DevTemp&) = delete; ~DevTemp() { release(); } };
+
+// Host memory that work queued on a stream reads (an upload) or writes (the early read-back), guarded by an event created
+// with it: begin() before the host touches it again, submitted() once that work is queued.
+struct Staging : Block {
+    unsigned ev_flags = hipEventDisableTiming | hipEventDisableSystemFence;     // guards host memory a copy only reads
+    hipEvent_t ev = nullptr; bool used = false;
+    hipError_t wait() { return used ? hipEventSynchronize(ev) : hipSuccess; }
+    hipError_t reserve(size_t bytes) {
+        if (!ev) { const hipError_t e = hipEventCreateWithFlags(&ev, ev_flags); if (e != hipSuccess) { ev = nullptr; return e; } }
+        return Block::reserve(bytes);
+    }
+    hipError_t begin(size_t bytes) { const hipError_t e = wait(); return e != hipSuccess ? e : reserve(bytes); }
+    hipError_t submitted(hipStream_t s) { const hipError_t e = hipEventRecord(ev, s); if (e == hipSuccess) used = true; return e; }
+    hipError_t upload(void* dst, size_t bytes, hipStream_t s) {
+        const hipError_t e = hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
+        return e != hipSuccess ? e : submitted(s);
+    }
+    // the device address of pinned memory when the runtime maps it (a kernel then reads or writes it directly), else nullptr
+    void* mapped() const {
+        void* m = nullptr;
+        if (hipHostGetDevicePointer(&m, p, 0) != hipSuccess) { (void)hipGetLastError(); m = nullptr; }
+        return m;
+    }
+    void destroy_event() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; }
+};
+// job lists of the pack / unpack kernels and the landing zone of the early resample read-back (pinned); the blocks uploaded
+// into B_RENDER, B_CAST and B_LOAD (pageable)
+enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_COUNT };
+
+// Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
+// copy that read it has completed (its event), so uploading never drains the stream.
+struct PinnedRing {
+    static const int N = 4;
+    Staging slot[N] = {{{MEM_PINNED}}, {{MEM_PINNED}}, {{MEM_PINNED}}, {{MEM_PINNED}}}; int next = 0;
+    hipError_t create(size_t slot_bytes) {
+        for (Staging& s : slot) { const hipError_t e = s.reserve(slot_bytes); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    void* acquire() { (void)slot[next].wait(); return slot[next].p; }
+    void* mapped() const { return slot[next].mapped(); }
+    void submitted(hipStream_t s) { (void)slot[next].submitted(s); next = (next + 1) % N; }
+    // the first `bytes` of the acquired slot -> dst.  Pinned and device-mapped: a kernel pulls them over (no copy-engine latency
+    // in the stream); DMA otherwise
+    hipError_t upload(void* dst, size_t bytes, hipStream_t s) {
+        if (void* m = mapped()) rbpf::launch_ingest(m, dst, bytes, s);
+        else { const hipError_t e = hipMemcpyAsync(dst, slot[next].p, bytes, hipMemcpyHostToDevice, s); if (e != hipSuccess) return e; }
+        submitted(s);
+        return hipSuccess;
+    }
+};
+enum { R_SCAN, R_LAST, R_IDX, R_COUNT };
+
+// events that live as long as the handle (timing rings, ev_weights)
+struct EventPool {
+    std::vector<hipEvent_t> all;
+    hipError_t create(hipEvent_t* out, unsigned flags) {
+        const hipError_t e = hipEventCreateWithFlags(out, flags);
+        if (e == hipSuccess) all.push_back(*out); else *out = nullptr;
+        return e;
+    }
+    void destroy() { for (hipEvent_t ev : all) (void)hipEventDestroy(ev); all.clear(); }
+};
+
+struct rbpf_handle {
+    rbpf_config cfg;
+    rbpf::DevView v;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    bool profiling = false;
+    unsigned prof_mask = 0;                     // kernel families whose launches are bracketed by timing events (bit k = family k)
+    bool have_scan = false;
+    bool dedup_enabled = true;                  // exact duplicates share one matcher run (RBPF_MATCH_DEDUP=0 turns it off)
+    std::string err;
+    std::vector<uint32_t> h_lut;
+    std::vector<Block> allocs;                  // dev_alloc: device memory that lives as long as the handle
+    Block buf[B_COUNT];
+    Staging stage[S_COUNT] = {{{MEM_PINNED}}, {{MEM_PINNED}, hipEventDisableTiming},   // the host reads S_EARLY after its event: system-scope release
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
+    // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
+    hipError_t reserve(int b, size_t bytes) {
+        if (buf[b].cap >= bytes) return hipSuccess;
+        if (b >= B_DRAIN_FIRST) { const hipError_t e = hipStreamSynchronize(stream); if (e != hipSuccess) return e; }
+        return buf[b].reserve(bytes);
+    }
+    PinnedRing rings[R_COUNT];
+    EventPool events;
+    template <typename F> void each_staging(F f) { for (Staging& s : stage) f(s); for (PinnedRing& r : rings) for (Staging& s : r.slot) f(s); }
+    hipEvent_t ev_weights = nullptr; bool ev_weights_valid = false, record_ev_weights = false, begin_seen = false;   // recorded after the weighting kernel of rbpf_scan_update_begin
+    int32_t* d_did_early = nullptr; bool scan_begun = false;
+    int early_n = 0;                            // entries of the early resample read-back in flight (S_EARLY), 0 = none
+    unsigned char* d_scan = nullptr; size_t scan_bytes = 0;   // device scan block (rbpf_create points the DevView's scan arrays into it)
+    // a slot of rings[R_SCAN] is laid out as the device scan block: the slot's copy of one of the DevView's scan arrays
+    template <typename T> T* in_slot(unsigned char* slot, const T* dev) const { return reinterpret_cast<T*>(slot + (reinterpret_cast<const unsigned char*>(dev) - d_scan)); }
+    int mN = 0, mds = 1, mncr = 0; double mmcs = 0, md0 = 0; size_t mlds = 0;
+    double* d_last_xy = nullptr; float* d_tmp_sel = nullptr;
+    int n_last_dev = -1;                       // points of the device-resident previous scan (rbpf_refresh_last_scan), -1 = none
+    int match_rows = 0;                        // d_match: 0 not written by the built-in matcher, 1 its rows, 2 its rows with duplicates skipped (dup_of)
+    double* d_match = nullptr; uint8_t* d_bad = nullptr; double* d_guess_full = nullptr;
+    unsigned long long resample_draws = 0;
+    bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
+    // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
+    static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
+    std::vector<hipEvent_t> ring[N_KERN][2];
+    int ring_n[N_KERN] = {0, 0, 0, 0, 0};
+    std::vector<hipEvent_t> begin_used[N_KERN];     // the event that marks a launch's start: its own, or the previous family's end
+    hipEvent_t last_end = nullptr;
+    bool timed(int k) const { return (prof_mask >> k) & 1u; }
+    void prof_begin(int k) { if (!timed(k)) return; hipEvent_t e = ring[k][0][ring_n[k] % RING]; (void)hipEventRecord(e, stream); begin_used[k][ring_n[k] % RING] = e; }
+    // the previous timed family ended right before this one starts (nothing enqueued in between): one record serves both
+    void prof_begin_chained(int k) { if (!timed(k)) return; if (!last_end) { prof_begin(k); return; } begin_used[k][ring_n[k] % RING] = last_end; }
+    void prof_end(int k) { if (!timed(k)) return; last_end = ring[k][1][ring_n[k] % RING]; (void)hipEventRecord(last_end, stream); ring_n[k]++; }
+    // a family that is one kernel: its timing events ride on the dispatch and take the kernel's own start and end (no event
+    // records in the stream).  False, and both null, if the family is not timed.
+    bool prof_take(int k, hipEvent_t& t0, hipEvent_t& t1) {
+        t0 = t1 = nullptr;
+        if (!timed(k)) return false;
+        const int slot = ring_n[k] % RING;
+        t0 = ring[k][0][slot]; t1 = ring[k][1][slot]; begin_used[k][slot] = t0; last_end = nullptr; ring_n[k]++;
+        return true;
+    }
+    rbpf::ResampleBuffers rs;
+    rbpf_counters counters;
+    unsigned long long scan_updates = 0;
+};

@@ -1,10 +1,8 @@
-// rbpf_internal.h -- handle layout and kernel-launch prototypes of librbpf_hip.so (gfx950 only).
+// rbpf_internal.h -- what the kernels and their launchers share in librbpf_hip.so (gfx950 only); the handle: rbpf_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
-#include <string>
-#include <vector>
 
 #include "../../include/rbpf_hip.h"
 #include "rbpf_math.h"
@@ -147,70 +145,6 @@ struct CastArgs {
     double* ranges; uint8_t* status;   // [n_poses][B]; status may be null
 };
 
-}  // namespace rbpf
-
-struct rbpf_handle {
-    rbpf_config cfg;
-    rbpf::DevView v;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    bool profiling = false;
-    unsigned prof_mask = 0;                     // kernel families whose launches are bracketed by timing events (bit k = family k)
-    bool have_scan = false;
-    bool dedup_enabled = true;                  // exact duplicates share one matcher run (RBPF_MATCH_DEDUP=0 turns it off)
-    std::string err;
-    std::vector<uint32_t> h_lut;
-    std::vector<void*> allocs;
-    // host staging
-    // pinned staging rings for the per-step uploads (scan block, previous scan): a slot is reused only after the copy
-    // that read it has completed (its event), so uploading never drains the stream
-    struct PinnedRing {
-        static const int N = 4;
-        unsigned char* base = nullptr; size_t slot_bytes = 0; int next = 0; hipEvent_t ev[N] = {}; bool used[N] = {};
-        void* acquire() { if (used[next]) (void)hipEventSynchronize(ev[next]); return base + (size_t)next * slot_bytes; }
-        void submitted(hipStream_t s) { (void)hipEventRecord(ev[next], s); used[next] = true; next = (next + 1) % N; }
-    };
-    PinnedRing ring_scan, ring_last, ring_idx;
-    hipEvent_t ev_weights = nullptr; bool ev_weights_valid = false, record_ev_weights = false, begin_seen = false;   // recorded after the weighting kernel of rbpf_scan_update_begin
-    int32_t* d_did_early = nullptr; bool scan_begun = false;
-    void* h_jobs = nullptr; size_t h_jobs_bytes = 0; hipEvent_t ev_jobs = nullptr; bool h_jobs_used = false;   // pinned job-list staging
-    hipEvent_t ev_early = nullptr; void* h_early = nullptr; size_t h_early_bytes = 0; int early_n = 0;   // early resample read-back
-    unsigned char* d_scan = nullptr; size_t scan_bytes = 0;   // device scan block, same layout as a ring_scan slot
-    // scratch device buffers for test entries
-    double* d_guess = nullptr; double* d_prs = nullptr; double* d_w = nullptr; size_t d_guess_n = 0;
-    int mN = 0, mds = 1, mncr = 0; double mmcs = 0, md0 = 0; size_t mlds = 0;
-    double* d_last_xy = nullptr; float* d_tmp_sel = nullptr;
-    int n_last_dev = -1;                       // points of the device-resident previous scan (rbpf_refresh_last_scan), -1 = none
-    int match_rows = 0;                        // d_match: 0 not written by the built-in matcher, 1 its rows, 2 its rows with duplicates skipped (dup_of)
-    double* d_match = nullptr; uint8_t* d_bad = nullptr; double* d_guess_full = nullptr;
-    unsigned long long resample_draws = 0;
-    int32_t* d_gT = nullptr; size_t d_gT_cap = 0; int32_t* d_gidx = nullptr; size_t d_gidx_cap = 0;
-    int32_t* d_i32 = nullptr; size_t d_i32_cap = 0; unsigned char* d_jobs = nullptr; size_t d_jobs_cap = 0;
-    // map rendering: LUT, weights and jobs of the last render (staged through h_render, reusable once ev_render completed),
-    // the group sums of a split render, the outputs of a render to host memory
-    unsigned char* d_render = nullptr; size_t d_render_cap = 0; double* d_render_part = nullptr; size_t d_render_part_cap = 0;
-    unsigned char* d_render_out = nullptr; size_t d_render_out_cap = 0;
-    std::vector<unsigned char> h_render; hipEvent_t ev_render = nullptr; bool ev_render_used = false;
-    unsigned char* d_load = nullptr; size_t d_load_cap = 0;   // map loading: flag, touched tiles, jobs, host raster
-    // scan casting: poses, beams and (for host outputs) ranges and status; staged through h_cast, reusable once ev_cast completed
-    unsigned char* d_cast = nullptr; size_t d_cast_cap = 0; std::vector<unsigned char> h_cast; hipEvent_t ev_cast = nullptr; bool ev_cast_used = false;
-    bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
-    // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
-    static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
-    std::vector<hipEvent_t> ring[N_KERN][2];
-    int ring_n[N_KERN] = {0, 0, 0, 0, 0};
-    std::vector<hipEvent_t> begin_used[N_KERN];     // the event that marks a launch's start: its own, or the previous family's end
-    hipEvent_t last_end = nullptr;
-    void prof_begin(int k) { if (!((prof_mask >> k) & 1u)) return; hipEvent_t e = ring[k][0][ring_n[k] % RING]; (void)hipEventRecord(e, stream); begin_used[k][ring_n[k] % RING] = e; }
-    // the previous timed family ended right before this one starts (nothing enqueued in between): one record serves both
-    void prof_begin_chained(int k) { if (!((prof_mask >> k) & 1u)) return; if (!last_end) { prof_begin(k); return; } begin_used[k][ring_n[k] % RING] = last_end; }
-    void prof_end(int k) { if (!((prof_mask >> k) & 1u)) return; last_end = ring[k][1][ring_n[k] % RING]; (void)hipEventRecord(last_end, stream); ring_n[k]++; }
-    rbpf::ResampleBuffers rs;
-    rbpf_counters counters;
-    unsigned long long scan_updates = 0;
-};
-
-namespace rbpf {
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
                            double* d_out_w, hipStream_t s);
