@@ -340,6 +340,29 @@ int  rbpf_get_map_updates(rbpf_handle* h, int32_t* on);
 int  rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* angles,
                      int32_t n_beams, double max_range, uint32_t flags, double* ranges, uint8_t* status);
 
+/* ---- global localization: where in a particle's map does this scan fit? -------------------------------------------------
+ * Scores the scan at every candidate pose (X, Y, r) of the box box4 = {x0, x1, y0, y1} (mosaic cells, half-open, the layout of
+ * rbpf_render_map) in the map of `particle` (>= 0), the robot standing at the centre of cell (X, Y) with heading theta_r.
+ * With v(X, Y) the lattice value rbpf_render_map gives (0 without a tile, outside a tile's written box, outside the lattice):
+ *   occ(X, Y)  = v * quantum > occupied_threshold            dil(X, Y) = OR of occ over the 3 x 3 cells round (X, Y)
+ *   F(X, Y)    = occ + dil  in {0, 1, 2}                     cand(X, Y) = v < 0   (observed free)
+ * Beam b is used iff match_min_range < ranges[b] < match_max_range (n_used of them); bx = ranges[b] cos(angles[b]),
+ * by = ranges[b] sin(angles[b]) (host libm, as rbpf_set_scan).  theta_r = (r * 6.283185307179586) / n_rot, r = 0 .. n_rot-1,
+ * c_r = cos(theta_r), s_r = sin(theta_r) (host libm).  In float64, every operation rounded on its own, inv = dim / tile_len:
+ *   u[r,b] = floor(0.5 + (c_r bx - s_r by) inv)              w[r,b] = floor(0.5 + (s_r bx + c_r by) inv)
+ *   score(X, Y, r) = sum over used b of F(X + u[r,b], Y + w[r,b])        (end points anywhere in the map, not only in the box)
+ *   best[X-x0][Y-y0] = max_r score(X, Y, r)      rot[X-x0][Y-y0] = the smallest r that attains it       where cand(X, Y),
+ *   both -1 elsewhere.  best <= 2 n_used; with no used beam best = rot = 0 on candidates.  rot may be NULL.
+ * Independent of rbpf_set_scan: 1 <= n_beams <= 16384, 1 <= n_rot <= 4096.  The box must lie in the tile lattice and hold
+ * fewer than 2^31 cells.  A NULL box4, ranges, angles or best, a non-finite range or angle, a bad particle, n_beams, n_rot or
+ * box, or an unknown flag is RBPF_EINVAL; a call between rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked
+ * before anything is queued, and nothing is written.  A box whose scratch would pass 2 GiB is RBPF_ENOMEM.  The call changes
+ * no engine state (maps, particles, random streams, counters, duplicate grouping).  It runs on the handle's stream; without
+ * RBPF_LOCATE_DEVICE_OUT the outputs are host arrays, complete on return. */
+#define RBPF_LOCATE_DEVICE_OUT 1u  /* best / rot are device pointers, written in stream order, no host wait */
+int  rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* ranges, const double* angles,
+                      int32_t n_beams, int32_t n_rot, uint32_t flags, int32_t* best, int32_t* rot);
+
 #ifdef __cplusplus
 }
 #endif

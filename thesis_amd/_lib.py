@@ -16,6 +16,7 @@ RBPF_EINVAL, RBPF_ENOMEM, RBPF_EDEVICE, RBPF_ESTATE, RBPF_ERANGE = -1, -2, -3, -
 RBPF_RENDER_DEVICE_OUT = 1
 RBPF_LOAD_DEVICE_IN = 1
 RBPF_CAST_DEVICE_OUT = 1
+RBPF_LOCATE_DEVICE_OUT = 1
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
 
 
@@ -113,6 +114,7 @@ PROTOTYPES = {
     "rbpf_set_map_updates": (C.c_int, [_H, C.c_int32]),
     "rbpf_get_map_updates": (C.c_int, [_H, _I]),
     "rbpf_cast_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rbpf_locate_scan": (C.c_int, [_H, C.c_int32, _I, _D, _D, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1520,4 +1520,82 @@ int rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, in
     return RBPF_OK;
 }
 
+// ---- global localization (kernels_locate.hip) -------------------------------------------------------------------------------
+int rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* ranges, const double* angles,
+                     int32_t n_beams, int32_t n_rot, uint32_t flags, int32_t* best, int32_t* rot) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4 || !ranges || !angles || !best) return fail(h, RBPF_EINVAL, "box4, ranges, angles or best is NULL");
+    if (flags & ~RBPF_LOCATE_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (n_beams < 1 || n_beams > 16384) return fail(h, RBPF_EINVAL, "1 <= n_beams <= 16384 is required");
+    if (n_rot < 1 || n_rot > 4096) return fail(h, RBPF_EINVAL, "1 <= n_rot <= 4096 is required");
+    if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
+    if (ncell >= (1LL << 31)) return fail(h, RBPF_EINVAL, "box must hold fewer than 2^31 cells");
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    if (ncell > 0 && (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge))
+        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(ranges[b]) || !std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "ranges and angles must be finite");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "scan search between rbpf_scan_update_begin and rbpf_scan_update_end");
+    if (ncell == 0) return RBPF_OK;
+    const rbpf_config& c = h->cfg;
+    LocateArgs a;
+    a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as lookup_cell_fast forms it
+    const double reach = ceil(c.match_max_range * a.inv) + 1.0;            // no used beam ends farther from its candidate cell
+    if (!(reach >= 1.0) || reach > 32767.0) return fail(h, RBPF_EINVAL, "match_max_range is more than 32766 cells");
+    int nb = 0;
+    for (int b = 0; b < n_beams; ++b) nb += ranges[b] > c.match_min_range && ranges[b] < c.match_max_range;   // BF_MATCH, hybridmap.py:218
+    a.particle = particle; a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
+    a.nyw = (int)((ny + 31) / 32); a.M = (int)reach;
+    a.rows = a.nx + 2 * a.M; a.W = a.nyw + ((2 * a.M) >> 5) + 2;
+    a.n_rot = n_rot; a.nb = nb;
+    // enough workgroups to fill the GPU: the rotations are cut into runs when the box has few candidate words
+    const long long words = nx * a.nyw, word_waves = (words + 63) / 64;
+    const long long runs = std::max(1LL, std::min<long long>(n_rot, (8192 + word_waves - 1) / word_waves));
+    a.rpw = (int)((n_rot + runs - 1) / runs);
+    const bool dev_out = (flags & RBPF_LOCATE_DEVICE_OUT) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t in_b = ((size_t)n_rot + nb) * 16, offs_b = pad((size_t)n_rot * nb * 4), field_b = pad((size_t)a.rows * a.W * 8);
+    const size_t cand_b = pad((size_t)words * 4), packed_b = pad((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 4 * (rot ? 2 : 1);
+    const size_t total = pad(in_b) + offs_b + field_b + 2 * cand_b + 256 + packed_b + out_b;
+    if (total > ((size_t)2 << 30)) return fail(h, RBPF_ENOMEM, "box, beams and rotations need more than 2 GiB of scratch: search a smaller box");
+    HIP_TRY(h, h->reserve(B_LOCATE, total));
+    const Block& d = h->buf[B_LOCATE];
+    HIP_TRY(h, h->stage[S_LOCATE].begin(in_b));                            // the last upload may still read it
+    double* st = reinterpret_cast<double*>(h->stage[S_LOCATE].p);
+    for (int r = 0; r < n_rot; ++r) {                                      // host libm: the device never sees an angle
+        const double th = ((double)r * 6.283185307179586) / (double)n_rot;
+        st[2 * r] = cos(th); st[2 * r + 1] = sin(th);
+    }
+    double* sb = st + 2 * (size_t)n_rot;
+    for (int b = 0, k = 0; b < n_beams; ++b)
+        if (ranges[b] > c.match_min_range && ranges[b] < c.match_max_range) {
+            sb[2 * k] = ranges[b] * cos(angles[b]); sb[2 * k + 1] = ranges[b] * sin(angles[b]);   // as rbpf_set_scan forms them
+            ++k;
+        }
+    HIP_TRY(h, h->stage[S_LOCATE].upload(d.p, in_b, h->stream));
+    size_t at = pad(in_b);
+    a.cs = d.as<const double>(); a.bxy = a.cs + 2 * (size_t)n_rot;
+    a.offs = d.as<int32_t>(at); at += offs_b;
+    a.field = d.as<uint2>(at); at += field_b;
+    a.cand = d.as<uint32_t>(at); at += cand_b;
+    a.items = d.as<int32_t>(at); at += cand_b;
+    a.n_items = d.as<int32_t>(at); at += 256;
+    a.packed = d.as<uint32_t>(at);
+    HIP_TRY(h, hipMemsetAsync(a.n_items, 0, 256 + packed_b, h->stream));   // the item count and the merge raster behind it
+    at += packed_b;
+    a.best = dev_out ? best : d.as<int32_t>(at);
+    a.rot = !rot ? nullptr : dev_out ? rot : d.as<int32_t>(at + (size_t)ncell * 4);
+    launch_locate_scan(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(best, a.best, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    if (rot) HIP_TRY(h, hipMemcpyAsync(rot, a.rot, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

@@ -144,6 +144,24 @@ struct CastArgs {
     double inv, tlim, max_range;       // cells per metre (dim / tile_len), max_range * inv, max_range
     double* ranges; uint8_t* status;   // [n_poses][B]; status may be null
 };
+// global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
+struct LocateArgs {
+    int particle;
+    int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
+    int nyw;                           // candidate words per box row = ceil(ny / 32)
+    int M;                             // largest beam offset in cells: the field is the box grown by M on every side
+    int rows, W;                       // field rows (nx + 2 M) and {occ, dil} word pairs per field row (nyw + (2 M >> 5) + 2)
+    int n_rot, nb, rpw;                // rotations, used beams, rotations per workgroup
+    double inv;                        // cells per metre (dim / tile_len)
+    const double* cs;                  // [n_rot][2] cos, sin of theta_r (host libm)
+    const double* bxy;                 // [nb][2] end points of the used beams, sensor frame, metres (host libm)
+    int32_t* offs;                     // [n_rot][nb] u << 16 | (M + w): offset in rows, and in bits of a field row
+    uint2* field;                      // [rows][W]
+    uint32_t* cand;                    // [nx][nyw] bit Y & 31: the cell is a candidate
+    int32_t* items; int32_t* n_items;  // the words of cand that are not 0, in any order; their number
+    uint32_t* packed;                  // [nx][ny] max over rotations of score << 16 | (n_rot - 1 - r), preset to 0
+    int32_t *best, *rot;               // [nx][ny] outputs; rot may be null
+};
 
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
@@ -200,4 +218,5 @@ void launch_render_filter(const DevView& v, const RenderFilter& f, int n_jobs, i
 void launch_load_validate(const DevView& v, const LoadArgs& a, hipStream_t s);
 void launch_load_map(const DevView& v, const LoadArgs& a, int n_jobs, hipStream_t s);   // tile allocation, then the cells
 void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
+void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 }  // namespace rbpf

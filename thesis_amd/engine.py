@@ -504,6 +504,64 @@ class ParticleEngine:
             self.synchronize()
         return (r, st) if return_status else r
 
+    # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
+    def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):
+        """Scores the scan (`ranges` [B], `angles` [B], sensor frame) at every observed-free cell and each of `n_rot`
+        headings of `box` = (x0, x1, y0, y1) in mosaic cells (default map_extent(particle)) in a particle's map:
+        `particle` an index or "best" (the first argmax of weights()).  Returns (best, rot, box): int32 [x1-x0, y1-y0]
+        rasters of the best score per cell and the smallest rotation index that attains it, -1 where no robot can stand
+        (locate.hypotheses turns them into poses).  device=True: torch tensors on the engine's device, ready
+        for work on torch's current stream."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = int(particle)
+        r, a = _f64(ranges), _f64(angles)
+        if r.ndim != 1 or a.shape != r.shape:
+            raise ValueError("ranges and angles must be 1-D and of equal length")
+        if box is None:
+            box = self.map_extent(p) or (0, 0, 0, 0)
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            best = torch.empty(shape, dtype=torch.int32, device=dev)
+            rot = torch.empty(shape, dtype=torch.int32, device=dev)
+            ptrs = [C.c_void_p(best.data_ptr() or 1), C.c_void_p(rot.data_ptr() or 1)]   # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            best, rot = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
+            ptrs = [C.c_void_p(best.ctypes.data), C.c_void_p(rot.ctypes.data)]
+        self._check(self._lib.rbpf_locate_scan(self._h, p, _ip(b), _dp(r), _dp(a), r.shape[0], int(n_rot),
+                                               _lib.RBPF_LOCATE_DEVICE_OUT if device else 0, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        return best, rot, tuple(int(x) for x in b)
+
+    def relocalize(self, ranges, angles, particle="best", k: int = 8, n_rot: int = 720, seed: int = 0, box=None,
+                   nms_cells: int = 10):
+        """Starts the filter anywhere in a known map: locate_scan, then locate.hypotheses, then set_state with the particles
+        shared among the hypotheses in proportion to their scores (locate.seed_particles), covariances 0 and weights 1.
+        Returns the hypotheses (locate.Hypotheses); the filter then runs as after any set_state."""
+        from . import locate
+        best, rot, box = self.locate_scan(ranges, angles, particle=particle, box=box, n_rot=n_rot)
+        r = _f64(ranges)
+        n_used = int(np.count_nonzero((r > float(self.cfg.match_min_range)) & (r < float(self.cfg.match_max_range))))
+        cell = float(self.cfg.tile_len_m) / self.dim
+        hyp = locate.hypotheses(best, rot, box, n_rot, cell, k=k, nms_cells=nms_cells, n_used=n_used)
+        if len(hyp.poses) == 0:
+            raise ValueError("the box holds no observed-free cell: nothing to relocalize in")
+        self.set_state(poses=locate.seed_particles(hyp, self.P, cell, n_rot, seed), covs=0.0, weights=1.0)
+        return hyp
+
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)
         vals = np.empty(len(pts))
