@@ -314,6 +314,43 @@ int  rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
  * each case nothing is written.  Complete on return. */
 #define RBPF_LOAD_DEVICE_IN 1u     /* cells is a device pointer, read in stream order (validated on the device) */
 int  rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* cells, uint32_t flags);
+/* ---- map placement: a map with its own cell size and its own pose in the world, resampled into the particles' tiles ----
+ * src[nsx][nsy] (row-major int8, units of quantum, every value in [min_odds_emp, max_odds_occ] / quantum) is a raster whose
+ * cell (i, j) covers [i, i+1) x [j, j+1) times src_cell in the frame with origin (ox, oy) rotated by yaw;
+ * src_pose3 = (ox, oy, yaw) is the world pose of the corner of cell (0, 0) (the origin of the common PGM + YAML map format).
+ * box4 = {x0, x1, y0, y1} and the mosaic cells are those of rbpf_render_map / rbpf_load_map.  In float64, every operation
+ * rounded on its own, c = cos(yaw), s = sin(yaw) (host libm), cs = tile_len / dim, S = samples (1 .. 8); for the mosaic cell
+ * (X, Y) of the box and a, b = 0 .. S-1:
+ *   fa = (a + 0.5) / S                      fb = (b + 0.5) / S
+ *   wx = (X + fa) * cs                      wy = (Y + fb) * cs
+ *   dx = wx - ox                            dy = wy - oy
+ *   u  = (c*dx + s*dy) / src_cell           w  = (c*dy - s*dx) / src_cell
+ *   inside iff 0 <= floor(u) < nsx and 0 <= floor(w) < nsy;   sample = src[floor(u)][floor(w)]
+ *   covered[X-x0][Y-y0] = any sample inside
+ *   warped [X-x0][Y-y0] = max of the inside samples (0 when none)
+ * The maximum keeps a wall that crosses any part of the cell; a cell is free only if all of it is; S = 1 is nearest
+ * neighbour.  DESIGN.md 3.9 has the kernels.
+ * Without RBPF_PLACE_DRY the covered cells of the box are merged under `mode` into `particle` (>= 0) or into every particle
+ * (-1), each with its own old cells; cells of the box that are not covered keep their values.  Everything else is as
+ * rbpf_load_map: missing lattice tiles of the box come from the free pool, every touched tile's written box grows to hold
+ * (box n tile), its occupancy bits are recomputed, duplicate groups are dissolved, and the call is complete on return.
+ * warped and covered ([x1-x0][y1-y0]) may each be NULL.  With RBPF_PLACE_DRY at least one must be given, `particle` is
+ * ignored and no engine state changes (maps, tiles, counters, random streams, duplicate grouping); with RBPF_PLACE_DEVICE_OUT
+ * and a host source such a call does not wait for the device.
+ * All or nothing, checked before anything is written: a NULL box4, src or src_pose3, nsx or nsy < 1, nsx * nsy >= 2^31, a box
+ * of more than 2^31 cells or one that leaves the lattice, a non-finite pose, src_cell not finite or not > 0, samples outside
+ * 1 .. 8, an unknown mode or flag, a bad particle or a source value out of range (a device source is checked on the device,
+ * and the call then waits for the verdict) is RBPF_EINVAL; too few free tiles is RBPF_ENOMEM (the message gives the number
+ * needed); a call between rbpf_scan_update_begin and _end is RBPF_ESTATE. */
+#define RBPF_PLACE_DEVICE_IN  1u   /* src is a device pointer, read in stream order, validated on the device */
+#define RBPF_PLACE_DEVICE_OUT 2u   /* warped / covered are device pointers, written in stream order, no host wait */
+#define RBPF_PLACE_DRY        4u   /* compute warped / covered only: no map, tile, counter or duplicate grouping changes */
+#define RBPF_PLACE_REPLACE 0       /* covered cells take the warped value                                  */
+#define RBPF_PLACE_KNOWN   1       /* ... only where the warped value is not 0 (the source knows something) */
+#define RBPF_PLACE_ADD     2       /* covered cells become clamp(old + warped, vmin, vmax): log-odds fusion  */
+int  rbpf_place_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* src, int32_t nsx, int32_t nsy,
+                    double src_cell, const double* src_pose3, int32_t samples, int32_t mode, uint32_t flags, int8_t* warped,
+                    uint8_t* covered);
 /* Map updates on (1, the default) or off (0).  Off, rbpf_scan_update(_end) leaves every map unchanged: the NaN-branch
  * weight increment (robot.py:73-78) is taken on the unchanged map, and the proposal's random stream still advances one
  * step per scan update (rbpf_get_rng_state).  This is localization in a known map.  An explicit rbpf_map_update writes

@@ -17,6 +17,8 @@ RBPF_RENDER_DEVICE_OUT = 1
 RBPF_LOAD_DEVICE_IN = 1
 RBPF_CAST_DEVICE_OUT = 1
 RBPF_LOCATE_DEVICE_OUT = 1
+RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
+RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
 
 
@@ -111,6 +113,8 @@ PROTOTYPES = {
     "rbpf_map_extent": (C.c_int, [_H, C.c_int32, _I]),
     "rbpf_render_map": (C.c_int, [_H, C.c_int32, _I, _D, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_load_map": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_uint32]),
+    "rbpf_place_map": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_int32, C.c_int32, C.c_double, _D, C.c_int32, C.c_int32, C.c_uint32,
+                       C.c_void_p, C.c_void_p]),
     "rbpf_set_map_updates": (C.c_int, [_H, C.c_int32]),
     "rbpf_get_map_updates": (C.c_int, [_H, _I]),
     "rbpf_cast_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -1391,7 +1391,72 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     return RBPF_OK;
 }
 
-// ---- map loading (kernels_load.hip) ---------------------------------------------------------------------------------------
+// ---- map loading (kernels_load.hip) and placement (kernels_place.hip) ---------------------------------------------------------
+// What a call that writes a box into tiles works out before it queues anything: the lattice positions the box touches with
+// (box n tile) in tile-local cells, the jobs of tile_write_kernel, and that the pool holds the tiles that are missing.
+struct TileWritePlan { std::vector<LoadTile> tiles; std::vector<RenderJob> jobs; int p_lo = 0, p_hi = 0; };
+
+static bool box_in_lattice(const DevView& v, const int32_t* box4) {
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    return box4[0] + off >= 0 && box4[1] + off <= edge && box4[2] + off >= 0 && box4[3] + off <= edge;
+}
+
+static int plan_tile_write(rbpf_handle* h, int32_t particle, const int32_t* box4, const char* what, TileWritePlan& pl) {
+    const DevView& v = h->v;
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2;
+    {
+        const long long a_lo = (box4[0] + off) / dim, a_hi = (box4[1] - 1 + off) / dim;
+        const long long b_lo = (box4[2] + off) / dim, b_hi = (box4[3] - 1 + off) / dim;
+        for (long long a = a_lo; a <= a_hi; ++a)
+            for (long long b = b_lo; b <= b_hi; ++b)
+                pl.tiles.push_back({(int32_t)(a * v.L + b), (int32_t)std::max(0LL, box4[0] + off - a * dim),
+                                    (int32_t)std::min(dim - 1, box4[1] - 1 + off - a * dim), (int32_t)std::max(0LL, box4[2] + off - b * dim),
+                                    (int32_t)std::min(dim - 1, box4[3] - 1 + off - b * dim)});
+    }
+    render_jobs(v, box4, pl.jobs, 32);
+    if (pl.jobs.size() > ((size_t)1 << 24)) return fail(h, RBPF_ENOMEM, std::string("box too large for one ") + what);
+    // count the missing tiles before anything is allocated: one read of free_top, the slots and their tile_tab rows
+    pl.p_lo = particle < 0 ? 0 : particle; pl.p_hi = particle < 0 ? v.P : particle + 1;
+    const int np = pl.p_hi - pl.p_lo;
+    const size_t LL = (size_t)v.L * v.L;
+    std::vector<int32_t> slot(np), tab((size_t)v.P * LL);
+    int32_t top = 0;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&top, v.free_top, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(slot.data(), v.slot + pl.p_lo, (size_t)np * 4, hipMemcpyDeviceToHost));
+    if (particle < 0) HIP_TRY(h, hipMemcpy(tab.data(), v.tile_tab, tab.size() * 4, hipMemcpyDeviceToHost));
+    else HIP_TRY(h, hipMemcpy(tab.data() + (size_t)slot[0] * LL, v.tile_tab + (size_t)slot[0] * LL, LL * 4, hipMemcpyDeviceToHost));
+    long long need = 0;
+    for (int q = 0; q < np; ++q)
+        for (const LoadTile& lt : pl.tiles) need += tab[(size_t)slot[q] * LL + lt.pos] < 0;
+    if (need > top)
+        return fail(h, RBPF_ENOMEM, std::string(what) + " needs " + std::to_string(need) + " free tiles, the pool has " + std::to_string(top));
+    return RBPF_OK;
+}
+
+// Device staging of such a call in scratch buffer b through staging block st: [flag, padded to 16] [tiles] [jobs], then
+// `extra` bytes of the caller's at byte meta_b, the first tail_b of them filled from `tail` (host memory, free again on return).
+// One upload (the flag cleared); points `a` into it.
+static int stage_tile_write(rbpf_handle* h, int b, int st_id, const TileWritePlan& pl, size_t extra, const void* tail, size_t tail_b,
+                            LoadArgs& a, size_t& meta_b) {
+    const size_t tiles_b = (pl.tiles.size() * sizeof(LoadTile) + 15) & ~(size_t)15, jobs_b = pl.jobs.size() * sizeof(RenderJob);
+    meta_b = 16 + tiles_b + ((jobs_b + 15) & ~(size_t)15);
+    HIP_TRY(h, h->reserve(b, meta_b + extra));
+    const Block& d = h->buf[b];
+    Staging& st = h->stage[st_id];
+    HIP_TRY(h, st.begin(meta_b + tail_b));
+    memset(st.p, 0, meta_b);
+    memcpy(st.p + 16, pl.tiles.data(), pl.tiles.size() * sizeof(LoadTile));
+    memcpy(st.p + 16 + tiles_b, pl.jobs.data(), jobs_b);
+    if (tail_b) memcpy(st.p + meta_b, tail, tail_b);
+    HIP_TRY(h, st.upload(d.p, meta_b + tail_b, h->stream));
+    a.bad = d.as<int32_t>();
+    a.tiles = d.as<const LoadTile>(16); a.n_tiles = (int)pl.tiles.size();
+    a.jobs = d.as<const RenderJob>(16 + tiles_b);
+    a.p_lo = pl.p_lo; a.p_hi = pl.p_hi;
+    return RBPF_OK;
+}
+
 int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* cells, uint32_t flags) {
     if (!h) return RBPF_EINVAL;
     ON_DEVICE(h);
@@ -1403,70 +1468,94 @@ int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const i
     if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
     const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
     if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
-    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
-    if (ncell > 0 && (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge))
-        return fail(h, RBPF_EINVAL, "box leaves the tile lattice (raise lattice_radius)");
+    if (ncell > 0 && !box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice (raise lattice_radius)");
     const bool dev_in = (flags & RBPF_LOAD_DEVICE_IN) != 0;
     if (!dev_in)   // the reference's cells never leave [min_odds_emp, max_odds_occ] (gridmap.py:86-117); the map kernels rely on it
         for (long long i = 0; i < ncell; ++i)
             if (cells[i] < v.cc.vmin || cells[i] > v.cc.vmax) return fail(h, RBPF_EINVAL, "cell value outside [min_odds_emp, max_odds_occ]");
     if (ncell == 0) return RBPF_OK;
-    // the lattice positions the box touches, with (box n tile) in tile-local cells
-    std::vector<LoadTile> tiles;
-    {
-        const long long a_lo = (box4[0] + off) / dim, a_hi = (box4[1] - 1 + off) / dim;
-        const long long b_lo = (box4[2] + off) / dim, b_hi = (box4[3] - 1 + off) / dim;
-        for (long long a = a_lo; a <= a_hi; ++a)
-            for (long long b = b_lo; b <= b_hi; ++b)
-                tiles.push_back({(int32_t)(a * v.L + b), (int32_t)std::max(0LL, box4[0] + off - a * dim),
-                                 (int32_t)std::min(dim - 1, box4[1] - 1 + off - a * dim), (int32_t)std::max(0LL, box4[2] + off - b * dim),
-                                 (int32_t)std::min(dim - 1, box4[3] - 1 + off - b * dim)});
-    }
-    std::vector<RenderJob> jobs;
-    render_jobs(v, box4, jobs, 32);
-    if (jobs.size() > ((size_t)1 << 24)) return fail(h, RBPF_ENOMEM, "box too large to load in one call");
-    // count the missing tiles before anything is allocated: one read of free_top, the slots and their tile_tab rows
-    const int p_lo = particle < 0 ? 0 : particle, p_hi = particle < 0 ? v.P : particle + 1, np = p_hi - p_lo;
-    const size_t LL = (size_t)v.L * v.L;
-    {
-        std::vector<int32_t> slot(np), tab((size_t)v.P * LL);
-        int32_t top = 0;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipMemcpy(&top, v.free_top, 4, hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(slot.data(), v.slot + p_lo, (size_t)np * 4, hipMemcpyDeviceToHost));
-        if (particle < 0) HIP_TRY(h, hipMemcpy(tab.data(), v.tile_tab, tab.size() * 4, hipMemcpyDeviceToHost));
-        else HIP_TRY(h, hipMemcpy(tab.data() + (size_t)slot[0] * LL, v.tile_tab + (size_t)slot[0] * LL, LL * 4, hipMemcpyDeviceToHost));
-        long long need = 0;
-        for (int q = 0; q < np; ++q)
-            for (const LoadTile& lt : tiles) need += tab[(size_t)slot[q] * LL + lt.pos] < 0;
-        if (need > top)
-            return fail(h, RBPF_ENOMEM, "map load needs " + std::to_string(need) + " free tiles, the pool has " + std::to_string(top));
-    }
-    // device staging: [flag, padded to 16] [tiles] [jobs] [the raster, host input only]
-    const size_t tiles_b = (tiles.size() * sizeof(LoadTile) + 15) & ~(size_t)15, jobs_b = jobs.size() * sizeof(RenderJob);
-    const size_t meta_b = 16 + tiles_b + ((jobs_b + 15) & ~(size_t)15);
-    HIP_TRY(h, h->reserve(B_LOAD, meta_b + (dev_in ? 0 : (size_t)ncell)));
-    const Block& d_load = h->buf[B_LOAD];
-    Staging& st = h->stage[S_LOAD];
-    HIP_TRY(h, st.begin(meta_b));
-    memset(st.p, 0, meta_b);
-    memcpy(st.p + 16, tiles.data(), tiles.size() * sizeof(LoadTile));
-    memcpy(st.p + 16 + tiles_b, jobs.data(), jobs_b);
-    HIP_TRY(h, st.upload(d_load.p, meta_b, h->stream));
-    if (!dev_in) HIP_TRY(h, hipMemcpyAsync(d_load.p + meta_b, cells, (size_t)ncell, hipMemcpyHostToDevice, h->stream));
+    TileWritePlan pl;
+    if (const int rc = plan_tile_write(h, particle, box4, "map load", pl)) return rc;
+    // the raster (host input only) follows the staged lists
     LoadArgs a;
-    a.bad = d_load.as<int32_t>();
-    a.tiles = d_load.as<const LoadTile>(16); a.n_tiles = (int)tiles.size();
-    a.jobs = d_load.as<const RenderJob>(16 + tiles_b);
+    size_t meta_b = 0;
+    if (const int rc = stage_tile_write(h, B_LOAD, S_LOAD, pl, dev_in ? 0 : (size_t)ncell, nullptr, 0, a, meta_b)) return rc;
+    const Block& d_load = h->buf[B_LOAD];
+    if (!dev_in) HIP_TRY(h, hipMemcpyAsync(d_load.p + meta_b, cells, (size_t)ncell, hipMemcpyHostToDevice, h->stream));
     a.cells = dev_in ? cells : d_load.as<const int8_t>(meta_b);
-    a.ny = ny; a.ncell = ncell; a.p_lo = p_lo; a.p_hi = p_hi;
+    a.ny = ny; a.ncell = ncell;
     if (dev_in) launch_load_validate(v, a, h->stream);
-    launch_load_map(v, a, (int)jobs.size(), h->stream);
+    launch_load_map(v, a, (int)pl.jobs.size(), h->stream);
     HIP_TRY(h, hipGetLastError());
     int32_t bad = 0;
     HIP_TRY(h, hipMemcpyAsync(&bad, a.bad, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (bad) return fail(h, RBPF_EINVAL, "cell value outside [min_odds_emp, max_odds_occ]");
+    v.dups_valid = 0;                   // a duplicate's map may differ from its representative's now
+    return check_device_error(h);
+}
+
+int rbpf_place_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* src, int32_t nsx, int32_t nsy,
+                   double src_cell, const double* src_pose3, int32_t samples, int32_t mode, uint32_t flags, int8_t* warped,
+                   uint8_t* covered) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    DevView& v = h->v;
+    if (!box4 || !src || !src_pose3) return fail(h, RBPF_EINVAL, "box4, src or src_pose3 is NULL");
+    if (flags & ~(RBPF_PLACE_DEVICE_IN | RBPF_PLACE_DEVICE_OUT | RBPF_PLACE_DRY)) return fail(h, RBPF_EINVAL, "unknown flags");
+    const bool dev_in = (flags & RBPF_PLACE_DEVICE_IN) != 0, dev_out = (flags & RBPF_PLACE_DEVICE_OUT) != 0, dry = (flags & RBPF_PLACE_DRY) != 0;
+    if (mode != RBPF_PLACE_REPLACE && mode != RBPF_PLACE_KNOWN && mode != RBPF_PLACE_ADD) return fail(h, RBPF_EINVAL, "unknown mode");
+    if (samples < 1 || samples > 8) return fail(h, RBPF_EINVAL, "1 <= samples <= 8 is required");
+    if (nsx < 1 || nsy < 1 || (long long)nsx * nsy >= (1LL << 31)) return fail(h, RBPF_EINVAL, "nsx >= 1, nsy >= 1 and nsx * nsy < 2^31 are required");
+    if (!std::isfinite(src_cell) || !(src_cell > 0.0)) return fail(h, RBPF_EINVAL, "src_cell must be finite and > 0");
+    if (!std::isfinite(src_pose3[0]) || !std::isfinite(src_pose3[1]) || !std::isfinite(src_pose3[2])) return fail(h, RBPF_EINVAL, "src_pose3 must be finite");
+    if (dry && !warped && !covered) return fail(h, RBPF_EINVAL, "a dry run needs warped and / or covered");
+    if (!dry && (particle < -1 || particle >= v.P)) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map placement between rbpf_scan_update_begin and rbpf_scan_update_end");
+    if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
+    const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
+    if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
+    if (ncell > 0 && !box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice (raise lattice_radius)");
+    const size_t nsrc = (size_t)nsx * nsy;
+    if (!dev_in)
+        for (size_t i = 0; i < nsrc; ++i)
+            if (src[i] < v.cc.vmin || src[i] > v.cc.vmax) return fail(h, RBPF_EINVAL, "source value outside [min_odds_emp, max_odds_occ]");
+    if (ncell == 0) return RBPF_OK;
+    TileWritePlan pl;
+    if (!dry)
+        if (const int rc = plan_tile_write(h, particle, box4, "map placement", pl)) return rc;
+    // behind the staged lists: the source (host input only, uploaded with them), then the rasters for host outputs
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t src_b = dev_in ? 0 : pad(nsrc), out_b = dev_out ? 0 : pad((size_t)ncell);
+    LoadArgs a;
+    size_t meta_b = 0;
+    if (const int rc = stage_tile_write(h, B_PLACE, S_PLACE, pl, src_b + 2 * out_b, src, dev_in ? 0 : nsrc, a, meta_b)) return rc;
+    const Block& d = h->buf[B_PLACE];
+    a.cells = dev_in ? src : d.as<const int8_t>(meta_b);
+    a.ny = ny; a.ncell = (long long)nsrc;                                  // what the validation kernel walks
+    PlaceArgs q;
+    q.src = a.cells; q.nsx = nsx; q.nsy = nsy;
+    q.c = cos(src_pose3[2]); q.s = sin(src_pose3[2]); q.ox = src_pose3[0]; q.oy = src_pose3[1];   // host libm: the device never sees the yaw
+    q.src_cell = src_cell; q.cs = v.tile_len / (double)v.dim;
+    q.S = samples; q.mode = mode; q.x0 = box4[0]; q.y0 = box4[2]; q.ny = ny; q.ncell = ncell;
+    q.warped = !warped ? nullptr : dev_out ? warped : d.as<int8_t>(meta_b + src_b);
+    q.covered = !covered ? nullptr : dev_out ? covered : d.as<uint8_t>(meta_b + src_b + out_b);
+    q.bad = a.bad;
+    if (dev_in) launch_load_validate(v, a, h->stream);
+    if (warped || covered) launch_place_warp(q, h->stream);
+    if (!dry) launch_place_map(v, a, q, (int)pl.jobs.size(), h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dry && dev_out && !dev_in) return RBPF_OK;                         // nothing to wait for: the host checked the source
+    int32_t bad = 0;
+    HIP_TRY(h, hipMemcpyAsync(&bad, a.bad, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (bad) return fail(h, RBPF_EINVAL, "source value outside [min_odds_emp, max_odds_occ]");
+    if (!dev_out) {
+        if (warped) HIP_TRY(h, hipMemcpyAsync(warped, q.warped, (size_t)ncell, hipMemcpyDeviceToHost, h->stream));
+        if (covered) HIP_TRY(h, hipMemcpyAsync(covered, q.covered, (size_t)ncell, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (dry) return RBPF_OK;
     v.dups_valid = 0;                   // a duplicate's map may differ from its representative's now
     return check_device_error(h);
 }

@@ -135,6 +135,19 @@ struct LoadArgs {
     int p_lo, p_hi;                    // particles [p_lo, p_hi)
     int32_t* bad;                      // [1] != 0: validation found a value out of range - the alloc and write kernels do nothing
 };
+// map placement (kernels_place.hip): a source raster with its own cell size and world pose, resampled onto the
+// mosaic cells of a box.  The trigonometry is done on the host.
+struct PlaceArgs {
+    const int8_t* src;                 // [nsx][nsy] (device)
+    int nsx, nsy;
+    double c, s, ox, oy;               // cos and sin of the source yaw, world position of the corner of source cell (0, 0)
+    double src_cell, cs;               // metres per source cell, metres per mosaic cell (tile_len / dim)
+    int S, mode;                       // samples per axis and cell (1 .. 8), RBPF_PLACE_REPLACE / _KNOWN / _ADD
+    int x0, y0;                        // mosaic cell of output element [0][0]
+    long long ny, ncell;               // output columns and cells
+    int8_t* warped; uint8_t* covered;  // [nx][ny] outputs of place_warp_kernel (either may be null)
+    const int32_t* bad;                // LoadArgs::bad of the same call
+};
 // scan casting (kernels_cast.hip): ray r = pose * B + beam; the trigonometry is done on the host
 struct CastArgs {
     const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
@@ -217,6 +230,9 @@ void launch_render_cells(const DevView& v, int particle, const RenderJob* d_jobs
 void launch_render_filter(const DevView& v, const RenderFilter& f, int n_jobs, int G, hipStream_t s);   // G particle chunks
 void launch_load_validate(const DevView& v, const LoadArgs& a, hipStream_t s);
 void launch_load_map(const DevView& v, const LoadArgs& a, int n_jobs, hipStream_t s);   // tile allocation, then the cells
+void launch_load_alloc(const DevView& v, const LoadArgs& a, hipStream_t s);             // the tile allocation alone
+void launch_place_warp(const PlaceArgs& q, hipStream_t s);                              // warped / covered rasters of the box
+void launch_place_map(const DevView& v, const LoadArgs& a, const PlaceArgs& q, int n_jobs, hipStream_t s);   // tile allocation, then the merge
 void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 }  // namespace rbpf

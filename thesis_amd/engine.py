@@ -342,6 +342,96 @@ class ParticleEngine:
         self._check(self._lib.rbpf_load_map(self._h, p, _ip(b), ptr, flags))
         del cells                                        # kept alive until the call returned (it is complete on return)
 
+    # -- map placement (include/rbpf_hip.h: rbpf_place_map; thesis_amd/mapio.py: SourceMap) ----------------
+    PLACE_MODES = {"replace": _lib.RBPF_PLACE_REPLACE, "known": _lib.RBPF_PLACE_KNOWN, "add": _lib.RBPF_PLACE_ADD}
+
+    def _place_inputs(self, src, box, samples):
+        """The arguments place_map and warp_map share: (cells kept alive, pointer, shape, input flag, pose, box, samples,
+        torch's current stream or None, whether the engine works on that stream)."""
+        from .mapio import placed_box
+        cfg = self.cfg
+        if abs(float(src.quantum) - float(cfg.quantum)) > 1e-9 * abs(float(cfg.quantum)):
+            raise ValueError(f"source quantum = {src.quantum!r} differs from the engine's {cfg.quantum!r}")
+        cells, flags, cur, same_stream = src.cells, 0, None, False
+        if hasattr(cells, "data_ptr"):                   # a torch tensor
+            import torch
+            dev = torch.device("cuda", int(cfg.device))
+            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
+                raise ValueError(f"a tensor source must be 2-D int8 on {dev}")
+            cells = cells.contiguous()
+            shape, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr() or 1), _lib.RBPF_PLACE_DEVICE_IN
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+        else:
+            a = np.asarray(cells)
+            if a.ndim != 2:
+                raise ValueError("source cells must be 2-D [nsx][nsy]")
+            if a.dtype != np.int8:
+                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
+                    raise ValueError("source cells must be int8 lattice values")
+            cells = np.ascontiguousarray(a, dtype=np.int8)
+            shape, ptr = cells.shape, C.c_void_p(cells.ctypes.data or 1)
+        cell = float(cfg.tile_len_m) / self.dim
+        if box is None:
+            box = placed_box(src, cell, self.dim, int(cfg.lattice_radius))
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        if samples is None:
+            samples = min(8, max(2, int(np.ceil(2.0 * cell / float(src.cell_size)))))
+        pose = _f64([float(v) for v in src.origin])
+        if pose.shape != (3,):
+            raise ValueError("source origin must be (x, y, yaw)")
+        return cells, ptr, shape, flags, pose, b, int(samples), cur, same_stream
+
+    def place_map(self, src, particle: Optional[int] = None, box=None, samples: Optional[int] = None, mode: str = "replace"):
+        """Resamples the map `src` (a mapio.SourceMap: any cell size, origin and yaw; e.g. mapio.read_map_image, or
+        mapio.source_from_raster of a render) onto the engine's cells and merges it into `particle`'s map, or into every
+        particle's (None), each with its own old cells.  `box` = (x0, x1, y0, y1) in mosaic cells, default
+        mapio.placed_box(src, ...); `samples` per axis and cell (1 .. 8), default min(8, max(2, ceil(2 cell / src cell))):
+        a cell takes the largest source value any of its samples meets.  `mode`: "replace" (covered cells take the
+        resampled value), "known" (only where that value is not 0) or "add" (log-odds fusion: old + new, clamped).  Cells
+        the source does not cover keep their values.  `src.cells` is a numpy array, or an int8 torch tensor on the
+        engine's device.  All or nothing: on an error no map changes.  Returns the box."""
+        if mode not in self.PLACE_MODES:
+            raise ValueError(f"unknown mode {mode!r}")
+        cells, ptr, shape, flags, pose, b, S, cur, same_stream = self._place_inputs(src, box, samples)
+        if cur is not None and not same_stream:
+            cur.synchronize()                            # the tensor was written in torch's stream order
+        self._check(self._lib.rbpf_place_map(self._h, -1 if particle is None else int(particle), _ip(b), ptr, shape[0], shape[1],
+                                             float(src.cell_size), _dp(pose), S, self.PLACE_MODES[mode], flags, None, None))
+        del cells                                        # kept alive until the call returned (it is complete on return)
+        return tuple(int(x) for x in b)
+
+    def warp_map(self, src, box=None, samples: Optional[int] = None, device: bool = False):
+        """What place_map would write, without writing it: (warped, covered, box) with `warped` int8 and `covered` uint8
+        rasters [x1-x0, y1-y0] of `box` (covered: some sample of the cell met the source; warped: the largest source value
+        met, 0 where none).  No engine state changes.  device=True: torch tensors on the engine's device, ready for work
+        on torch's current stream."""
+        cells, ptr, shape, flags, pose, b, S, cur, same_stream = self._place_inputs(src, box, samples)
+        oshape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))   # a bad box is the library's to refuse
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            if cur is None:
+                cur = torch.cuda.current_stream(dev)
+                same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            warped = torch.empty(oshape, dtype=torch.int8, device=dev)
+            covered = torch.empty(oshape, dtype=torch.uint8, device=dev)
+            ptrs = [C.c_void_p(warped.data_ptr() or 1), C.c_void_p(covered.data_ptr() or 1)]   # (an empty tensor has no data pointer)
+            flags |= _lib.RBPF_PLACE_DEVICE_OUT
+        else:
+            warped, covered = np.empty(oshape, dtype=np.int8), np.empty(oshape, dtype=np.uint8)
+            ptrs = [C.c_void_p(warped.ctypes.data or 1), C.c_void_p(covered.ctypes.data or 1)]
+        if cur is not None and not same_stream:
+            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
+        self._check(self._lib.rbpf_place_map(self._h, -1, _ip(b), ptr, shape[0], shape[1], float(src.cell_size), _dp(pose), S,
+                                             _lib.RBPF_PLACE_REPLACE, flags | _lib.RBPF_PLACE_DRY, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        del cells
+        return warped, covered, tuple(int(x) for x in b)
+
     @property
     def map_updates(self) -> bool:
         """True (default): every scan update writes the maps.  False: localization in the maps as they are; the NaN

@@ -153,6 +153,11 @@ class ParticleFilter:
         """A prior map (a MapRaster with int8 cells, e.g. mapio.read_occupancy_map) into one particle or into all (None)."""
         self.engine.load_map(raster, particle)
 
+    def place_map(self, src, particle=None, box=None, samples=None, mode="replace"):
+        """A map of any cell size, origin and yaw (a mapio.SourceMap, e.g. mapio.read_map_image) resampled into one particle
+        or into all (None) (ParticleEngine.place_map).  Returns the box it was placed in."""
+        return self.engine.place_map(src, particle, box=box, samples=samples, mode=mode)
+
     @property
     def map_updates(self) -> bool:
         return self.engine.map_updates
