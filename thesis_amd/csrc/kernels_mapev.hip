@@ -37,6 +37,7 @@ static const int EB = 1024;                    // threads per particle
 static const int HIT_BOUND = 62;               // per direction class; two classes can meet in a cell, +1 for the flag's count bit: 125 < 128
 static const int EVCAP = 3072;                 // passes over flagged cells kept per particle (more: exact replay of every flagged cell)
 static const int NPAIR = 3;                    // pairs (beam, e) per thread kept in registers: 3 * EB pairs = 1536 beams
+static const int FOLD_SPAN = 64;               // a flagged cell whose pairs lie within this many of each other is folded from a 64-bit set in registers
 
 struct EvGeom {
     int fanw, bpad, ncell, T, logT, E;
@@ -194,7 +195,9 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     if (tid <= MAXLEV) s_lcnt[tid] = 0;
     for (int i = tid; i < (NEAR_W * NEAR_W + 1) / 2; i += EB) mini[i] = 0;
     __syncthreads();
+#ifndef EV_STAMP_FLAGS
     STAMP(0);
+#endif
     const double s_s = s_sincos[0], s_c = s_sincos[1];
 
     const int C = v.R * v.dim + v.dim / 2;
@@ -329,6 +332,9 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         }
     }
 
+#ifdef EV_STAMP_FLAGS                                                           // diagnostic: slot 0 = the pairs' set-up (slot 1 then holds the whole set-up), slot 2 = clearing the window and the flags
+    STAMP(0);
+#endif
     // =============================================== windows ==============================================
     int n_win = 0;
     for (int S0 = S_lo; S0 <= S_hi; S0 += rows_cap - 1, ++n_win) {
@@ -639,9 +645,41 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         for (int r = tid; r < NR; r += EB) {
             const int h = rlist[r];
             int val = (int)oldc[h];
-            // the cell's pairs, laid out one after the other
-            int n = 0;
-            for (int m = (int)head[h]; m != 0xFFFF; m = nextp[m]) ++n;
+            // ONE walk of the cell's list: its length, its smallest and largest pair, and the pairs as bits of a 128-bit set
+            // round the first one (w0: pairs first - 64 .. first - 1, w1: first .. first + 63)
+            const int first = (int)head[h];
+            int n = 0, plo = 0xFFFF, phi = 0;
+            unsigned long long w0 = 0, w1 = 0;
+            for (int m = first; m != 0xFFFF; m = nextp[m]) {
+                ++n; plo = min(plo, m); phi = max(phi, m);
+                const int d = m - first;
+                if ((unsigned)(d + 64) < 64u) w0 |= 1ull << ((d + 64) & 63);
+                if ((unsigned)d < 64u) w1 |= 1ull << (d & 63);
+            }
+            if (phi - plo < FOLD_SPAN) {
+                // the cell's pairs lie within 64 of each other (the beams that end in one cell are neighbours in the scan):
+                // bit i of the set = pair plo + i.  Its bits in rising order are the events in (beam, nearby) order, and
+                // the neighbours of a bit say what the list's order said: pair e - 1 of the same beam right before an
+                // odd e, pair e + 1 right after an even one.
+                const int s = plo - first + 64;                                       // 1 .. 64
+                const unsigned long long set = s == 64 ? w1 : (w0 >> (s & 63)) | (w1 << ((64 - s) & 63));
+                unsigned long long rest = set;
+                while (rest) {
+                    const int bit = __ffsll((long long)rest) - 1;
+                    rest &= rest - 1;
+                    const int ek = plo + bit;
+                    const bool below = bit > 0 && ((set >> ((bit - 1) & 63)) & 1ull), above = bit < 63 && ((set >> ((bit + 1) & 63)) & 1ull);
+                    // the beam's own pass over the cell before its nearby hit is not in the list: it precedes the beam's first event here
+                    const bool own_pass = (ek & 1) ? !below : above;
+                    const int np = (int)ic16[ek] + (own_pass ? 1 : 0);
+                    val = max(val + min(np, sat) * v.cc.emp, v.cc.vmin);              // gridmap.py:97-101, np times
+                    val = min(val + ((ek & 1) ? v.cc.nearby : v.cc.occ), v.cc.vmax);  // gridmap.py:86-90 / 108-112
+                }
+                val = max(val + min((int)iclast[h], sat) * v.cc.emp, v.cc.vmin);
+                store_cell(keys[h], val);
+                continue;
+            }
+            // pairs further apart (beams out of angular order, a scan that wraps round): laid out one after the other
             const int o2 = atomicAdd(&s_wsum[0], n);
             { int i = 0; for (int m = (int)head[h]; m != 0xFFFF; m = nextp[m]) evl[o2 + i++] = (uint16_t)m; }
             // the events in ascending (beam, nearby) order: the smallest one above the last, n times (a handful per cell)
