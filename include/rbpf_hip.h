@@ -400,6 +400,31 @@ int  rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, i
 int  rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* ranges, const double* angles,
                       int32_t n_beams, int32_t n_rot, uint32_t flags, int32_t* best, int32_t* rot);
 
+/* ---- alignment: where in a particle's map does this point set (a map of unknown pose) fit? ------------------------------
+ * Scores a set of occupied points occ_xy[n_occ][2] and free points free_xy[n_free][2] (metres, in a frame of their own) at
+ * every pose (X, Y, r) of the box box4 = {x0, x1, y0, y1} and the rotation window r = r_begin .. r_begin + r_count - 1 in the
+ * map of `particle` (>= 0): the origin of the points' frame stands at the centre of cell (X, Y), turned by theta_r.  v, occ,
+ * dil, F, inv, theta_r, c_r, s_r (host libm), the mosaic cells and box4 are those of rbpf_locate_scan.  In float64, every
+ * operation rounded on its own, for occupied and free points (px, py) alike:
+ *   u[r,k] = floor(0.5 + (c_r px_k - s_r py_k) inv)          w[r,k] = floor(0.5 + (s_r px_k + c_r py_k) inv)
+ *   hits (X, Y, r) = sum over occupied points of F(X + u, Y + w)                        in 0 .. 2 n_occ
+ *   clash(X, Y, r) = number of free points with occ(X + u, Y + w)                       in 0 .. n_free
+ *   score(X, Y, r) = hits - 2 clash                                                     in -2 n_free .. 2 n_occ
+ *   best[X-x0][Y-y0] = max over the window of score      rot[X-x0][Y-y0] = the smallest r of the window that attains it
+ * Every cell of the box is a candidate: there is no gate and no -1.  (The kernels sum hits + 2 (n_free - clash) >= 0 and
+ * subtract 2 n_free at the end.)  Limits: 1 <= n_occ, 0 <= n_free (free_xy may then be NULL), n_occ + n_free <= 32767;
+ * 1 <= n_rot <= 4096, 0 <= r_begin, 1 <= r_count, r_begin + r_count <= n_rot; the box must lie in the tile lattice and hold
+ * fewer than 2^31 cells; M = ceil(max_k hypot(px_k, py_k) inv) + 1 (host libm) must not pass 16384.  A NULL box4, occ_xy,
+ * best or rot, a non-finite coordinate, a bad particle, box, count, window or M, or an unknown flag is RBPF_EINVAL; a call
+ * between rbpf_scan_update_begin and _end is RBPF_ESTATE; scratch beyond 2 GiB is RBPF_ENOMEM; all are checked before
+ * anything is queued, and nothing is written.  The call changes no engine state (maps, particles, random streams,
+ * counters, duplicate grouping).  It runs on the handle's stream; without RBPF_ALIGN_DEVICE_OUT the outputs are host
+ * arrays, complete on return. */
+#define RBPF_ALIGN_DEVICE_OUT 1u   /* best / rot are device pointers, written in stream order, no host wait */
+int  rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* occ_xy, int32_t n_occ,
+                       const double* free_xy, int32_t n_free, int32_t n_rot, int32_t r_begin, int32_t r_count, uint32_t flags,
+                       int32_t* best, int32_t* rot);
+
 #ifdef __cplusplus
 }
 #endif

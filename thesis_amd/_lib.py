@@ -17,6 +17,7 @@ RBPF_RENDER_DEVICE_OUT = 1
 RBPF_LOAD_DEVICE_IN = 1
 RBPF_CAST_DEVICE_OUT = 1
 RBPF_LOCATE_DEVICE_OUT = 1
+RBPF_ALIGN_DEVICE_OUT = 1
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -119,6 +120,8 @@ PROTOTYPES = {
     "rbpf_get_map_updates": (C.c_int, [_H, _I]),
     "rbpf_cast_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_locate_scan": (C.c_int, [_H, C.c_int32, _I, _D, _D, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rbpf_align_points": (C.c_int, [_H, C.c_int32, _I, _D, C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                          C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

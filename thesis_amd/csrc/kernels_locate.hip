@@ -181,6 +181,10 @@ __global__ __launch_bounds__(LB) void locate_final_kernel(LocateArgs a) {
 
 static unsigned blocks_for(long long n) { return (unsigned)((n + LB - 1) / LB); }
 
+void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s) {
+    locate_field_kernel<<<blocks_for((long long)a.rows * a.W), LB, 0, s>>>(v, a);
+}
+
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s) {
     const long long words = (long long)a.nx * a.nyw;
     locate_field_kernel<<<blocks_for((long long)a.rows * a.W), LB, 0, s>>>(v, a);

@@ -1687,4 +1687,82 @@ int rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     return RBPF_OK;
 }
 
+// ---- alignment of a point set (kernels_align.hip) -------------------------------------------------------------------------------
+int rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* occ_xy, int32_t n_occ,
+                      const double* free_xy, int32_t n_free, int32_t n_rot, int32_t r_begin, int32_t r_count, uint32_t flags,
+                      int32_t* best, int32_t* rot) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4 || !occ_xy || !best || !rot) return fail(h, RBPF_EINVAL, "box4, occ_xy, best or rot is NULL");
+    if (flags & ~RBPF_ALIGN_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (n_occ < 1 || n_free < 0 || (long long)n_occ + n_free > 32767) return fail(h, RBPF_EINVAL, "1 <= n_occ, 0 <= n_free and n_occ + n_free <= 32767 are required");
+    if (n_free > 0 && !free_xy) return fail(h, RBPF_EINVAL, "free_xy is NULL with n_free > 0");
+    if (n_rot < 1 || n_rot > 4096) return fail(h, RBPF_EINVAL, "1 <= n_rot <= 4096 is required");
+    if (r_begin < 0 || r_count < 1 || (long long)r_begin + r_count > n_rot) return fail(h, RBPF_EINVAL, "0 <= r_begin, 1 <= r_count and r_begin + r_count <= n_rot are required");
+    if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
+    if (ncell >= (1LL << 31)) return fail(h, RBPF_EINVAL, "box must hold fewer than 2^31 cells");
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    if (ncell > 0 && (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge))
+        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    const int np = n_occ + n_free;
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as lookup_cell_fast forms it
+    double far = 0.0;
+    for (int k = 0; k < np; ++k) {
+        const double* q = k < n_occ ? occ_xy + 2 * (size_t)k : free_xy + 2 * (size_t)(k - n_occ);
+        if (!std::isfinite(q[0]) || !std::isfinite(q[1])) return fail(h, RBPF_EINVAL, "point coordinates must be finite");
+        far = std::max(far, hypot(q[0], q[1]));
+    }
+    const double reach = ceil(far * inv) + 1.0;                            // no point lands farther from its cell
+    if (!(reach >= 1.0) || reach > 16384.0) return fail(h, RBPF_EINVAL, "the point set reaches more than 16383 cells from its origin");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "alignment between rbpf_scan_update_begin and rbpf_scan_update_end");
+    if (ncell == 0) return RBPF_OK;
+    LocateArgs f;                                                          // the field: locate's, over the box grown by M
+    AlignArgs a;
+    f.particle = particle; a.x0 = f.x0 = box4[0]; a.y0 = f.y0 = box4[2]; a.nx = f.nx = (int)nx; a.ny = f.ny = (int)ny;
+    a.nyw = f.nyw = (int)((ny + 31) / 32); a.M = f.M = (int)reach;
+    f.rows = a.nx + 2 * a.M; a.W = f.W = a.nyw + ((2 * a.M) >> 5) + 2;
+    a.n_rot = n_rot; a.r_begin = r_begin; a.r_count = r_count; a.n_occ = n_occ; a.np = np; a.inv = inv;
+    // enough workgroups to fill the GPU: the window is cut into runs of rotations when the box has few words
+    const long long words = nx * a.nyw, word_waves = (words + 63) / 64;
+    const long long runs = std::max(1LL, std::min<long long>(r_count, (8192 + word_waves - 1) / word_waves));
+    a.rpw = (int)((r_count + runs - 1) / runs);
+    const bool dev_out = (flags & RBPF_ALIGN_DEVICE_OUT) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t in_b = ((size_t)r_count + np) * 16, offs_b = pad((size_t)r_count * np * 4), field_b = pad((size_t)f.rows * f.W * 8);
+    const size_t packed_b = pad((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 8;
+    const size_t total = pad(in_b) + offs_b + field_b + packed_b + out_b;
+    if (total > ((size_t)2 << 30)) return fail(h, RBPF_ENOMEM, "box, points and rotations need more than 2 GiB of scratch: search a smaller box or window");
+    HIP_TRY(h, h->reserve(B_ALIGN, total));
+    const Block& d = h->buf[B_ALIGN];
+    HIP_TRY(h, h->stage[S_ALIGN].begin(in_b));                             // the last upload may still read it
+    double* st = reinterpret_cast<double*>(h->stage[S_ALIGN].p);
+    for (int q = 0; q < r_count; ++q) {                                    // host libm: the device never sees an angle
+        const double th = ((double)(r_begin + q) * 6.283185307179586) / (double)n_rot;
+        st[2 * q] = cos(th); st[2 * q + 1] = sin(th);
+    }
+    double* sp = st + 2 * (size_t)r_count;
+    memcpy(sp, occ_xy, (size_t)n_occ * 16);
+    if (n_free > 0) memcpy(sp + 2 * (size_t)n_occ, free_xy, (size_t)n_free * 16);
+    HIP_TRY(h, h->stage[S_ALIGN].upload(d.p, in_b, h->stream));
+    size_t at = pad(in_b);
+    a.cs = d.as<const double>(); a.pxy = a.cs + 2 * (size_t)r_count;
+    a.offs = d.as<int32_t>(at); at += offs_b;
+    a.field = f.field = d.as<uint2>(at); at += field_b;
+    a.packed = d.as<uint32_t>(at);
+    HIP_TRY(h, hipMemsetAsync(a.packed, 0, packed_b, h->stream));          // the merge raster
+    at += packed_b;
+    a.best = dev_out ? best : d.as<int32_t>(at);
+    a.rot = dev_out ? rot : d.as<int32_t>(at + (size_t)ncell * 4);
+    launch_align_points(v, f, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(best, a.best, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(rot, a.rot, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

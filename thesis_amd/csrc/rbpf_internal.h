@@ -175,6 +175,23 @@ struct LocateArgs {
     uint32_t* packed;                  // [nx][ny] max over rotations of score << 16 | (n_rot - 1 - r), preset to 0
     int32_t *best, *rot;               // [nx][ny] outputs; rot may be null
 };
+// alignment of a point set (kernels_align.hip): occupied and free points against one particle's map over a box of cells and a
+// window of rotations.  The field is locate's: a LocateArgs with particle, x0, y0, M, rows, W and field set describes it
+struct AlignArgs {
+    int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
+    int nyw;                           // words per box row = ceil(ny / 32)
+    int M;                             // largest point offset in cells: the field is the box grown by M on every side
+    int W;                             // {occ, dil} word pairs per field row (nyw + (2 M >> 5) + 2)
+    int n_rot, r_begin, r_count, rpw;  // rotations of the full turn, the window searched, rotations per workgroup
+    int n_occ, np;                     // occupied points; all points (the free ones follow the occupied ones)
+    double inv;                        // cells per metre (dim / tile_len)
+    const double* cs;                  // [r_count][2] cos, sin of theta_r, r = r_begin .. (host libm)
+    const double* pxy;                 // [np][2] the points, metres, frame of the point set
+    int32_t* offs;                     // [r_count][np] u << 16 | (M + w): offset in rows, and in bits of a field row
+    const uint2* field;                // [nx + 2 M][W]
+    uint32_t* packed;                  // [nx][ny] max over rotations of biased score << 16 | (n_rot - 1 - r), preset to 0
+    int32_t *best, *rot;               // [nx][ny] outputs; rot may be null
+};
 
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
@@ -235,4 +252,6 @@ void launch_place_warp(const PlaceArgs& q, hipStream_t s);                      
 void launch_place_map(const DevView& v, const LoadArgs& a, const PlaceArgs& q, int n_jobs, hipStream_t s);   // tile allocation, then the merge
 void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
+void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
+void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
 }  // namespace rbpf

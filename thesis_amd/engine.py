@@ -652,6 +652,76 @@ class ParticleEngine:
         self.set_state(poses=locate.seed_particles(hyp, self.P, cell, n_rot, seed), covs=0.0, weights=1.0)
         return hyp
 
+    # -- alignment of a map of unknown pose (include/rbpf_hip.h: rbpf_align_points; thesis_amd/align.py) --------
+    def align_points(self, occ_xy, free_xy=None, particle="best", box=None, n_rot: int = 720, rot_window=None,
+                     device: bool = False):
+        """Scores a point set of unknown pose - `occ_xy` [n, 2] occupied and `free_xy` [m, 2] free points, metres in a frame
+        of their own - at every cell of `box` = (x0, x1, y0, y1) in mosaic cells (default map_extent(particle)) and every
+        rotation of `rot_window` = (r_begin, r_count) out of `n_rot` (default all) in a particle's map: `particle` an index
+        or "best" (the first argmax of weights()).  score = sum of F over the occupied points - 2 * the free points that land
+        on an occupied cell.  Returns (best, rot, box): int32 [x1-x0, y1-y0] rasters of the best score per
+        cell and the smallest rotation index of the window that attains it.  device=True: torch tensors on the engine's
+        device, ready for work on torch's current stream."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = int(particle)
+        o = _f64(occ_xy)
+        f = _f64(np.empty((0, 2)) if free_xy is None else free_xy)
+        if o.ndim != 2 or o.shape[1] != 2 or f.ndim != 2 or f.shape[1] != 2:
+            raise ValueError("occ_xy and free_xy must be [n, 2]")
+        if box is None:
+            box = self.map_extent(p) or (0, 0, 0, 0)
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        r_begin, r_count = (0, int(n_rot)) if rot_window is None else (int(rot_window[0]), int(rot_window[1]))
+        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            best = torch.empty(shape, dtype=torch.int32, device=dev)
+            rot = torch.empty(shape, dtype=torch.int32, device=dev)
+            ptrs = [C.c_void_p(best.data_ptr() or 1), C.c_void_p(rot.data_ptr() or 1)]   # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            best, rot = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
+            ptrs = [C.c_void_p(best.ctypes.data or 1), C.c_void_p(rot.ctypes.data or 1)]
+        self._check(self._lib.rbpf_align_points(self._h, p, _ip(b), _dp(o), o.shape[0], _dp(f) if f.shape[0] else None, f.shape[0],
+                                                int(n_rot), r_begin, r_count, _lib.RBPF_ALIGN_DEVICE_OUT if device else 0, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        return best, rot, tuple(int(x) for x in b)
+
+    def align_map(self, src, particle="best", k: int = 4, n_rot: int = 360, refine: int = 8, box=None):
+        """Finds where the map `src` (a mapio.SourceMap whose frame is unknown) fits a particle's map: its occupied and free
+        cells become a point set (align.points_from_source), a coarse align_points pass over `box` (default
+        map_extent(particle)) at `n_rot` rotations gives up to `k` hypotheses, and a fine pass at n_rot * refine rotations
+        (one coarse step either way, 5 x 5 cells) sharpens each.  Returns locate.Hypotheses, best first: poses[n] is the
+        rigid transform for src.moved, e.g. place_map(src.moved(hyp.poses[0]), mode="add")."""
+        from . import align
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = int(particle)
+        if box is None:
+            box = self.map_extent(p)
+            if box is None:
+                raise ValueError("the particle's map is empty: nothing to align to")
+        lo = -int(self.cfg.lattice_radius) * self.dim - self.dim // 2
+        limits = (lo, lo + (2 * int(self.cfg.lattice_radius) + 1) * self.dim)
+
+        def search(occ_xy, free_xy, bx, nr, r_begin, r_count):
+            return self.align_points(occ_xy, free_xy, particle=p, box=bx, n_rot=nr, rot_window=(r_begin, r_count))[:2]
+        return align.align_map(search, src, float(self.cfg.occupied_threshold), float(self.cfg.tile_len_m) / self.dim, box, limits,
+                               k=k, n_rot=n_rot, refine=refine)
+
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)
         vals = np.empty(len(pts))
