@@ -425,6 +425,36 @@ int  rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, co
                        const double* free_xy, int32_t n_free, int32_t n_rot, int32_t r_begin, int32_t r_count, uint32_t flags,
                        int32_t* best, int32_t* rot);
 
+/* ---- view gain: which map cells would a scan taken at a pose observe? ----------------------------------------------------
+ * For each pose (x, y, theta) the rays are exactly those of rbpf_cast_scans (same host libm cos / sin of theta and of each angle,
+ * same float64 walk, inv and tlim = max_range * inv, same tie rule and the same strict "occupied" test).  The
+ * visited set V of a pose in a map is the set of DISTINCT mosaic cells that the walk of any of its beams tests while inside the
+ * lattice: the origin cell, every cell entered with t <= tlim, and the hit cell that ends a ray (an occupied cell that is seen
+ * is observed); nothing behind a hit, nothing outside the lattice; V is empty when the origin cell lies outside the lattice.
+ * With v(c) the lattice value rbpf_render_map gives for cell c and vmin = min_odds_emp / quantum:
+ *   seen    = |V|
+ *   unknown = #{c in V : v(c) == 0}
+ *   gain    = sum over c in V of value_tab[v(c) - vmin]
+ * value_tab has (max_odds_occ - min_odds_emp) / quantum + 1 entries (61 with the defaults), each in 0 .. 2^20.  All three are
+ * exact integers: the result does not depend on any summation order and is bit-identical from call to call.  DESIGN.md 3.11
+ * has the kernel.
+ * particle >= 0: outputs are [n_poses], every pose in that particle's map.  particle == -1: outputs are [P][n_poses], EVERY
+ * pose in EVERY particle's map (what an expectation over the posterior needs) - unlike rbpf_cast_scans, which pairs pose n
+ * with particle n.  seen and unknown may each be NULL.
+ * Window limit: with M = ceil(max_range * inv) + 2 every visited cell lies within M cells of the origin cell on each axis, and
+ * the kernel keeps the (2M + 1)^2 window as a bitmap in one workgroup's LDS: 2M + 1 <= 1024 is required (max_range up to about
+ * 25.4 m at 0.05 m cells, 12.7 m at 0.025 m, 50.9 m at 0.1 m), otherwise RBPF_EINVAL; the message gives the largest admissible
+ * max_range.
+ * A NULL poses_n3, angles, value_tab or gain, a non-finite pose or angle, max_range not finite or not > 0, n_beams < 1,
+ * n_poses < 1, n_poses * n_beams >= 2^31, a table entry out of range, a bad particle or an unknown flag is RBPF_EINVAL; a call
+ * between rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked before anything is queued, and nothing is written.
+ * The call changes no engine state (maps, particles, random streams, counters, duplicate grouping).  It runs on the handle's
+ * stream; without RBPF_GAIN_DEVICE_OUT the outputs are host arrays, complete on return. */
+#define RBPF_GAIN_DEVICE_OUT 1u    /* gain / seen / unknown are device pointers, written in stream order, no host wait */
+int  rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* angles,
+                    int32_t n_beams, double max_range, const int32_t* value_tab, uint32_t flags, int64_t* gain, int32_t* seen,
+                    int32_t* unknown);
+
 #ifdef __cplusplus
 }
 #endif

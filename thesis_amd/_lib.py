@@ -18,6 +18,7 @@ RBPF_LOAD_DEVICE_IN = 1
 RBPF_CAST_DEVICE_OUT = 1
 RBPF_LOCATE_DEVICE_OUT = 1
 RBPF_ALIGN_DEVICE_OUT = 1
+RBPF_GAIN_DEVICE_OUT = 1
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -122,6 +123,8 @@ PROTOTYPES = {
     "rbpf_locate_scan": (C.c_int, [_H, C.c_int32, _I, _D, _D, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_align_points": (C.c_int, [_H, C.c_int32, _I, _D, C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                           C.c_void_p, C.c_void_p]),
+    "rbpf_view_gain": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, _I, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
 }
 
 _lib = None

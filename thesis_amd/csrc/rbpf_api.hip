@@ -1765,4 +1765,69 @@ int rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, con
     return RBPF_OK;
 }
 
+// ---- view gain (kernels_gain.hip) ---------------------------------------------------------------------------------------------
+int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* angles,
+                   int32_t n_beams, double max_range, const int32_t* value_tab, uint32_t flags, int64_t* gain, int32_t* seen,
+                   int32_t* unknown) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!poses_n3 || !angles || !value_tab || !gain) return fail(h, RBPF_EINVAL, "poses, angles, value_tab or gain is NULL");
+    if (flags & ~RBPF_GAIN_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (n_poses < 1 || n_beams < 1 || (long long)n_poses * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_poses >= 1, n_beams >= 1 and n_poses * n_beams < 2^31 are required");
+    const long long results = (long long)(particle >= 0 ? 1 : v.P) * n_poses;
+    if (results >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_particles * n_poses < 2^31 is required with particle -1");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    for (long long k = 0; k < 3LL * n_poses; ++k)
+        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    const int nv = v.cc.vmax - v.cc.vmin + 1;                              // one entry per lattice value
+    if (v.cc.vmin > 0 || v.cc.vmax < 0 || nv > 256) return fail(h, RBPF_EINVAL, "the lattice values must include 0");
+    for (int k = 0; k < nv; ++k)
+        if (value_tab[k] < 0 || value_tab[k] > (1 << 20)) return fail(h, RBPF_EINVAL, "value_tab entries must lie in 0 .. 2^20");
+    GainArgs a;
+    a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as rbpf_cast_scans forms it
+    a.tlim = max_range * a.inv;
+    const double reach = ceil(a.tlim) + 2.0;                               // no tested cell lies farther from the origin cell on either axis
+    if (!(2.0 * reach + 1.0 <= 1024.0))
+        return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window of more than 1024 cells: the largest admissible "
+                                    "max_range is " + std::to_string(509.0 / a.inv) + " m (ceil(max_range * cells per metre) <= 509)");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "view gain between rbpf_scan_update_begin and rbpf_scan_update_end");
+    a.M = (int)reach; a.W = (2 * a.M + 1 + 31) / 32 + 1;
+    const bool dev_out = (flags & RBPF_GAIN_DEVICE_OUT) != 0;
+    const size_t nres = (size_t)results;
+    const size_t in_b = (size_t)n_poses * 32 + (size_t)n_beams * 16 + (size_t)nv * 4, out_at = (in_b + 7) & ~(size_t)7;
+    const size_t out_b = dev_out ? 0 : nres * (8 + (seen ? 4 : 0) + (unknown ? 4 : 0));
+    HIP_TRY(h, h->reserve(B_GAIN, out_at + out_b));
+    const Block& d = h->buf[B_GAIN];
+    HIP_TRY(h, h->stage[S_GAIN].begin(in_b));                              // the last upload may still read it
+    double* st = reinterpret_cast<double*>(h->stage[S_GAIN].p);
+    for (int n = 0; n < n_poses; ++n) {                                    // host libm, as rbpf_cast_scans
+        st[4 * (size_t)n] = poses_n3[3 * (size_t)n]; st[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
+        st[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); st[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
+    }
+    double* sb = st + 4 * (size_t)n_poses;
+    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    memcpy(sb + 2 * (size_t)n_beams, value_tab, (size_t)nv * 4);
+    HIP_TRY(h, h->stage[S_GAIN].upload(d.p, in_b, h->stream));
+    a.pose4 = d.as<const double>();
+    a.beam2 = a.pose4 + 4 * (size_t)n_poses;
+    a.table = reinterpret_cast<const int32_t*>(a.beam2 + 2 * (size_t)n_beams);
+    a.n_poses = n_poses; a.B = n_beams; a.nv = nv; a.particle = particle;
+    a.gain = dev_out ? gain : d.as<int64_t>(out_at);
+    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(out_at + nres * 8);
+    a.unknown = !unknown ? nullptr : dev_out ? unknown : d.as<int32_t>(out_at + nres * (8 + (seen ? 4 : 0)));
+    launch_view_gain(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(gain, a.gain, nres * 8, hipMemcpyDeviceToHost, h->stream));
+    if (seen) HIP_TRY(h, hipMemcpyAsync(seen, a.seen, nres * 4, hipMemcpyDeviceToHost, h->stream));
+    if (unknown) HIP_TRY(h, hipMemcpyAsync(unknown, a.unknown, nres * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

@@ -157,6 +157,18 @@ struct CastArgs {
     double inv, tlim, max_range;       // cells per metre (dim / tile_len), max_range * inv, max_range
     double* ranges; uint8_t* status;   // [n_poses][B]; status may be null
 };
+// view gain (kernels_gain.hip): the set of cells the beams of a pose test, reduced against a particle's map; one
+// workgroup per (particle, pose), result r = particle * n_poses + pose (particle counted from 0 only when every particle is asked for)
+struct GainArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
+    const double* beam2;               // [B][2] cos(angle), sin(angle)
+    const int32_t* table;              // [nv] value of a seen cell by its lattice value: table[v - vmin]
+    int n_poses, B, nv;
+    int particle;                      // >= 0: every pose in this particle's map; -1: every pose in every particle's map
+    int M, W;                          // window half-width in cells: ceil(max_range * inv) + 2; words per bitmap row
+    double inv, tlim;                  // cells per metre (dim / tile_len), max_range * inv
+    int64_t* gain; int32_t *seen, *unknown;   // [particles][n_poses]; seen and unknown may be null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -251,6 +263,8 @@ void launch_load_alloc(const DevView& v, const LoadArgs& a, hipStream_t s);     
 void launch_place_warp(const PlaceArgs& q, hipStream_t s);                              // warped / covered rasters of the box
 void launch_place_map(const DevView& v, const LoadArgs& a, const PlaceArgs& q, int n_jobs, hipStream_t s);   // tile allocation, then the merge
 void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
+size_t view_gain_lds_bytes(int M, int W);
+void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

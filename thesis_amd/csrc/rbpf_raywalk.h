@@ -1,0 +1,65 @@
+// rbpf_raywalk.h -- the supercover (4-connected) ray walk of DESIGN 3.7 against the occupancy bit planes: one copy of the
+// arithmetic for every kernel that walks it (kernels_cast.hip, kernels_gain.hip).
+//
+// The walk is float64: the crossing parameters are (n + f) * td, functions of the step counts alone, so every lane reproduces
+// the specification's values whatever its neighbours do.  A ray tests occ[tile][row][col >> 5], bit col & 31 (cell > threshold,
+// zero outside a tile's written box like the cells themselves), 32 cells per 4-byte load.  The current word stays in a register
+// and is loaded again only when (tile, row, col >> 5) changes.  The position is kept as (lattice tile, tile-local cell) per axis
+// and stepped by +-1 with a wrap at the seam, so the loop has no division and the tile table is read only at a seam (and once
+// at the start).  Every step moves one cell away from the origin along one axis, so a ray ends after at most 2 * L * dim steps
+// (it has left the lattice by then).
+#pragma once
+#include "rbpf_internal.h"
+
+namespace rbpf {
+
+// ps = x, y, cos(theta), sin(theta); bm = cos(angle), sin(angle); tab = the particle's row of the tile table.  Returns the
+// status of rbpf_cast_scans (1 hit, 0 nothing occupied within tlim, 2 the ray or its origin left the lattice); t is the
+// parameter (cells) at which the last tested cell was entered.  visit(kx, ky) is called for every cell the loop tests while
+// inside the lattice, the hit cell included: (kx, ky) = its offset from the origin cell, in cells.
+template <class Visit>
+__device__ __forceinline__ int walk_ray(const DevView& v, const int32_t* __restrict__ tab, const double4 ps, const double2 bm,
+                                        const double inv, const double tlim, double& t, Visit&& visit) {
+    const int L = v.L, dim = v.dim, ow = v.ow;
+    const double ox = ps.x * inv, oy = ps.y * inv;                        // origin in mosaic-cell units
+    const double dx = ps.z * bm.x - ps.w * bm.y, dy = ps.w * bm.x + ps.z * bm.y;
+    const double fX = __builtin_floor(ox), fY = __builtin_floor(oy);
+    const int off = v.R * dim + dim / 2;                                  // mosaic X + off = tile * dim + cell
+    const double lo = -(double)off, hi = (double)(L * dim - off);
+    t = 0.0;
+    if (!(fX >= lo && fX < hi && fY >= lo && fY < hi)) return 2;          // (a NaN as well)
+    const int u = (int)fX + off, w = (int)fY + off;
+    int ta = u / dim, i = u - ta * dim, tb = w / dim, j = w - tb * dim;
+    const int sx = dx > 0 ? 1 : -1, sy = dy > 0 ? 1 : -1;
+    const double inf = __builtin_inf();
+    // a ray along an axis never crosses the other one: (n + 1) * inf = inf stands for the specification's "inf"
+    const double tdx = dx != 0 ? 1.0 / __builtin_fabs(dx) : inf, tdy = dy != 0 ? 1.0 / __builtin_fabs(dy) : inf;
+    const double fx = dx != 0 ? (dx > 0 ? (fX + 1.0) - ox : ox - fX) : 1.0;
+    const double fy = dy != 0 ? (dy > 0 ? (fY + 1.0) - oy : oy - fY) : 1.0;
+    double nx = 0.0, ny = 0.0;                                            // step counts (exact in float64)
+    int kx = 0, ky = 0;
+    int cur_pos = -1, cur_w = -1, tile = -1;
+    uint32_t word = 0u;
+    for (;;) {
+        if ((unsigned)ta >= (unsigned)L || (unsigned)tb >= (unsigned)L) return 2;           // left the lattice
+        visit(kx, ky);
+        const int pos = ta * L + tb, wi = i * ow + (j >> 5);
+        if (pos != cur_pos) { tile = tab[pos]; cur_pos = pos; cur_w = -1; }
+        if (wi != cur_w) {
+            word = tile >= 0 ? v.occ[(size_t)tile * dim * ow + (size_t)wi] : 0u;              // no tile: free
+            cur_w = wi;
+        }
+        if ((word >> (j & 31)) & 1u) return 1;
+        const double tmx = (nx + fx) * tdx, tmy = (ny + fy) * tdy;
+        const bool step_x = tmx < tmy;                                    // a tie steps in y
+        t = step_x ? tmx : tmy;
+        nx += step_x ? 1.0 : 0.0; ny += step_x ? 0.0 : 1.0;
+        i += step_x ? sx : 0; j += step_x ? 0 : sy;
+        kx += step_x ? sx : 0; ky += step_x ? 0 : sy;
+        if (i == dim) { i = 0; ++ta; } else if (i < 0) { i = dim - 1; --ta; }
+        if (j == dim) { j = 0; ++tb; } else if (j < 0) { j = dim - 1; --tb; }
+        if (t > tlim) return 0;
+    }
+}
+
+}  // namespace rbpf

@@ -10,7 +10,7 @@ import atexit
 import ctypes as C
 import sys
 import weakref
-from typing import Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -30,6 +30,13 @@ def _ip(a: np.ndarray):
 
 def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class ViewGain(NamedTuple):
+    """ParticleEngine.view_gain: per pose [N], or per particle and pose [P, N] (numpy arrays, or torch tensors on the GPU)."""
+    gain: Any        # int64: sum of table[v - vmin] over the distinct cells a scan there would observe
+    seen: Any        # int32: how many cells that is
+    unknown: Any     # int32: how many of them have the lattice value 0
 
 
 class RbpfError(RuntimeError):
@@ -593,6 +600,55 @@ class ParticleEngine:
         if device and not same_stream:
             self.synchronize()
         return (r, st) if return_status else r
+
+    # -- view gain (include/rbpf_hip.h: rbpf_view_gain; thesis_amd/explore.py) ---------------------------------
+    def view_gain(self, poses, angles, particle="best", max_range: Optional[float] = None, table=None, device: bool = False):
+        """What a scan with beam directions `angles` [B] taken at `poses` [N, 3] (or [3]) would observe in a particle's map:
+        the set of distinct cells its rays test (the rays of cast_scans), reduced against the map.  `particle`: an index,
+        "best" (the first argmax of weights()), or None: every pose in EVERY particle's map.  Returns ViewGain(gain int64,
+        seen int32, unknown int32), each [N], or [P, N] for particle=None: the number of cells seen, how many of them are
+        unknown (lattice value 0), and the sum of table[v - vmin] over them.  `max_range` defaults to cfg.max_ray_m, the
+        range the map update draws; `table` (one int in 0 .. 2^20 per lattice value) to explore.entropy_table(cfg), with
+        which gain / 65536 reads as bits.  device=True: torch tensors on the engine's device, ready for work on torch's
+        current stream."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        ps = _f64(poses)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        a = _f64(angles)
+        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1:
+            raise ValueError("poses must be [N, 3] (or [3]) and angles 1-D")
+        if table is None:
+            from .explore import entropy_table
+            table = entropy_table(self.cfg)
+        tab = np.ascontiguousarray(table, dtype=np.int32)
+        nv = int(round((float(self.cfg.max_odds_occ) - float(self.cfg.min_odds_emp)) / float(self.cfg.quantum))) + 1
+        if tab.shape != (nv,):
+            raise ValueError(f"table must have {nv} entries, one per lattice value")
+        shape = (ps.shape[0],) if p >= 0 else (self.P, ps.shape[0])
+        mr = float(self.cfg.max_ray_m if max_range is None else max_range)
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [torch.empty(shape, dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32)]
+            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            outs = [np.empty(shape, dtype=d) for d in (np.int64, np.int32, np.int32)]
+            ptrs = [C.c_void_p(o.ctypes.data) for o in outs]
+        self._check(self._lib.rbpf_view_gain(self._h, p, _dp(ps), ps.shape[0], _dp(a), a.shape[0], mr, _ip(tab),
+                                             _lib.RBPF_GAIN_DEVICE_OUT if device else 0, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        return ViewGain(*outs)
 
     # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
     def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):

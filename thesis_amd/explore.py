@@ -1,0 +1,91 @@
+"""Where should the robot look next?  Candidate view poses on the frontier of a map, ranked by the map cells a scan taken
+there would observe (ParticleEngine.view_gain; include/rbpf_hip.h, rbpf_view_gain).  Host side, NumPy only:
+the GPU call is the work, this module turns a map into candidates and the gains into a ranking."""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+
+def entropy_table(cfg) -> np.ndarray:
+    """int32 table over the lattice values vmin .. vmax (61 with the default constants): round(65536 H2(sigma(|v| quantum))),
+    H2 the binary entropy in bits, sigma(o) = e^o / (1 + e^o) as in rbpf_render_map.  H2(sigma(o)) is even in o, so the table
+    is formed from |v| and is symmetric to the last bit; v = 0 gives 65536, so view_gain's gain / 65536 reads as bits."""
+    q = float(cfg.quantum)
+    vmin, vmax = int(round(float(cfg.min_odds_emp) / q)), int(round(float(cfg.max_odds_occ) / q))
+    out = np.empty(vmax - vmin + 1, np.int32)
+    for v in range(vmin, vmax + 1):
+        e = math.exp(abs(v) * q)
+        p, r = e / (1.0 + e), 1.0 / (1.0 + e)
+        out[v - vmin] = int(round(65536.0 * -(p * math.log2(p) + r * math.log2(r))))
+    return out
+
+
+def frontier_cells(raster) -> np.ndarray:
+    """[n, 2] mosaic cells (X, Y), in row-major order, of the observed-free cells (v < 0) of a particle's raster
+    (ParticleEngine.render_map) that have a 4-neighbour with v == 0.  Cells outside the raster are 0, as in the map."""
+    c = np.pad(np.asarray(raster.cells), 1)
+    unknown = c == 0
+    near = unknown[:-2, 1:-1] | unknown[2:, 1:-1] | unknown[1:-1, :-2] | unknown[1:-1, 2:]
+    ij = np.argwhere((c[1:-1, 1:-1] < 0) & near)
+    return ij + np.array([int(raster.x0), int(raster.y0)])
+
+
+def candidate_poses(raster, spacing_m: float = 1.0, n_headings: int = 8, clearance_cells: int = 4,
+                    occupied_threshold: float = 1.0) -> np.ndarray:
+    """[n, 3] view poses (x, y, theta) from a particle's raster: the frontier cells with no occupied cell
+    (v quantum > occupied_threshold) within `clearance_cells` on either axis, thinned to the first one (row-major) of every
+    `spacing_m` square, each at its cell centre and once per heading 2 pi k / n_headings."""
+    cells = np.asarray(raster.cells)
+    cell = float(raster.tile_len) / int(raster.dim)
+    f = frontier_cells(raster)
+    k = int(clearance_cells)
+    occ = np.pad(cells * float(raster.quantum) > occupied_threshold, k)
+    blocked = np.zeros(cells.shape, bool)
+    for di in range(2 * k + 1):
+        for dj in range(2 * k + 1):
+            blocked |= occ[di:di + cells.shape[0], dj:dj + cells.shape[1]]
+    f = f[~blocked[f[:, 0] - int(raster.x0), f[:, 1] - int(raster.y0)]]
+    square = np.floor((f + 0.5) * cell / float(spacing_m)).astype(np.int64)
+    _, first = np.unique(square, axis=0, return_index=True)
+    xy = (f[np.sort(first)] + 0.5) * cell
+    th = 2.0 * np.pi * np.arange(int(n_headings)) / int(n_headings)
+    return np.concatenate([np.repeat(xy, len(th), axis=0), np.tile(th, len(xy))[:, None]], axis=1).reshape(-1, 3)
+
+
+class NextViews(NamedTuple):
+    poses: np.ndarray       # [k, 3] the best view poses, best first
+    scores: np.ndarray      # [k] float64: expected gain in table units / 65536 (bits with the entropy table)
+    order: np.ndarray       # [k] their indices among the candidates
+    candidates: np.ndarray  # [n, 3] every candidate scored
+    gain: np.ndarray        # view_gain's gain for them: [n], or [P, n] with particle=None
+
+
+def rank(gain, weights=None, k: int = 8):
+    """(order [k], scores [n]): scores = gain / 65536, for a [P, n] gain its weighted mean over the particles (uniform by
+    default); order = the k best candidates, ties to the lower index."""
+    g = np.asarray(gain, dtype=np.float64)
+    if g.ndim == 2:
+        w = np.ones(g.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64)
+        g = (w[:, None] * g).sum(axis=0) / w.sum()
+    scores = g / 65536.0
+    return np.argsort(-scores, kind="stable")[:int(k)], scores
+
+
+def next_view(engine, angles, particle="best", weights=None, k: int = 8, spacing_m: float = 1.0, n_headings: int = 8,
+              clearance_cells: int = 4, max_range: Optional[float] = None, table=None) -> NextViews:
+    """The k candidate poses whose scan would observe the most: candidates from the map of `particle` (an index or "best";
+    with None the best particle's map), scored by view_gain in that map, or with particle=None in every particle's map and
+    averaged with `weights` (uniform by default)."""
+    if isinstance(particle, str) and particle != "best":
+        raise ValueError(f"unknown particle {particle!r}")
+    best = int(np.argmax(engine.weights()))
+    src = best if particle is None or isinstance(particle, str) else int(particle)
+    cand = candidate_poses(engine.render_map(src), spacing_m, n_headings, clearance_cells, float(engine.cfg.occupied_threshold))
+    if len(cand) == 0:
+        raise ValueError("the map has no frontier cell with that clearance: nowhere to look")
+    res = engine.view_gain(cand, angles, particle=None if particle is None else src, max_range=max_range, table=table)
+    order, scores = rank(res.gain, weights, k)
+    return NextViews(cand[order], scores[order], order, cand, res.gain)
