@@ -187,6 +187,20 @@ int  rbpf_import_last_scan(rbpf_handle* h, const void* d_xy, int32_t n_points);
 int  rbpf_scan_update_begin(rbpf_handle* h, int32_t adj, const double* last_scan_xy, int32_t n_last,
                             const double* match_override, const double* guesses);
 int  rbpf_scan_update_end(rbpf_handle* h);
+/* Read-out of the proposal of the last rbpf_scan_update_begin / rbpf_scan_update (test / inspection entry).
+ * rbpf_set_proposal_capture(on != 0): the following scan updates also keep every sample's raw weight w_k (robot.py:138,
+ * before the shift of robot.py:96) in a [P][K] buffer allocated on first use.  Off by default, and then the launches are
+ * exactly those of a handle that never heard of it.
+ * rbpf_get_proposal copies out, for one particle (any output may be NULL):
+ *   frame24    [24]   U[9] (row-major, pseudo-inverse square root: maha = |(g - mean) U|^2), A[9] (row-major sampling
+ *                     matrix: g = mean + A z), mean[3], log c, bad flag (1 = NaN / indefinite covariance: no proposal, the
+ *                     rest of the read-out is then whatever an earlier step left), one unused
+ *   samples    [K][6] x, y, theta, cos theta, sin theta, motion probability (pdf * 10)
+ *   frame_f32  [K][4] the single-precision look-up frame: cos / cell, sin / cell, x / cell + off_x, y / cell + off_y
+ *   raw_w      [K]    the captured w_k; RBPF_ESTATE unless capture was on during that scan update
+ * RBPF_ESTATE before the first scan update. */
+int  rbpf_set_proposal_capture(rbpf_handle* h, int32_t on);
+int  rbpf_get_proposal(rbpf_handle* h, int32_t particle, double* frame24, double* samples, float* frame_f32, double* raw_w);
 
 /* ---- a6/a7: scan matcher, stateless twin of the engine seam (hybridmap.py:244-251) ------------ */
 int  rbpf_match_scan(rbpf_handle* h, const double* curr_xy, int32_t n_curr, const double* ref_xy,

@@ -83,6 +83,8 @@ PROTOTYPES = {
     "rbpf_import_last_scan": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "rbpf_scan_update_begin": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _D]),
     "rbpf_scan_update_end": (C.c_int, [_H]),
+    "rbpf_set_proposal_capture": (C.c_int, [_H, C.c_int32]),
+    "rbpf_get_proposal": (C.c_int, [_H, C.c_int32, _D, _D, C.POINTER(C.c_float), _D]),
     "rbpf_match_scan": (C.c_int, [_H, _D, C.c_int32, _D, C.c_int32, _D, C.c_int32, _D, _D, _D, _D]),
     "rbpf_match_inputs": (C.c_int, [_H, C.c_int32, _D, _D, _I, _D, _I, C.c_int32]),
     "rbpf_match_results": (C.c_int, [_H, _D]),

@@ -8,7 +8,7 @@
 //
 // One 256-thread workgroup per particle; the K sample poses live in LDS, the per-sample lattice sums
 // are exact integers, the moments are a K-term sequential float64 loop in the reference's order.
-// A particle whose matcher covariance holds a NaN takes the reference's fallback (robot.py:73-78):
+// A particle whose matcher covariance holds a NaN, or has an eigenvalue below -eps, takes the reference's fallback (robot.py:73-78):
 // its pose is kept, its map is updated at that pose and its weight is incremented AFTER the map
 // update by bad_weight_kernel.
 #include "rbpf_internal.h"
@@ -115,6 +115,7 @@ __global__ __launch_bounds__(64) void propose_prep_kernel(DevView v, ProposeArgs
     double log_pdet = 0.0; int rank = 0;
     for (int j = 0; j < 3; ++j) {
         bool keep = w[j] > eps;
+        if (!keep && fabs(w[j]) > eps) { a.bad[p] = 1; o[22] = 1.0; return; }   // an eigenvalue below -eps: indefinite (scipy raises) - the NaN branch, the state stays finite
         double inv_sqrt = fabs(w[j]) > eps ? sqrt(1.0 / w[j]) : 0.0;
         if (keep) { log_pdet += log(w[j]); ++rank; }
         double sq = w[j] > 0 ? sqrt(w[j]) : 0.0;

@@ -614,7 +614,9 @@ int rbpf_scan_update_begin(rbpf_handle* h, int32_t adj, const double* last_scan_
     // the matcher ran once per group of exact duplicates (copies made by the last resample, untouched since): every
     // member reads its representative's row; the proposal below is what makes the copies differ, so the groups end here
     const int32_t* match_of = (!match_override && v.dups_valid) ? v.dup_of : nullptr;
-    launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, nullptr, h->stream);
+    if (h->prop_capture && !h->d_prop_w) ALLOC(h, h->d_prop_w, P * (size_t)v.K);
+    launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, h->prop_capture ? h->d_prop_w : nullptr, h->stream);
+    h->prop_valid = true; h->prop_captured = h->prop_capture;
     v.dups_valid = 0;
     h->prof_end(1);
     HIP_TRY(h, hipGetLastError());
@@ -642,6 +644,40 @@ int rbpf_scan_update_end(rbpf_handle* h) {
     // HybridMap.update at the new mean pose (robot.py:115), then - in the same launch - the robot.py:73-78 weight
     // increment of the particles on the NaN-covariance branch, on their updated maps
     return run_map_update(h, h->d_bad);
+}
+
+// ---- read-out of the last proposal (tests): the frame propose_prep_kernel left, the samples of propose_samples_kernel,
+//      the raw weights of propose_weight_kernel (ProposeArgs::dbg_w) ------------------------------------------------------
+int rbpf_set_proposal_capture(rbpf_handle* h, int32_t on) {
+    if (!h) return RBPF_EINVAL;
+    h->prop_capture = on != 0;
+    return RBPF_OK;
+}
+
+int rbpf_get_proposal(rbpf_handle* h, int32_t particle, double* frame24, double* samples, float* frame_f32, double* raw_w) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle out of range");
+    if (!h->prop_valid) return fail(h, RBPF_ESTATE, "no scan update has run yet");
+    if (raw_w && !h->prop_captured) return fail(h, RBPF_ESTATE, "the last scan update ran without rbpf_set_proposal_capture");
+    const int K = v.K;
+    double prep[24], samp[256];                          // PREP_W, SAMP_W of kernels_propose.hip
+    std::vector<double> w((size_t)K);
+    HIP_TRY(h, hipMemcpyAsync(prep, v.prop_prep + (size_t)particle * 24, sizeof(prep), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(samp, v.prop_samp + (size_t)particle * 256, sizeof(samp), hipMemcpyDeviceToHost, h->stream));
+    if (raw_w) HIP_TRY(h, hipMemcpyAsync(w.data(), h->d_prop_w + (size_t)particle * K, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (frame24) memcpy(frame24, prep, sizeof(prep));
+    for (int k = 0; k < K; ++k) {
+        if (samples) {
+            double* o = samples + 6 * k;
+            o[0] = samp[64 + k]; o[1] = samp[96 + k]; o[2] = samp[128 + k]; o[3] = samp[k]; o[4] = samp[32 + k]; o[5] = samp[160 + k];
+        }
+        if (frame_f32) memcpy(frame_f32 + 4 * k, reinterpret_cast<const unsigned char*>(samp + 192) + 16 * k, 16);
+        if (raw_w) raw_w[k] = w[k];
+    }
+    return RBPF_OK;
 }
 
 int rbpf_set_map_updates(rbpf_handle* h, int32_t on) {

@@ -169,4 +169,7 @@ struct rbpf_handle {
     rbpf::ResampleBuffers rs;
     rbpf_counters counters;
     unsigned long long scan_updates = 0;
+    // rbpf_set_proposal_capture / rbpf_get_proposal (tests): the raw sample weights of the last proposal, [P][K], allocated on first use
+    bool prop_capture = false, prop_valid = false, prop_captured = false;
+    double* d_prop_w = nullptr;
 };

@@ -39,6 +39,21 @@ class ViewGain(NamedTuple):
     unknown: Any     # int32: how many of them have the lattice value 0
 
 
+class Proposal(NamedTuple):
+    """ParticleEngine.proposal: one particle's proposal frame and its K samples."""
+    U: np.ndarray          # [3, 3] pseudo-inverse square root of the matcher covariance: maha = |(g - mean) U|^2
+    A: np.ndarray          # [3, 3] sampling matrix: g = mean + A z
+    mean: np.ndarray       # [3] the matcher's pose
+    log_c: float           # log of the normalisation: pdf = exp(log_c - maha / 2)
+    bad: bool              # NaN or indefinite covariance: nothing was proposed, the fields below are stale
+    g: np.ndarray          # [K, 3] sample poses
+    cos: np.ndarray        # [K]
+    sin: np.ndarray        # [K]
+    motion_pr: np.ndarray  # [K] pdf * 10 (robot.py:87)
+    frame_f32: np.ndarray  # [K, 4] float32 look-up frame: cos / cell, sin / cell, x / cell + off_x, y / cell + off_y
+    raw_w: Any             # [K] raw sample weights (robot.py:138), or None without capture
+
+
 class RbpfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"librbpf_hip error {code}: {msg}")
@@ -94,6 +109,7 @@ class ParticleEngine:
         self.n_beams = 0
         self._borrowed_stream = False
         self._stream_ptr = None
+        self._capture = False
         _LIVE.add(self)
 
     # -- plumbing ------------------------------------------------------------------------------------
@@ -231,6 +247,23 @@ class ParticleEngine:
     def scan_update_end(self):
         """Second half: the map update at the new mean pose and the NaN branch (robot.py:115, 73-78)."""
         self._check(self._lib.rbpf_scan_update_end(self._h))
+
+    def set_proposal_capture(self, on: bool):
+        """True: the following scan updates keep every sample's raw weight for proposal().  Off by default; changes no result."""
+        self._check(self._lib.rbpf_set_proposal_capture(self._h, int(bool(on))))
+        self._capture = bool(on)
+
+    def proposal(self, particle: int) -> "Proposal":
+        """The proposal of the last scan_update / scan_update_begin for one particle, as the kernels left it.
+        Test/inspection entry; raw_w is None with capture off (turned on only after that update: an RbpfError)."""
+        frame, samp = np.empty(24), np.empty((self.K, 6))
+        f32 = np.empty((self.K, 4), dtype=np.float32)
+        w = np.empty(self.K) if self._capture else None
+        self._check(self._lib.rbpf_get_proposal(self._h, int(particle), _dp(frame), _dp(samp), f32.ctypes.data_as(C.POINTER(C.c_float)),
+                                                None if w is None else _dp(w)))
+        return Proposal(U=frame[0:9].reshape(3, 3).copy(), A=frame[9:18].reshape(3, 3).copy(), mean=frame[18:21].copy(),
+                        log_c=float(frame[21]), bad=bool(frame[22] != 0.0), g=samp[:, 0:3].copy(), cos=samp[:, 3].copy(),
+                        sin=samp[:, 4].copy(), motion_pr=samp[:, 5].copy(), frame_f32=f32, raw_w=w)
 
     def match_inputs(self, particle: int, guess, cap_ref: int = 1 << 16):
         """The (curr, ref) point lists HybridMap.get_scan_match would hand to the matcher (hybridmap.py:210-242)."""
