@@ -469,6 +469,49 @@ int  rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, in
                     int32_t n_beams, double max_range, const int32_t* value_tab, uint32_t flags, int64_t* gain, int32_t* seen,
                     int32_t* unknown);
 
+/* ---- travel cost: can the robot get there, how far is it, and which way? ---------------------------------------------------
+ * Clearance, traversable set and shortest-path cost from a set of start points to every cell of the box box4 = {x0, x1, y0, y1}
+ * (mosaic cells, half-open, raster layout [x1-x0][y1-y0] and v(X, Y) of rbpf_render_map / rbpf_locate_scan: v is 0 without a tile,
+ * outside a tile's written box and outside the lattice) in the map of `particle`.  occ(c) = v(c) * quantum > occupied_threshold,
+ * strict.  A point (x, y) in metres lies in cell (floor(x * inv), floor(y * inv)), inv = dim / tile_len, in float64 as
+ * rbpf_cast_scans forms its origin cell.  All results are integers in chamfer units: an axial step costs 5, a diagonal step 7, so
+ * cost * (tile_len / dim) / 5 is metres.
+ *   d(c)         = min over ALL occupied cells o of the map (outside the box too) of 5 max(|dx|, |dy|) + 2 min(|dx|, |dy|)
+ *   clearance[c] = min(d(c), clear_max).  Only occupied cells count, unknown ones do not.  0 <= inflate < clear_max <= 320; the
+ *                  map is read over the box grown by ceil(clear_max / 5) cells (v = 0 outside the lattice), which is exact.
+ *   blocked(c)   = v(c) >= 0: only known-free cells carry the robot; with RBPF_TRAVEL_THROUGH_UNKNOWN blocked(c) = occ(c)
+ *   T            = {c in box : !blocked(c) and d(c) > inflate}, plus every start cell that lies in the box (the robot is where it
+ *                  is).  Start points outside the box are ignored; if none lies inside, every cost is -1 and the call succeeds.
+ *   cost[c]      = length of the shortest path from any start cell to c over cells of T by steps to the 8 neighbours (5 axial, 7
+ *                  diagonal); the diagonal step (X, Y) -> (X+sx, Y+sy) needs both (X+sx, Y) and (X, Y+sy) in T (no corner is
+ *                  cut).  0 on start cells, -1 where there is no path, so on every cell outside T.  It is the unique least fixed
+ *                  point of the relaxation: independent of evaluation order, identical from call to call.
+ *   goal_cost[g] = cost at the cell of goal g, -1 for a goal outside the box.
+ * The box must hold at least one and at most 2^27 cells (7 * 2^27 fits an int32) and lie in the tile lattice.
+ * particle >= 0: all n_start >= 1 starts are sources in that particle's map; cost (int32 [nx][ny]), clearance (uint16 [nx][ny]) and
+ * goal_cost ([n_goals]) may each be NULL, but not all; goal_cost needs goal_xy and n_goals >= 1 (goal_xy is read only then).
+ * particle == -1: cost and clearance must be NULL; goal_cost is [P][n_goals], EVERY goal in EVERY particle's map (as
+ * rbpf_view_gain); n_start is 1 (the same start in every map) or P (start n in particle n's map, the pairing of rbpf_cast_scans).
+ * The particles are worked on in batches whose scratch stays under 2 GiB; the environment variable RBPF_TRAVEL_BATCH=<n>, read per
+ * call, caps a batch at n particles (for tests).  One particle whose scratch would pass 2 GiB is RBPF_ENOMEM.
+ * rounds (may be NULL) receives the number of relaxation rounds launched, summed over the batches: a diagnostic.  Rounds are
+ * queued several at a time between two reads of their counters, so it is a multiple of that number.  DESIGN.md 3.12 has the kernels.
+ * A NULL box4 or start_xy, a wrong NULL pattern, a non-finite coordinate, a bad particle, count, box, inflate or clear_max, a box
+ * that leaves the lattice or holds more than 2^27 cells, or an unknown flag is RBPF_EINVAL; a call between rbpf_scan_update_begin
+ * and _end is RBPF_ESTATE; all are checked before anything is queued, and nothing is written.  The call changes no engine state
+ * (maps, particles, random streams, counters, duplicate grouping).  It runs on the handle's stream; without
+ * RBPF_TRAVEL_DEVICE_OUT the outputs are host arrays, complete on return; with it the call still waits for its own convergence
+ * reads but not for the outputs.  rounds is complete on return either way. */
+#define RBPF_TRAVEL_DEVICE_OUT      1u   /* cost / clearance / goal_cost are device pointers, stream order, no host wait for them */
+#define RBPF_TRAVEL_THROUGH_UNKNOWN 2u   /* cells that are not known free may be crossed unless occupied */
+int  rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* start_xy, int32_t n_start,
+                      const double* goal_xy, int32_t n_goals, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* cost,
+                      uint16_t* clearance, int32_t* goal_cost, int32_t* rounds);
+/* How the last successful rbpf_travel_cost of this handle went (test / inspection entry): out3 = {relaxation rounds launched,
+ * block runs: (particle, block, round) triples whose workgroup did not leave at once, (particle, block) pairs}.  A sweep of
+ * every block in every round would be out3[0] * out3[2] block runs. */
+int  rbpf_travel_stats(rbpf_handle* h, uint64_t* out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1866,4 +1866,133 @@ int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int
     return RBPF_OK;
 }
 
+// ---- travel cost (kernels_travel.hip) -----------------------------------------------------------------------------------------
+// relaxation rounds queued between two reads of their counters.  A read costs a host wait; a round after convergence costs one
+// launch of workgroups that leave at once.  DESIGN.md 3.12 has the measurement behind the value.
+static const int TRAVEL_ROUNDS_PER_READ = 8;
+
+int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* start_xy, int32_t n_start,
+                     const double* goal_xy, int32_t n_goals, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* cost,
+                     uint16_t* clearance, int32_t* goal_cost, int32_t* rounds) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4 || !start_xy) return fail(h, RBPF_EINVAL, "box4 or start_xy is NULL");
+    if (flags & ~(RBPF_TRAVEL_DEVICE_OUT | RBPF_TRAVEL_THROUGH_UNKNOWN)) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    const bool all = particle < 0;
+    if (all && (cost || clearance)) return fail(h, RBPF_EINVAL, "cost and clearance must be NULL with particle -1");
+    if (!cost && !clearance && !goal_cost) return fail(h, RBPF_EINVAL, "cost, clearance and goal_cost are all NULL");
+    if (n_goals < 0 || (goal_cost && (n_goals < 1 || !goal_xy))) return fail(h, RBPF_EINVAL, "goal_cost needs goal_xy and n_goals >= 1");
+    if (all ? (n_start != 1 && n_start != v.P) : n_start < 1)
+        return fail(h, RBPF_EINVAL, "n_start >= 1 is required, and with particle -1 n_start must be 1 or the number of particles");
+    if (inflate < 0 || clear_max <= inflate || clear_max > 320) return fail(h, RBPF_EINVAL, "0 <= inflate < clear_max <= 320 is required");
+    if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
+    if (ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must hold at most 2^27 cells");
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    if (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge)
+        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    const int ng = goal_cost ? n_goals : 0;                                // goals are read only when their cost is asked for
+    for (long long k = 0; k < 2LL * n_start; ++k)
+        if (!std::isfinite(start_xy[k])) return fail(h, RBPF_EINVAL, "start coordinates must be finite");
+    for (long long k = 0; k < 2LL * ng; ++k)
+        if (!std::isfinite(goal_xy[k])) return fail(h, RBPF_EINVAL, "goal coordinates must be finite");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "travel cost between rbpf_scan_update_begin and rbpf_scan_update_end");
+
+    TravelArgs a;
+    a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
+    a.nbx = (int)((nx + 63) / 64); a.nby = (int)((ny + 63) / 64);
+    a.m = (clear_max + 4) / 5; a.inflate = inflate; a.clear_max = clear_max;
+    a.through_unknown = (flags & RBPF_TRAVEL_THROUGH_UNKNOWN) != 0;
+    a.n_start = n_start; a.start_each = all && n_start == v.P && v.P > 1; a.n_goals = ng;
+    const bool dev_out = (flags & RBPF_TRAVEL_DEVICE_OUT) != 0;
+    const int np_all = all ? v.P : 1;
+    const long long nblk = (long long)a.nbx * a.nby;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    a.cw = a.nby * 64 + 2;
+    const size_t cost_b = pad((size_t)(a.nbx * 64LL + 2) * a.cw * 4), t_b = pad((size_t)nblk * 512), dirty_b = pad((size_t)nblk);
+    const size_t per = cost_b + t_b + 2 * dirty_b;
+    const size_t in_b = pad(((size_t)n_start + ng) * 8);
+    const size_t out_b = dev_out ? 0 : pad(cost ? (size_t)ncell * 4 : 0) + pad(clearance ? (size_t)ncell * 2 : 0) + pad((size_t)np_all * ng * 4);
+    const size_t fixed = in_b + 256 + out_b, limit = (size_t)2 << 30;
+    if (fixed + per > limit) return fail(h, RBPF_ENOMEM, "one particle's travel cost over this box needs more than 2 GiB of scratch: use a smaller box");
+    long long batch = std::min<long long>(std::min<long long>(np_all, 65535), (long long)((limit - fixed) / per));
+    if (const char* e = getenv("RBPF_TRAVEL_BATCH")) batch = std::max(1LL, std::min<long long>(batch, atoll(e)));
+    int per_read = TRAVEL_ROUNDS_PER_READ;
+    if (const char* e = getenv("RBPF_TRAVEL_ROUNDS_PER_READ")) per_read = std::max(1, std::min(32, atoi(e)));   // measurement switch (tools/README.md)
+    HIP_TRY(h, h->reserve(B_TRAVEL, fixed + (size_t)batch * per));
+    const Block& d = h->buf[B_TRAVEL];
+    Staging& st = h->stage[S_TRAVEL];
+    HIP_TRY(h, st.begin(256 + in_b));                                      // the last upload may still read it
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as rbpf_cast_scans forms it
+    int32_t* cells = reinterpret_cast<int32_t*>(st.p + 256);
+    for (long long k = 0; k < (long long)n_start + ng; ++k) {
+        const double* q = k < n_start ? start_xy + 2 * k : goal_xy + 2 * (k - n_start);
+        const double fx = floor(q[0] * inv) - (double)box4[0], fy = floor(q[1] * inv) - (double)box4[2];   // exact: integers in float64
+        const bool in = fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)ny;
+        cells[2 * k] = in ? (int32_t)fx : -1; cells[2 * k + 1] = in ? (int32_t)fy : -1;
+    }
+    HIP_TRY(h, hipMemcpyAsync(d.p, st.p + 256, in_b, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, st.submitted(h->stream));
+    a.starts = d.as<const int32_t>(); a.goals = a.starts + 2 * (size_t)n_start;
+    int32_t* d_count = d.as<int32_t>(in_b);
+    size_t at = in_b + 256;
+    int32_t* o_cost = nullptr; uint16_t* o_clear = nullptr; int32_t* o_goal = nullptr;
+    if (!dev_out) {
+        if (cost) { o_cost = d.as<int32_t>(at); at += pad((size_t)ncell * 4); }
+        if (clearance) { o_clear = d.as<uint16_t>(at); at += pad((size_t)ncell * 2); }
+        if (ng) { o_goal = d.as<int32_t>(at); at += pad((size_t)np_all * ng * 4); }
+    } else { o_cost = cost; o_clear = clearance; o_goal = goal_cost; }
+    unsigned char* work = d.p + at;
+    a.cost_out = o_cost; a.clearance = o_clear;
+    long long launched = 0, runs = 0;
+    const int32_t* h_count = reinterpret_cast<const int32_t*>(st.p);
+    for (long long p0 = 0; p0 < np_all; p0 += batch) {
+        const long long nb = std::min<long long>(batch, np_all - p0);
+        a.particle = all ? (int)p0 : particle; a.n_part = (int)nb;
+        a.cost = reinterpret_cast<int32_t*>(work); a.cost_stride = (long long)(cost_b / 4);
+        a.tbits = reinterpret_cast<uint16_t*>(work + (size_t)nb * cost_b); a.t_stride = (long long)(t_b / 2);
+        a.dirty = work + (size_t)nb * (cost_b + t_b);
+        a.goal_out = o_goal ? o_goal + (size_t)p0 * ng : nullptr;
+        HIP_TRY(h, hipMemsetAsync(a.cost, 0x3f, (size_t)nb * cost_b, h->stream));          // TRAVEL_INF everywhere
+        HIP_TRY(h, hipMemsetAsync(a.dirty, 0, 2 * (size_t)nb * dirty_b, h->stream));
+        launch_travel_mask(v, a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        // dirty flags: [2][nb][nblk] packed without the padding of dirty_b (2 * nb * nblk <= 2 * nb * dirty_b)
+        bool done = false;
+        for (long long r = 0; !done; ) {
+            if (r > ncell + 1) return fail(h, RBPF_EDEVICE, "internal error: the travel cost did not converge");
+            HIP_TRY(h, hipMemsetAsync(d_count, 0, 256, h->stream));
+            for (int q = 0; q < per_read; ++q, ++r) launch_travel_round(a, (int)(r & 1), d_count + q, h->stream);
+            HIP_TRY(h, hipGetLastError());
+            launched += per_read;
+            HIP_TRY(h, hipMemcpyAsync(st.p, d_count, 256, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (int q = 0; q < per_read; ++q) {
+                done = done || h_count[q] == 0;                                            // a round that changed no block: the fixed point
+                runs += h_count[32 + q];
+            }
+        }
+        launch_travel_output(a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        a.clearance = nullptr;
+    }
+    if (rounds) *rounds = (int32_t)std::min<long long>(launched, INT32_MAX);
+    h->travel_stats[0] = (uint64_t)launched; h->travel_stats[1] = (uint64_t)runs; h->travel_stats[2] = (uint64_t)(nblk * np_all);
+    if (dev_out) return RBPF_OK;
+    if (cost) HIP_TRY(h, hipMemcpyAsync(cost, o_cost, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    if (clearance) HIP_TRY(h, hipMemcpyAsync(clearance, o_clear, (size_t)ncell * 2, hipMemcpyDeviceToHost, h->stream));
+    if (ng) HIP_TRY(h, hipMemcpyAsync(goal_cost, o_goal, (size_t)np_all * ng * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_travel_stats(rbpf_handle* h, uint64_t* out3) {
+    if (!h) return RBPF_EINVAL;
+    if (!out3) return fail(h, RBPF_EINVAL, "out3 is NULL");
+    for (int k = 0; k < 3; ++k) out3[k] = h->travel_stats[k];
+    return RBPF_OK;
+}
+
 }  // extern "C"

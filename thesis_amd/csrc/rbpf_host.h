@@ -38,8 +38,9 @@ struct Block {
 // render to host memory; flag, touched tiles, jobs and host raster of a map load; poses, beams and host outputs of a cast;
 // rotations, beams, offset table, field planes, candidate words, merge raster and host outputs of a locate; flag, touched tiles,
 // jobs, host source and host outputs of a map placement; rotations, points, offset table, field planes, merge raster and host
-// outputs of an alignment; poses, beams, table and host outputs of a view gain
-enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_COUNT };
+// outputs of an alignment; poses, beams, table and host outputs of a view gain; start and goal cells, round counters, cost fields,
+// traversable bits, dirty flags and host outputs of a travel cost
+enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_COUNT };
 
 // A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
 // early error return cannot pull memory from under queued work.
@@ -70,8 +71,9 @@ struct Staging : Block {
     void destroy_event() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; }
 };
 // job lists of the pack / unpack kernels and the landing zone of the early resample read-back (pinned); the blocks uploaded
-// into B_RENDER, B_CAST, B_LOAD, B_LOCATE, B_PLACE, B_ALIGN and B_GAIN (pageable)
-enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_COUNT };
+// into B_RENDER, B_CAST, B_LOAD, B_LOCATE, B_PLACE, B_ALIGN and B_GAIN (pageable); the round counters a travel cost reads back
+// and, behind them, the block it uploads into B_TRAVEL (pinned)
+enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_COUNT };
 
 // Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
 // copy that read it has completed (its event), so uploading never drains the stream.
@@ -123,7 +125,7 @@ struct rbpf_handle {
     Staging stage[S_COUNT] = {{{MEM_PINNED}}, {{MEM_PINNED}, hipEventDisableTiming},   // the host reads S_EARLY after its event: system-scope release
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;
@@ -172,4 +174,5 @@ struct rbpf_handle {
     // rbpf_set_proposal_capture / rbpf_get_proposal (tests): the raw sample weights of the last proposal, [P][K], allocated on first use
     bool prop_capture = false, prop_valid = false, prop_captured = false;
     double* d_prop_w = nullptr;
+    uint64_t travel_stats[3] = {0, 0, 0};      // rbpf_travel_stats: rounds, block runs, (particle, block) pairs of the last rbpf_travel_cost
 };

@@ -204,6 +204,29 @@ struct AlignArgs {
     uint32_t* packed;                  // [nx][ny] max over rotations of biased score << 16 | (n_rot - 1 - r), preset to 0
     int32_t *best, *rot;               // [nx][ny] outputs; rot may be null
 };
+// travel cost (kernels_travel.hip): clearance, traversable set and shortest-path cost over a box of one particle's
+// map, or of a batch of particles' maps.  The box is cut into 64 x 64 blocks, block k = bx * nby + by; a particle of the batch
+// is blockIdx.y.  Cells are box-relative: (i, j) = (X - x0, Y - y0).
+static const int TRAVEL_INF = 0x3f3f3f3f;   // "not reached" in the cost field (the byte 0x3f four times: a memset fills it); 7 * 2^27 < it
+struct TravelArgs {
+    int particle;                      // the first particle of this launch
+    int n_part;                        // particles of this launch (gridDim.y)
+    int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
+    int nbx, nby;                      // blocks per axis: ceil(nx / 64), ceil(ny / 64)
+    int m;                             // margin read round a block: ceil(clear_max / 5) <= 64
+    int inflate, clear_max;            // T needs d > inflate; the clearance output is min(d, clear_max)
+    int through_unknown;               // 1: blocked = occupied; 0: blocked = v >= 0
+    int n_start, start_each;           // start_each 1: start (particle + blockIdx.y) only; 0: all n_start in every particle
+    int n_goals;
+    const int32_t* starts;             // [n_start][2] box-relative cell, (-1, -1) outside the box
+    const int32_t* goals;              // [n_goals][2] likewise
+    int32_t* cost; long long cost_stride; int cw;   // [n_part][nbx * 64 + 2][cw = nby * 64 + 2]: cell (i, j) at [i + 1][j + 1]; the rim stays TRAVEL_INF
+    uint16_t* tbits; long long t_stride;            // [n_part][nbx * 64][nby * 4]: bit j & 15 of halfword j >> 4 of row i: cell in T
+    uint8_t* dirty;                    // [2][n_part][nbx * nby]: block changed in the previous / in this round
+    uint16_t* clearance;               // [nx][ny] output or null (single particle only)
+    int32_t* cost_out;                 // [nx][ny] output or null (single particle only)
+    int32_t* goal_out;                 // [n_part][n_goals] output or null
+};
 
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
@@ -268,4 +291,7 @@ void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
+void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.cost preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
+void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one relaxation round; d_count[0] += blocks it changed, d_count[32] += blocks that ran
+void launch_travel_output(const TravelArgs& a, hipStream_t s);                   // cost_out and goal_out from the finished field
 }  // namespace rbpf

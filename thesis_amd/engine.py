@@ -683,6 +683,82 @@ class ParticleEngine:
             self.synchronize()
         return ViewGain(*outs)
 
+    # -- travel cost (include/rbpf_hip.h: rbpf_travel_cost; thesis_amd/plan.py) ---------------------------------
+    def travel_cost(self, starts, goals=None, particle="best", box=None, radius_m: float = 0.0, clear_max: Optional[int] = None,
+                    through_unknown: bool = False, device: bool = False):
+        """Travel cost from `starts` [n, 2] (or [2]; metres, further columns such as a heading are ignored) to every cell of
+        `box` = (x0, x1, y0, y1) in mosaic cells (default map_extent of the particle, or of all particles with particle=None)
+        in a particle's map, walls inflated by `radius_m`: inflate = floor(radius_m * cells per metre * 5) chamfer units, and a
+        cell carries the robot if it is known free (with through_unknown: not occupied) and its clearance exceeds inflate.
+        `particle`: an index or "best" (the first argmax of weights()): returns plan.Travel with cost int32 and clearance uint16
+        rasters [x1-x0, y1-y0] (cost in chamfer units, 5 per axial step and 7 per diagonal one, -1 unreachable; clearance capped
+        at `clear_max`, default and at least inflate + 1) and goal_cost [n_goals] for `goals` [n, 2].  particle=None: goal_cost
+        [P, n_goals] only, every goal in every particle's map; starts are then one point, or P points (start n in particle n's
+        map, e.g. poses()).  plan.path_to walks a path down the field, plan.cost_metres converts.  device=True: torch tensors
+        on the engine's device (clearance as int16), ready for work on torch's current stream."""
+        from .plan import Travel
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        s = _f64(starts)
+        if s.ndim == 1:
+            s = s.reshape(1, -1)
+        if s.ndim != 2 or s.shape[1] < 2:
+            raise ValueError("starts must be [n, 2] (or [2])")
+        s = np.ascontiguousarray(s[:, :2])
+        g = None
+        if goals is not None:
+            g = _f64(goals)
+            if g.ndim == 1:
+                g = g.reshape(1, -1)
+            if g.ndim != 2 or g.shape[1] < 2:
+                raise ValueError("goals must be [n, 2] (or [2])")
+            g = np.ascontiguousarray(g[:, :2])
+        if p < 0 and g is None:
+            raise ValueError("particle=None computes goal costs only: give goals")
+        if box is None:
+            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        inv = self.dim / float(self.cfg.tile_len_m)
+        inflate = int(np.floor(float(radius_m) * inv * 5.0))
+        cmax = max(inflate + 1, inflate + 1 if clear_max is None else int(clear_max))
+        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
+        gshape = None if g is None else ((g.shape[0],) if p >= 0 else (self.P, g.shape[0]))
+        want = [(shape, "int32") if p >= 0 else None, (shape, "int16" if device else "uint16") if p >= 0 else None,
+                (gshape, "int32") if g is not None else None]
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [None if w is None else torch.empty(w[0], dtype=getattr(torch, w[1]), device=dev) for w in want]
+            ptrs = [None if o is None else C.c_void_p(o.data_ptr() or 1) for o in outs]   # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            outs = [None if w is None else np.empty(w[0], dtype=w[1]) for w in want]
+            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
+        flags = (_lib.RBPF_TRAVEL_DEVICE_OUT if device else 0) | (_lib.RBPF_TRAVEL_THROUGH_UNKNOWN if through_unknown else 0)
+        rounds = C.c_int32(0)
+        self._check(self._lib.rbpf_travel_cost(self._h, p, _ip(b), _dp(s), s.shape[0], None if g is None else _dp(g),
+                                               0 if g is None else g.shape[0], inflate, cmax, flags, *ptrs, C.byref(rounds)))
+        if device and not same_stream:
+            self.synchronize()
+        return Travel(outs[0], outs[1], outs[2], int(rounds.value), tuple(int(x) for x in b), float(self.cfg.tile_len_m) / self.dim,
+                      inv, inflate, cmax)
+
+    def travel_stats(self) -> Dict[str, int]:
+        """How the last travel_cost went: relaxation rounds, block runs (workgroups that had work), and the (particle, block)
+        pairs a sweep of everything would run in every round."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._lib.rbpf_travel_stats(self._h, out))
+        return {"rounds": int(out[0]), "block_runs": int(out[1]), "blocks": int(out[2])}
+
     # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
     def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):
         """Scores the scan (`ranges` [B], `angles` [B], sensor frame) at every observed-free cell and each of `n_rot`

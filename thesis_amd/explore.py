@@ -89,3 +89,47 @@ def next_view(engine, angles, particle="best", weights=None, k: int = 8, spacing
     res = engine.view_gain(cand, angles, particle=None if particle is None else src, max_range=max_range, table=table)
     order, scores = rank(res.gain, weights, k)
     return NextViews(cand[order], scores[order], order, cand, res.gain)
+
+
+class ReachableViews(NamedTuple):
+    poses: np.ndarray       # [k', 3] the best reachable view poses, best first (k' <= k)
+    scores: np.ndarray      # [k'] float64: expected gain in bits minus travel_weight times the expected way there in metres
+    order: np.ndarray       # [k'] their indices among the candidates
+    candidates: np.ndarray  # [n, 3] every candidate scored
+    gain: np.ndarray        # view_gain's gain for them: [n], or [P, n] with particle=None
+    goal_cost: np.ndarray   # travel_cost's goal_cost for them, same shape: chamfer units, -1 unreachable
+    reach: np.ndarray       # [n] weighted share of the particles in whose map the candidate can be reached
+
+
+def next_reachable_view(engine, angles, start, particle="best", weights=None, k: int = 8, radius_m: float = 0.2,
+                        travel_weight: float = 0.0, min_reach: float = 0.5, spacing_m: float = 1.0, n_headings: int = 8,
+                        clearance_cells: int = 4, max_range: Optional[float] = None, table=None,
+                        through_unknown: bool = False) -> ReachableViews:
+    """next_view with the way there: candidates as in next_view, scored by view_gain as there, and travel_cost from `start`
+    ((x, y, ...) in metres; with particle=None also [P, 2+], start n in particle n's map) to each of them with walls inflated by
+    `radius_m`.  reach = the weighted share of particles in whose map the candidate has a cost >= 0; candidates with
+    reach < min_reach are dropped; score = gain in bits - travel_weight * (weighted mean of the cost in metres over the
+    particles that reach it).  The k best are returned, ties to the lower index; none if no candidate can be reached."""
+    from .plan import cost_metres
+    if isinstance(particle, str) and particle != "best":
+        raise ValueError(f"unknown particle {particle!r}")
+    best = int(np.argmax(engine.weights()))
+    src = best if particle is None or isinstance(particle, str) else int(particle)
+    cand = candidate_poses(engine.render_map(src), spacing_m, n_headings, clearance_cells, float(engine.cfg.occupied_threshold))
+    if len(cand) == 0:
+        raise ValueError("the map has no frontier cell with that clearance: nowhere to look")
+    which = None if particle is None else src
+    gain = np.asarray(engine.view_gain(cand, angles, particle=which, max_range=max_range, table=table).gain)
+    tr = engine.travel_cost(start, goals=cand[:, :2], particle=which, radius_m=radius_m, through_unknown=through_unknown)
+    goal_cost = np.asarray(tr.goal_cost)
+    g2, c2 = np.atleast_2d(gain).astype(np.float64), np.atleast_2d(goal_cost)
+    w = np.ones(g2.shape[0]) if weights is None or g2.shape[0] == 1 else np.asarray(weights, dtype=np.float64)
+    ok = c2 >= 0
+    wsum = (w[:, None] * ok).sum(axis=0)
+    reach = wsum / w.sum()
+    metres = (w[:, None] * np.where(ok, np.nan_to_num(cost_metres(c2, tr.cell)), 0.0)).sum(axis=0) / np.where(wsum > 0, wsum, 1.0)
+    scores = (w[:, None] * g2).sum(axis=0) / w.sum() / 65536.0 - float(travel_weight) * metres
+    keep = (reach >= float(min_reach)) & (wsum > 0)
+    order = np.argsort(np.where(keep, -scores, np.inf), kind="stable")[:int(k)]
+    order = order[keep[order]]
+    return ReachableViews(cand[order], scores[order], order, cand, gain, goal_cost, reach)
