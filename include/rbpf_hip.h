@@ -220,7 +220,13 @@ int  rbpf_native_sincosf(rbpf_handle* h, const float* x, int32_t n, float* s, fl
 
 /* ---- a8+a9: resample (main.py:46-79) ---------------------------------------------------------- */
 /* u in [0,1) replaces np.random.random() (main.py:59); NaN => internal Philox draw.
- * idx_out[P] (may be NULL) receives the ancestor index of every new particle. */
+ * idx_out[P] (may be NULL) receives the ancestor index of every new particle.
+ * Tile pool: a copy takes a tile from the free pool for every lattice position its ancestor holds and its destination
+ * does not; the tiles the destinations give up go back to the pool only after all copies.  A resample therefore needs as
+ * many FREE tiles as it allocates, not the net number: one that releases a tile and allocates another with no free tile
+ * fails.  Exhaustion is RBPF_ENOMEM (here with idx_out or did_resample, else at the next call that checks the device's
+ * error word, e.g. rbpf_synchronize); the maps are then incomplete and the handle should be destroyed.  The same holds for
+ * rbpf_apply_resample_local. */
 int  rbpf_resample(rbpf_handle* h, double u, int32_t* idx_out, int32_t* did_resample);
 
 /* multi-GPU pieces (one handle per rank; the collectives themselves are the caller's, over RCCL).

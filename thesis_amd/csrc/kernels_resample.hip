@@ -327,6 +327,8 @@ __global__ __launch_bounds__(COPY_BLOCK) void resample_copy_kernel(CopyArgs a) {
                 }
                 __syncthreads();
                 td = s_tile;
+                __syncthreads();                              // every wave has read s_tile before thread 0 may write the tile of
+                                                              // a later position of this job into it (nothing else orders the two)
                 if (td < 0) continue;
             } else {
                 for (int k = 0; k < 4; ++k) db[k] = v.tile_bbox[4 * td + k];
