@@ -518,6 +518,43 @@ int  rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, con
  * every block in every round would be out3[0] * out3[2] block runs. */
 int  rbpf_travel_stats(rbpf_handle* h, uint64_t* out3);
 
+/* ---- frontier regions: where does the known map end, and how large is each opening? ---------------------------------------
+ * The frontier cells of the box box4 (cells, raster layout and v(X, Y) as for rbpf_travel_cost; occ(c) = v(c) * quantum >
+ * occupied_threshold, strict) in the map of `particle`, their connected components, and a table of the largest.  With nx = x1-x0,
+ * ny = y1-y0, dx = X-x0, dy = Y-y0 and L(c) = dx * ny + dy:
+ *   front(c)  = v(c) < 0 and some 4-neighbour n of c has v(n) == 0 and no cell o with occ(o) lies within Chebyshev distance
+ *               `clear` of c.  The REAL map decides: neighbours and occupied cells outside the box count (the map is read over
+ *               the box grown by max(clear, 1) cells, v = 0 outside the lattice); 0 <= clear <= 16.
+ *   F         = {c in box : front(c)}
+ *   region    = a connected component of F under 8-connectivity, members inside the box only (the box clips regions)
+ *   label[c]  = min of L over the region of c; -1 for c not in F                                       (int32 [nx][ny])
+ *   size, sum_dx, sum_dy, x_min, x_max, y_min, y_max of a region: over its members (sums of dx, dy; the bounds in absolute X, Y)
+ *   cx        = floor((2 sum_dx + size) / (2 size)), cy likewise      (the centroid, rounded half up; it need not be a member)
+ *   rep       = the member that minimises (dx - cx)^2 + (dy - cy)^2, ties to the smaller L    (a cell the robot can be sent to)
+ *   kept      = the regions with size >= min_size, by size descending, ties to the smaller label, the first max_regions of them
+ *   regions[k][10] (int64) = {label, size, sum_dx, sum_dy, x_min, x_max, y_min, y_max, rep_X, rep_Y} of kept region k; all -1 for
+ *               k >= n_kept
+ *   counts[3] = {|F|, number of regions before the size filter, n_kept}
+ * Everything is an exact integer, a least fixed point (the labels) or an order-free reduction: the result does not depend on any
+ * evaluation order and is bit-identical from call to call.  Limits: 1 <= nx, ny <= 32768, nx * ny <= 2^27, the box lies in the
+ * tile lattice, min_size >= 1, 1 <= max_regions <= 1024.
+ * particle >= 0: label, regions and counts may each be NULL, but not all three.  particle == -1: label must be NULL, regions is
+ * [P][max_regions][10] and counts [P][3], every particle in its own map; regions and counts may each be NULL, not both.  The
+ * particles are worked on in batches whose scratch stays under 2 GiB; the environment variable RBPF_FRONTIER_BATCH=<n>, read per
+ * call, caps a batch at n particles (for tests).  One particle whose scratch would pass 2 GiB is RBPF_ENOMEM.  DESIGN.md 3.13 has
+ * the kernels.
+ * A NULL box4, a wrong NULL pattern, a bad particle, box, clear, min_size or max_regions, or an unknown flag is RBPF_EINVAL; a call
+ * between rbpf_scan_update_begin and _end is RBPF_ESTATE; all are checked before anything is queued, and nothing is written.  The
+ * call changes no engine state (maps, particles, random streams, counters, duplicate grouping).  It runs on the handle's stream;
+ * without RBPF_FRONTIER_DEVICE_OUT the outputs are host arrays, complete on return; with it the call still waits for its own
+ * convergence reads but not for the outputs. */
+#define RBPF_FRONTIER_DEVICE_OUT 1u   /* label / regions / counts are device pointers, stream order, no host wait for them */
+int  rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4, int32_t clear, int32_t min_size,
+                           int32_t max_regions, uint32_t flags, int32_t* label, int64_t* regions, int32_t* counts);
+/* How the last successful rbpf_frontier_regions of this handle went: out3 = {labelling rounds launched, block runs, (particle,
+ * block) pairs}, as rbpf_travel_stats. */
+int  rbpf_frontier_stats(rbpf_handle* h, uint64_t* out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@
 //                         writes it gets the old or the new value, both are upper bounds, and the neighbour is dirty, so the
 //                         block runs again.  There is no wait on another workgroup anywhere: a round is a kernel.
 //   travel_cost_kernel, travel_goal_kernel   TRAVEL_INF -> -1 into the cost raster; the cost at every goal's cell.
-#include "rbpf_internal.h"
+#include "rbpf_device.h"
 
 namespace rbpf {
 
@@ -32,36 +32,6 @@ static const int TW = 66;             // block with its halo
 static const int TSTRIDE = 67;        // LDS row stride of the cost window: odd, so the rows of a wave's lanes fall into different banks
 static const int TROWS = 192;         // rows of the mask window at the largest margin (64 + 2 * 64)
 static const int SWEEP_CAP = 4096;    // sweeps of one block run; a block that hits it is dirty and goes on in the next round
-
-// bits k = 0 .. 31: cell (u, w0 + k) is occupied; u, w count from the lattice's first cell.  Outside the lattice, without a
-// tile and outside a tile's written box the answer is 0.
-__device__ __forceinline__ uint32_t travel_occ_word(const DevView& v, const int32_t* __restrict__ tab, int u, int w0) {
-    const int dim = v.dim, edge = v.L * dim;
-    if (u < 0 || u >= edge || w0 + 31 < 0 || w0 >= edge) return 0u;
-    const int a = u / dim, i = u - a * dim;
-    uint32_t bits = 0u, word = 0u;
-    int cur_b = -1, cur_w = -1, tile = -1;
-    for (int k = 0; k < 32; ++k) {
-        const int w = w0 + k;
-        if (w < 0 || w >= edge) continue;
-        const int b = w / dim, j = w - b * dim;
-        if (b != cur_b) { tile = tab[a * v.L + b]; cur_b = b; cur_w = -1; }
-        if ((j >> 5) != cur_w) {
-            cur_w = j >> 5;
-            word = tile >= 0 ? v.occ[(size_t)tile * dim * v.ow + (size_t)i * v.ow + cur_w] : 0u;
-        }
-        bits |= ((word >> (j & 31)) & 1u) << k;
-    }
-    return bits;
-}
-
-// 64 bits of a 192-bit row starting at bit `start` (0 .. 128)
-__device__ __forceinline__ uint64_t travel_bits64(const uint32_t* row, int start) {
-    const int w = start >> 5, s = start & 31;
-    const uint64_t lo = (uint64_t)row[w] | ((uint64_t)row[w + 1] << 32);
-    const uint64_t hi = w + 2 < 6 ? (uint64_t)row[w + 2] : 0ull;
-    return s ? (lo >> s) | (hi << (64 - s)) : lo;
-}
 
 __global__ __launch_bounds__(TB) void travel_mask_kernel(DevView v, TravelArgs a) {
     __shared__ uint32_t s_occ[TROWS * 6];                 // row r = X0 - m + r; bit 32 w + k of a row = column Y0 - 64 + 32 w + k
@@ -73,12 +43,12 @@ __global__ __launch_bounds__(TB) void travel_mask_kernel(DevView v, TravelArgs a
     const int dim = v.dim, off = v.R * dim + dim / 2;
     for (int k = tid; k < rows * 6; k += TB) {
         const int r = k / 6, w = k - 6 * r;
-        s_occ[k] = travel_occ_word(v, tab, X0 - m + r + off, Y0 - TS + 32 * w + off);
+        s_occ[k] = occ_word32(v, tab, X0 - m + r + off, Y0 - TS + 32 * w + off);
     }
     __syncthreads();
     for (int k = tid; k < rows * TS; k += TB) {
         const int r = k >> 6, pos = TS + (k & 63);        // the cell's bit in its row
-        const uint64_t right = travel_bits64(s_occ + 6 * r, pos), left = travel_bits64(s_occ + 6 * r, pos - 63);
+        const uint64_t right = occ_bits64(s_occ + 6 * r, pos), left = occ_bits64(s_occ + 6 * r, pos - 63);
         const int dr = right ? __builtin_ctzll(right) : 64, dl = left ? __builtin_clzll(left) : 64;
         s_g[k] = (uint8_t)min(dr, dl);
     }

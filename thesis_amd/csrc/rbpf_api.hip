@@ -1995,4 +1995,102 @@ int rbpf_travel_stats(rbpf_handle* h, uint64_t* out3) {
     return RBPF_OK;
 }
 
+// ---- frontier regions (kernels_frontier.hip) ----------------------------------------------------------------------------------
+int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4, int32_t clear, int32_t min_size, int32_t max_regions,
+                          uint32_t flags, int32_t* label, int64_t* regions, int32_t* counts) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4) return fail(h, RBPF_EINVAL, "box4 is NULL");
+    if (flags & ~RBPF_FRONTIER_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    const bool all = particle < 0;
+    if (all && label) return fail(h, RBPF_EINVAL, "label must be NULL with particle -1");
+    if (!label && !regions && !counts) return fail(h, RBPF_EINVAL, "label, regions and counts are all NULL");
+    if (clear < 0 || clear > 16) return fail(h, RBPF_EINVAL, "0 <= clear <= 16 is required");
+    if (min_size < 1 || max_regions < 1 || max_regions > 1024) return fail(h, RBPF_EINVAL, "min_size >= 1 and 1 <= max_regions <= 1024 are required");
+    if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
+    if (nx > 32768 || ny > 32768 || ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must be at most 32768 cells on a side and hold at most 2^27 cells");
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    if (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge)
+        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "frontier regions between rbpf_scan_update_begin and rbpf_scan_update_end");
+
+    FrontierArgs a;
+    a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
+    a.nbx = (int)((nx + 63) / 64); a.nby = (int)((ny + 63) / 64);
+    a.clear = clear; a.min_size = min_size; a.max_regions = max_regions;
+    const bool dev_out = (flags & RBPF_FRONTIER_DEVICE_OUT) != 0, table = regions || counts;
+    const int np_all = all ? v.P : 1;
+    const long long nblk = (long long)a.nbx * a.nby;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    a.cw = a.nby * 64 + 2;
+    const size_t lab_b = pad((size_t)(a.nbx * 64LL + 2) * a.cw * 4), dirty_b = pad((size_t)nblk);
+    const size_t per = lab_b * (table ? 2 : 1) + 2 * dirty_b;
+    const size_t counts_b = pad((size_t)np_all * 12), table_b = table ? pad((size_t)np_all * max_regions * 80) : 0;
+    const size_t label_b = label && !dev_out ? pad((size_t)ncell * 4) : 0;
+    const size_t fixed = 256 + counts_b + table_b + label_b, limit = (size_t)2 << 30;
+    if (fixed + per > limit) return fail(h, RBPF_ENOMEM, "one particle's frontier regions over this box need more than 2 GiB of scratch: use a smaller box");
+    long long batch = std::min<long long>(std::min<long long>(np_all, 65535), (long long)((limit - fixed) / per));
+    if (const char* e = getenv("RBPF_FRONTIER_BATCH")) batch = std::max(1LL, std::min<long long>(batch, atoll(e)));
+    HIP_TRY(h, h->reserve(B_FRONTIER, fixed + (size_t)batch * per));
+    const Block& d = h->buf[B_FRONTIER];
+    Staging& st = h->stage[S_FRONTIER];
+    HIP_TRY(h, st.begin(256));
+    int32_t* d_count = d.as<int32_t>();
+    // the counts and the table are written where they are wanted when that is device memory, else into scratch and copied
+    int32_t* o_counts = dev_out && counts ? counts : d.as<int32_t>(256);
+    unsigned long long* o_table = !table ? nullptr : dev_out && regions ? reinterpret_cast<unsigned long long*>(regions) : d.as<unsigned long long>(256 + counts_b);
+    a.label_out = !label ? nullptr : dev_out ? label : d.as<int32_t>(256 + counts_b + table_b);
+    unsigned char* work = d.p + fixed;
+    HIP_TRY(h, hipMemsetAsync(o_counts, 0, (size_t)np_all * 12, h->stream));
+    long long launched = 0, runs = 0;
+    const int32_t* h_count = reinterpret_cast<const int32_t*>(st.p);
+    for (long long p0 = 0; p0 < np_all; p0 += batch) {
+        const long long nb = std::min<long long>(batch, np_all - p0);
+        a.particle = all ? (int)p0 : particle; a.n_part = (int)nb;
+        a.lab = reinterpret_cast<int32_t*>(work); a.lab_stride = (long long)(lab_b / 4);
+        a.aux = table ? reinterpret_cast<int32_t*>(work + (size_t)nb * lab_b) : nullptr;
+        a.dirty = work + (size_t)nb * lab_b * (table ? 2 : 1);
+        a.counts = o_counts + 3 * (size_t)p0;
+        a.table = table ? o_table + (size_t)p0 * max_regions * 10 : nullptr;
+        HIP_TRY(h, hipMemsetAsync(a.lab, 0x7f, (size_t)nb * lab_b, h->stream));           // FRONTIER_NONE everywhere
+        HIP_TRY(h, hipMemsetAsync(work + (size_t)nb * lab_b, 0, (size_t)nb * (per - lab_b), h->stream));   // sizes and dirty flags
+        launch_frontier_mask(v, a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        // dirty flags: [2][nb][nblk] packed without the padding of dirty_b, as in rbpf_travel_cost
+        bool done = false;
+        for (long long r = 0; !done; ) {
+            if (r > ncell + 1) return fail(h, RBPF_EDEVICE, "internal error: the frontier labels did not converge");
+            HIP_TRY(h, hipMemsetAsync(d_count, 0, 256, h->stream));
+            for (int q = 0; q < TRAVEL_ROUNDS_PER_READ; ++q, ++r) launch_frontier_round(a, (int)(r & 1), d_count + q, h->stream);
+            HIP_TRY(h, hipGetLastError());
+            launched += TRAVEL_ROUNDS_PER_READ;
+            HIP_TRY(h, hipMemcpyAsync(st.p, d_count, 256, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (int q = 0; q < TRAVEL_ROUNDS_PER_READ; ++q) {
+                done = done || h_count[q] == 0;                                            // a round that changed no block: the fixed point
+                runs += h_count[32 + q];
+            }
+        }
+        launch_frontier_output(a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+    }
+    h->frontier_stats[0] = (uint64_t)launched; h->frontier_stats[1] = (uint64_t)runs; h->frontier_stats[2] = (uint64_t)(nblk * np_all);
+    if (dev_out) return RBPF_OK;
+    if (label) HIP_TRY(h, hipMemcpyAsync(label, a.label_out, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    if (regions) HIP_TRY(h, hipMemcpyAsync(regions, o_table, (size_t)np_all * max_regions * 80, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIP_TRY(h, hipMemcpyAsync(counts, o_counts, (size_t)np_all * 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_frontier_stats(rbpf_handle* h, uint64_t* out3) {
+    if (!h) return RBPF_EINVAL;
+    if (!out3) return fail(h, RBPF_EINVAL, "out3 is NULL");
+    for (int k = 0; k < 3; ++k) out3[k] = h->frontier_stats[k];
+    return RBPF_OK;
+}
+
 }  // extern "C"

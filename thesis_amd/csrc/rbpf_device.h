@@ -149,5 +149,35 @@ __device__ __forceinline__ void unpack_end(int32_t e, int x0, int y0, int& x1, i
     y1 = y0 + (int)(int16_t)((uint32_t)e >> 16);
 }
 
+// ---- occupancy words of a row of mosaic cells (kernels_travel.hip, kernels_frontier.hip) ----------------------------------
+// bits k = 0 .. 31: cell (u, w0 + k) is occupied; u, w count from the lattice's first cell.  Outside the lattice, without a
+// tile and outside a tile's written box the answer is 0.
+__device__ __forceinline__ uint32_t occ_word32(const DevView& v, const int32_t* __restrict__ tab, int u, int w0) {
+    const int dim = v.dim, edge = v.L * dim;
+    if (u < 0 || u >= edge || w0 + 31 < 0 || w0 >= edge) return 0u;
+    const int a = u / dim, i = u - a * dim;
+    uint32_t bits = 0u, word = 0u;
+    int cur_b = -1, cur_w = -1, tile = -1;
+    for (int k = 0; k < 32; ++k) {
+        const int w = w0 + k;
+        if (w < 0 || w >= edge) continue;
+        const int b = w / dim, j = w - b * dim;
+        if (b != cur_b) { tile = tab[a * v.L + b]; cur_b = b; cur_w = -1; }
+        if ((j >> 5) != cur_w) {
+            cur_w = j >> 5;
+            word = tile >= 0 ? v.occ[(size_t)tile * dim * v.ow + (size_t)i * v.ow + cur_w] : 0u;
+        }
+        bits |= ((word >> (j & 31)) & 1u) << k;
+    }
+    return bits;
+}
+
+// 64 bits of a 192-bit row starting at bit `start` (0 .. 128)
+__device__ __forceinline__ uint64_t occ_bits64(const uint32_t* row, int start) {
+    const int w = start >> 5, s = start & 31;
+    const uint64_t lo = (uint64_t)row[w] | ((uint64_t)row[w + 1] << 32);
+    const uint64_t hi = w + 2 < 6 ? (uint64_t)row[w + 2] : 0ull;
+    return s ? (lo >> s) | (hi << (64 - s)) : lo;
+}
 
 }  // namespace rbpf

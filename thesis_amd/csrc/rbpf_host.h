@@ -39,8 +39,9 @@ struct Block {
 // rotations, beams, offset table, field planes, candidate words, merge raster and host outputs of a locate; flag, touched tiles,
 // jobs, host source and host outputs of a map placement; rotations, points, offset table, field planes, merge raster and host
 // outputs of an alignment; poses, beams, table and host outputs of a view gain; start and goal cells, round counters, cost fields,
-// traversable bits, dirty flags and host outputs of a travel cost
-enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_COUNT };
+// traversable bits, dirty flags and host outputs of a travel cost; round counters, region counts, tables, label and size rasters,
+// dirty flags and the host label output of a frontier labelling
+enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_COUNT };
 
 // A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
 // early error return cannot pull memory from under queued work.
@@ -72,8 +73,8 @@ struct Staging : Block {
 };
 // job lists of the pack / unpack kernels and the landing zone of the early resample read-back (pinned); the blocks uploaded
 // into B_RENDER, B_CAST, B_LOAD, B_LOCATE, B_PLACE, B_ALIGN and B_GAIN (pageable); the round counters a travel cost reads back
-// and, behind them, the block it uploads into B_TRAVEL (pinned)
-enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_COUNT };
+// and, behind them, the block it uploads into B_TRAVEL (pinned); the round counters a frontier labelling reads back (pinned)
+enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_COUNT };
 
 // Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
 // copy that read it has completed (its event), so uploading never drains the stream.
@@ -125,7 +126,7 @@ struct rbpf_handle {
     Staging stage[S_COUNT] = {{{MEM_PINNED}}, {{MEM_PINNED}, hipEventDisableTiming},   // the host reads S_EARLY after its event: system-scope release
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;
@@ -175,4 +176,5 @@ struct rbpf_handle {
     bool prop_capture = false, prop_valid = false, prop_captured = false;
     double* d_prop_w = nullptr;
     uint64_t travel_stats[3] = {0, 0, 0};      // rbpf_travel_stats: rounds, block runs, (particle, block) pairs of the last rbpf_travel_cost
+    uint64_t frontier_stats[3] = {0, 0, 0};    // rbpf_frontier_stats: the same of the last rbpf_frontier_regions
 };

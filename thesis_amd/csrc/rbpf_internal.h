@@ -228,6 +228,25 @@ struct TravelArgs {
     int32_t* goal_out;                 // [n_part][n_goals] output or null
 };
 
+// frontier regions (kernels_frontier.hip): frontier cells of a box of one particle's map, or of a batch of particles'
+// maps, their connected components and a table of the largest.  Blocks, particles of the batch and box-relative cells as in
+// TravelArgs; the label of a cell is L = i * ny + j.
+static const int FRONTIER_NONE = 0x7f7f7f7f;   // "no frontier cell" in the label raster (the byte 0x7f four times); 2^27 < it
+struct FrontierArgs {
+    int particle;                      // the first particle of this launch
+    int n_part;                        // particles of this launch (gridDim.y)
+    int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
+    int nbx, nby;                      // blocks per axis: ceil(nx / 64), ceil(ny / 64)
+    int clear;                         // no occupied cell within this Chebyshev distance of a frontier cell (0 .. 16)
+    int min_size, max_regions;         // the table: regions of at least min_size cells, the max_regions largest
+    int32_t* lab; long long lab_stride; int cw;   // [n_part][nbx * 64 + 2][cw = nby * 64 + 2]: cell (i, j) at [i + 1][j + 1]; FRONTIER_NONE elsewhere
+    int32_t* aux;                      // same layout, preset to 0: at a root (lab == L) the region's size, then -(row + 1) if the table keeps it
+    uint8_t* dirty;                    // [2][n_part][nbx * nby]: block changed in the previous / in this round
+    int32_t* counts;                   // [n_part][3] |F|, regions, kept regions; preset to 0
+    unsigned long long* table;         // [n_part][max_regions][10] the rows of include/rbpf_hip.h (two's complement); null: no table
+    int32_t* label_out;                // [nx][ny] output or null (single particle only)
+};
+
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
                            double* d_out_w, hipStream_t s);
@@ -294,4 +313,7 @@ void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs&
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.cost preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one relaxation round; d_count[0] += blocks it changed, d_count[32] += blocks that ran
 void launch_travel_output(const TravelArgs& a, hipStream_t s);                   // cost_out and goal_out from the finished field
+void launch_frontier_mask(const DevView& v, const FrontierArgs& a, hipStream_t s);   // a.lab preset to FRONTIER_NONE, a.aux, a.dirty, a.counts to 0: F, its seeds, |F|
+void launch_frontier_round(const FrontierArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one labelling round; d_count as launch_travel_round
+void launch_frontier_output(const FrontierArgs& a, hipStream_t s);               // from the finished labels: sizes, the table, label_out
 }  // namespace rbpf

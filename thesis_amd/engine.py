@@ -759,6 +759,59 @@ class ParticleEngine:
         self._check(self._lib.rbpf_travel_stats(self._h, out))
         return {"rounds": int(out[0]), "block_runs": int(out[1]), "blocks": int(out[2])}
 
+    # -- frontier regions (include/rbpf_hip.h: rbpf_frontier_regions; thesis_amd/explore.py) ----------------------
+    def frontier_regions(self, particle="best", box=None, clearance_cells: int = 4, min_size: int = 1, max_regions: int = 64,
+                         labels: bool = True, device: bool = False):
+        """The frontier of a particle's map as regions: the known-free cells of `box` = (x0, x1, y0, y1) in mosaic cells (default
+        map_extent of the particle, or of all particles with particle=None) that touch an unknown cell and have no occupied cell
+        within `clearance_cells` on either axis, joined into 8-connected regions.  `particle`: an index or "best" (the first argmax
+        of weights()): returns explore.Frontiers(label, regions, counts, box, cell) with label int32 [x1-x0, y1-y0] (the smallest
+        dx * ny + dy of the cell's region, -1 off the frontier; None with labels=False), regions a structured array [max_regions]
+        with the fields explore.REGION_FIELDS (the regions of at least `min_size` cells, largest first, ties to the smaller label;
+        every field -1 past the last) and counts int32 [3]: frontier cells, regions, regions in the table.  particle=None: every
+        particle in its own map, regions [P, max_regions], counts [P, 3], no label.  device=True: torch tensors on the engine's
+        device (regions as int64 [..., 10]), ready for work on torch's current stream."""
+        from .explore import Frontiers, REGION_DTYPE
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        if box is None:
+            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        K = int(max_regions)
+        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
+        lead = () if p >= 0 else (self.P,)
+        want = [(shape, "int32") if labels and p >= 0 else None, (lead + (max(K, 0), 10), "int64"), (lead + (3,), "int32")]
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [None if w is None else torch.empty(w[0], dtype=getattr(torch, w[1]), device=dev) for w in want]
+            ptrs = [None if o is None else C.c_void_p(o.data_ptr() or 1) for o in outs]   # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            outs = [None if w is None else np.empty(w[0], dtype=w[1]) for w in want]
+            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
+        self._check(self._lib.rbpf_frontier_regions(self._h, p, _ip(b), int(clearance_cells), int(min_size), K,
+                                                    _lib.RBPF_FRONTIER_DEVICE_OUT if device else 0, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        regions = outs[1] if device else outs[1].view(REGION_DTYPE)[..., 0]
+        return Frontiers(outs[0], regions, outs[2], tuple(int(x) for x in b), float(self.cfg.tile_len_m) / self.dim)
+
+    def frontier_stats(self) -> Dict[str, int]:
+        """How the last frontier_regions went: labelling rounds, block runs and (particle, block) pairs, as travel_stats."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._lib.rbpf_frontier_stats(self._h, out))
+        return {"rounds": int(out[0]), "block_runs": int(out[1]), "blocks": int(out[2])}
+
     # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
     def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):
         """Scores the scan (`ranges` [B], `angles` [B], sensor frame) at every observed-free cell and each of `n_rot`

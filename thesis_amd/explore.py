@@ -1,5 +1,6 @@
 """Where should the robot look next?  Candidate view poses on the frontier of a map, ranked by the map cells a scan taken
-there would observe (ParticleEngine.view_gain; include/rbpf_hip.h, rbpf_view_gain).  Host side, NumPy only:
+there would observe (ParticleEngine.view_gain; include/rbpf_hip.h, rbpf_view_gain), from single frontier cells
+or from the frontier regions the GPU labels in every particle's map (ParticleEngine.frontier_regions).  Host side, NumPy only:
 the GPU call is the work, this module turns a map into candidates and the gains into a ranking."""
 from __future__ import annotations
 
@@ -133,3 +134,111 @@ def next_reachable_view(engine, angles, start, particle="best", weights=None, k:
     order = np.argsort(np.where(keep, -scores, np.inf), kind="stable")[:int(k)]
     order = order[keep[order]]
     return ReachableViews(cand[order], scores[order], order, cand, gain, goal_cost, reach)
+
+
+# ---- frontier regions (ParticleEngine.frontier_regions; include/rbpf_hip.h, rbpf_frontier_regions; DESIGN.md 3.13) -----------------
+REGION_FIELDS = ("label", "size", "sum_dx", "sum_dy", "x_min", "x_max", "y_min", "y_max", "rep_X", "rep_Y")
+REGION_DTYPE = np.dtype([(name, np.int64) for name in REGION_FIELDS])
+
+
+class Frontiers(NamedTuple):
+    label: Optional[np.ndarray]  # int32 [x1-x0, y1-y0]: the smallest dx * ny + dy of the cell's region, -1 off the frontier; or None
+    regions: np.ndarray     # REGION_DTYPE [max_regions], or [P, max_regions] with particle=None: largest first, -1 past the last
+    counts: np.ndarray      # int32 [3] or [P, 3]: frontier cells, regions, regions in the table
+    box: tuple              # (x0, x1, y0, y1) in mosaic cells
+    cell: float             # metres per cell
+
+
+def region_poses(fr: Frontiers, n_headings: int = 8) -> np.ndarray:
+    """[n_kept * n_headings, 3] view poses (x, y, theta) of one particle's Frontiers: the centre of every kept region's rep
+    cell, once per heading 2 pi k / n_headings, regions in the table's order."""
+    if np.ndim(fr.counts) != 1:
+        raise ValueError("region_poses takes the Frontiers of one particle")
+    r = fr.regions[:int(fr.counts[2])]
+    xy = (np.stack([r["rep_X"], r["rep_Y"]], axis=1) + 0.5) * float(fr.cell)
+    th = 2.0 * np.pi * np.arange(int(n_headings)) / int(n_headings)
+    return np.concatenate([np.repeat(xy, len(th), axis=0), np.tile(th, len(xy))[:, None]], axis=1).reshape(-1, 3)
+
+
+class PosteriorRegions(NamedTuple):
+    cells: np.ndarray       # [n, 2] int64 mosaic cells (X, Y): one per square
+    support: np.ndarray     # [n] float64: weighted share of the particles with a rep cell in the square
+    size: np.ndarray        # [n] int64: the largest region any particle proposed there
+
+
+def posterior_regions(fr_all: Frontiers, weights=None, spacing_m: float = 1.0, min_support: float = 0.0,
+                      max_candidates: int = 256) -> PosteriorRegions:
+    """Pools the rep cells of every particle's kept regions (Frontiers of particle=None) into squares of `spacing_m`, the
+    squares of candidate_poses.  The support of a square is the weighted share (`weights`, uniform by default) of the particles
+    with at least one rep in it; its cell is the rep proposed with the largest weight sum, ties to the smaller (X, Y).  Squares
+    with support >= min_support come back by support descending, ties row-major, at most `max_candidates` of them."""
+    counts = np.asarray(fr_all.counts)
+    if counts.ndim != 2:
+        raise ValueError("posterior_regions takes the Frontiers of particle=None")
+    P, K = fr_all.regions.shape
+    w = np.ones(P) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != (P,):
+        raise ValueError(f"weights must have shape ({P},)")
+    pidx, kidx = np.nonzero(np.arange(K)[None, :] < counts[:, 2:3])
+    r = fr_all.regions[pidx, kidx]
+    XY = np.stack([r["rep_X"], r["rep_Y"]], axis=1).astype(np.int64).reshape(-1, 2)
+    if len(XY) == 0:
+        return PosteriorRegions(np.zeros((0, 2), np.int64), np.zeros(0), np.zeros(0, np.int64))
+    square = np.floor((XY + 0.5) * float(fr_all.cell) / float(spacing_m)).astype(np.int64)
+    _, s = np.unique(square, axis=0, return_inverse=True)                  # squares in row-major order
+    s = s.reshape(-1)
+    n = int(s.max()) + 1
+    support = np.zeros(n)
+    sp = np.unique(np.stack([s, pidx], axis=1), axis=0)                    # a particle counts once per square
+    np.add.at(support, sp[:, 0], w[sp[:, 1]])
+    support /= w.sum()
+    size = np.zeros(n, np.int64)
+    np.maximum.at(size, s, r["size"].astype(np.int64))
+    cp = np.unique(np.concatenate([s[:, None], XY, pidx[:, None]], axis=1), axis=0)   # and once per cell
+    cells, c = np.unique(cp[:, :3], axis=0, return_inverse=True)           # (square, X, Y), sorted
+    wsum = np.zeros(len(cells))
+    np.add.at(wsum, c.reshape(-1), w[cp[:, 3]])
+    best = np.lexsort((cells[:, 2], cells[:, 1], -wsum, cells[:, 0]))      # per square: weight descending, then (X, Y)
+    first = best[np.unique(cells[best, 0], return_index=True)[1]]
+    keep = np.nonzero(support >= float(min_support))[0]
+    order = keep[np.argsort(-support[keep], kind="stable")][:int(max_candidates)]
+    return PosteriorRegions(cells[first][order, 1:], support[order], size[order])
+
+
+class FrontierViews(NamedTuple):
+    poses: np.ndarray       # [k, 3] the best view poses, best first
+    scores: np.ndarray      # [k] float64: expected gain in table units / 65536 (bits with the entropy table)
+    order: np.ndarray       # [k] their indices among the candidates
+    candidates: np.ndarray  # [n, 3] every candidate scored
+    gain: np.ndarray        # view_gain's gain for them: [n], or [P, n] with particle=None
+    size: np.ndarray        # [k] cells of the frontier region a pose stands for (with particle=None the largest proposed there)
+    support: np.ndarray     # [k] weighted share of the particles that propose it (1 with one particle)
+
+
+def next_frontier_view(engine, angles, particle="best", weights=None, k: int = 8, min_size: int = 4, max_regions: int = 64,
+                       n_headings: int = 8, clearance_cells: int = 4, spacing_m: float = 1.0, min_support: float = 0.0,
+                       max_range: Optional[float] = None, table=None) -> FrontierViews:
+    """next_view with regions for candidates: the rep cells of the frontier regions of at least `min_size` cells
+    (ParticleEngine.frontier_regions) of `particle` (an index or "best"), scored by view_gain in that map.  particle=None: the
+    regions of EVERY particle's map, pooled by posterior_regions with `weights` (uniform by default), so that a frontier the best
+    map lacks is proposed too, scored in every map and averaged."""
+    if isinstance(particle, str) and particle != "best":
+        raise ValueError(f"unknown particle {particle!r}")
+    th = 2.0 * np.pi * np.arange(int(n_headings)) / int(n_headings)
+    if particle is None:
+        fr = engine.frontier_regions(None, clearance_cells=clearance_cells, min_size=min_size, max_regions=max_regions, labels=False)
+        pr = posterior_regions(fr, weights, spacing_m, min_support)
+        xy = (pr.cells + 0.5) * float(fr.cell)
+        cand = np.concatenate([np.repeat(xy, len(th), axis=0), np.tile(th, len(xy))[:, None]], axis=1).reshape(-1, 3)
+        size, support, which = pr.size, pr.support, None
+    else:
+        which = int(np.argmax(engine.weights())) if isinstance(particle, str) else int(particle)
+        fr = engine.frontier_regions(which, clearance_cells=clearance_cells, min_size=min_size, max_regions=max_regions, labels=False)
+        cand = region_poses(fr, n_headings)
+        size = np.asarray(fr.regions["size"][:int(fr.counts[2])], dtype=np.int64)
+        support = np.ones(len(size))
+    if len(cand) == 0:
+        raise ValueError("the map has no frontier region of that size and clearance: nowhere to look")
+    res = engine.view_gain(cand, angles, particle=which, max_range=max_range, table=table)
+    order, scores = rank(res.gain, weights, k)
+    return FrontierViews(cand[order], scores[order], order, cand, res.gain, size[order // len(th)], support[order // len(th)])
