@@ -92,6 +92,27 @@ def test_an_unknown_room_has_no_frontier_and_a_disc_has_a_ring():
     e.close()
 
 
+# ---- 1b. the rounds: what the host queues, reads and counts ---------------------------------------------
+def test_rounds_of_one_block_with_work():
+    e = engine(1)
+    box = (-30, 30, 5, 65)                                # 60 x 60: one block
+    ii, jj = np.mgrid[-25:26, -25:26]
+    load_cells(e, (-25, 26, 10, 61), np.where(ii * ii + jj * jj <= 20 * 20, FREE, 0))
+    fr, _ = check(e, 0, box, 0, what="disc in one block")
+    assert fr.counts[0] > 100 and fr.counts[1:].tolist() == [1, 1]        # a ring: its labels fall to one
+    # round 0 changes the block, round 1 runs it and changes nothing, rounds 2 .. 7 of the first read find no dirty block
+    assert e.frontier_stats() == {"rounds": 8, "block_runs": 2, "blocks": 1}
+    e.close()
+
+
+def test_rounds_with_nothing_to_do():
+    e = engine(1)                                         # no map: not one known cell
+    fr = e.frontier_regions(0, box=(0, 100, 0, 100), clearance_cells=0)   # 2 x 2 blocks
+    assert fr.counts.tolist() == [0, 0, 0] and np.all(fr.label == -1)
+    assert e.frontier_stats() == {"rounds": 8, "block_runs": 0, "blocks": 4}
+    e.close()
+
+
 # ---- 2. a label that has to travel through every block, against the sweeps ---------------------------------------------------------
 def serpentine_cells():
     """200 x 150: one-cell-wide free rows at every second x, joined at alternating ends; everything else unknown."""

@@ -222,6 +222,46 @@ def test_sources():
     e.close()
 
 
+# ---- 5b. the rounds: what the host queues, reads and counts ---------------------------------------------
+def free_square(e):
+    """40 x 40 known-free cells in one block, a start inside: (box, start, the cost of every cell)."""
+    box = (10, 50, -20, 20)
+    e.load_map(raster(e, box, np.full((40, 40), FREE, np.int8)))
+    di, dj = np.abs(np.mgrid[0:40, 0:40] - np.array([7, 30]).reshape(2, 1, 1))
+    return box, centre(e, box[0] + 7, box[2] + 30), (5 * np.maximum(di, dj) + 2 * np.minimum(di, dj)).astype(np.int32)
+
+
+def test_rounds_of_one_block_with_work():
+    e = engine(1)
+    box, start, cost = free_square(e)
+    tr = e.travel_cost([start], particle=0, box=box)
+    same(tr, oracle(e, 0, box, [start], None, 0, 1), "free square")
+    assert np.array_equal(tr.cost, cost)
+    # round 0 changes the block, round 1 runs it and changes nothing, rounds 2 .. 7 of the first read find no dirty block
+    assert e.travel_stats() == {"rounds": 8, "block_runs": 2, "blocks": 1} and tr.rounds == 8
+    e.close()
+
+
+def test_rounds_of_one_block_with_one_round_per_read(monkeypatch):
+    e = engine(1)
+    box, start, cost = free_square(e)
+    monkeypatch.setenv("RBPF_TRAVEL_ROUNDS_PER_READ", "1")
+    tr = e.travel_cost([start], particle=0, box=box)
+    assert np.array_equal(tr.cost, cost)
+    assert e.travel_stats() == {"rounds": 2, "block_runs": 2, "blocks": 1} and tr.rounds == 2
+    e.close()
+
+
+def test_rounds_with_nothing_to_do():
+    e = engine(1)
+    box = (0, 100, 0, 100)                                # 2 x 2 blocks
+    e.load_map(raster(e, box, np.full((100, 100), FREE, np.int8)))
+    tr = e.travel_cost([centre(e, -3, 50)], particle=0, box=box)          # the only start lies outside the box
+    assert np.all(tr.cost == -1) and tr.cost.shape == (100, 100)
+    assert e.travel_stats() == {"rounds": 8, "block_runs": 0, "blocks": 4} and tr.rounds == 8
+    e.close()
+
+
 # ---- 6. maps the engine built: every particle, state, device outputs, a path ---------------------------------------------------
 @pytest.fixture(scope="module")
 def built():

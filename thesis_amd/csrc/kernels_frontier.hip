@@ -2,19 +2,17 @@
 // 8-connectivity, and a table of the largest with a cell of each to send the robot to (include/rbpf_hip.h, rbpf_frontier_regions;
 // the specification is DESIGN 3.13).
 //
-// The box is cut into 64 x 64 blocks as in kernels_travel.hip; one 256-lane workgroup works on one (particle, block), and a lane
+// The box is cut into 64 x 64 blocks (rbpf_blockrelax.h); one 256-lane workgroup works on one (particle, block), and a lane
 // owns 16 neighbouring cells of one row.
 //   frontier_mask_kernel    the block's occupancy bits with `clear` rows above and below (and 64 columns either side) from the tiles'
 //                           occupancy words, its int8 cells with a one-cell halo.  A row's bits are widened by `clear` columns, the
 //                           widened rows of the 2 clear + 1 rows round a cell are or-ed: a bit of the result says "an occupied cell
 //                           within Chebyshev distance clear".  A frontier cell gets its own L = i ny + j as its label; the others
 //                           keep FRONTIER_NONE.  Counts |F| with one atomic per wave, marks the block dirty if it holds a cell of F.
-//   frontier_label_kernel   one round.  A block runs if it or one of its 8 neighbours changed in the previous round: it loads its
-//                           labels with a one-cell halo (66 x 66) into LDS and sweeps label = min(label, the 8 neighbours' labels)
-//                           over its frontier cells to its local fixed point, as travel_relax_kernel sweeps.  A cell outside F holds
-//                           FRONTIER_NONE for ever, which no minimum takes.  Labels only fall and are at all times the L of a member
-//                           of the cell's own region, so a stale read of a neighbour's edge is an upper bound, and the neighbour is
-//                           dirty, so the block runs again.  There is no wait on another workgroup anywhere: a round is a kernel.
+//   frontier_label_kernel   one round of rbpf_blockrelax.h over the labels with the rule of FrontierRule: a frontier cell takes the
+//                           least of its own and its 8 neighbours' labels.  A cell outside F holds FRONTIER_NONE for ever, which
+//                           no minimum takes, so the window itself says which cells are active.  Labels only fall and are at all
+//                           times the L of a member of the cell's own region.
 //   frontier_reduce_kernel  the fixed point: label = the smallest L of the region, and the root is the cell with label == L.  Every
 //                           frontier cell adds 1 to the size kept at its root's position; the roots are counted.
 //   frontier_select_kernel  one workgroup per particle: the max_regions largest roots with size >= min_size by the key (size
@@ -33,13 +31,8 @@
 
 namespace rbpf {
 
-static const int FB = 256;
-static const int FS = 64;             // block edge
-static const int FW = 66;             // block with its halo
-static const int FSTRIDE = 67;        // LDS row stride of the label window: odd, as in travel_relax_kernel
 static const int FVS = 68;            // LDS row stride of the int8 window
 static const int FROWS = 96;          // rows of the occupancy window at the largest clearance (64 + 2 * 16)
-static const int SWEEP_CAP = 4096;    // sweeps of one block run; a block that hits it is dirty and goes on in the next round
 static const int SEL_N = 2048;        // keys of the selection buffer: 1024 kept at the most, 1024 (four per lane) added between two tests
 
 typedef unsigned long long u64;
@@ -52,46 +45,46 @@ __device__ __forceinline__ int frontier_cell(const DevView& v, const int32_t* __
     return tile < 0 ? 0 : v.pool[(size_t)tile * dim * dim + (size_t)(u - a * dim) * dim + (w - b * dim)];
 }
 
-__global__ __launch_bounds__(FB) void frontier_mask_kernel(DevView v, FrontierArgs a) {
+__global__ __launch_bounds__(BR_LANES) void frontier_mask_kernel(DevView v, FrontierArgs a) {
     __shared__ uint32_t s_occ[FROWS * 6];                 // row r = X0 - clear + r; bit 32 w + k of a row = column Y0 - 64 + 32 w + k
     __shared__ uint64_t s_wide[FROWS];                    // bit j: an occupied cell of the row within `clear` columns of Y0 + j
-    __shared__ uint64_t s_near[FS];                       // bit j of row i: an occupied cell within Chebyshev distance `clear` of (X0 + i, Y0 + j)
-    __shared__ int8_t s_v[FW * FVS];                      // cell (X0 - 1 + r, Y0 - 1 + q) at [r][q]
+    __shared__ uint64_t s_near[BR_EDGE];                       // bit j of row i: an occupied cell within Chebyshev distance `clear` of (X0 + i, Y0 + j)
+    __shared__ int8_t s_v[BR_WIN * FVS];                      // cell (X0 - 1 + r, Y0 - 1 + q) at [r][q]
     const int tid = threadIdx.x, pi = blockIdx.y, p = a.particle + pi;
     const int bx = blockIdx.x / a.nby, by = blockIdx.x - bx * a.nby;
-    const int X0 = a.x0 + FS * bx, Y0 = a.y0 + FS * by, m = a.clear, rows = FS + 2 * m;
+    const int X0 = a.x0 + BR_EDGE * bx, Y0 = a.y0 + BR_EDGE * by, m = a.clear, rows = BR_EDGE + 2 * m;
     const int32_t* __restrict__ tab = v.tile_tab + (size_t)v.slot[p] * v.L * v.L;
     const int off = v.R * v.dim + v.dim / 2;
-    for (int k = tid; k < rows * 6; k += FB) {
+    for (int k = tid; k < rows * 6; k += BR_LANES) {
         const int r = k / 6, w = k - 6 * r;
-        s_occ[k] = occ_word32(v, tab, X0 - m + r + off, Y0 - FS + 32 * w + off);
+        s_occ[k] = occ_word32(v, tab, X0 - m + r + off, Y0 - BR_EDGE + 32 * w + off);
     }
-    for (int k = tid; k < FW * FW; k += FB) {
-        const int r = k / FW, q = k - FW * r;
+    for (int k = tid; k < BR_WIN * BR_WIN; k += BR_LANES) {
+        const int r = k / BR_WIN, q = k - BR_WIN * r;
         s_v[r * FVS + q] = (int8_t)frontier_cell(v, tab, X0 - 1 + r + off, Y0 - 1 + q + off);
     }
     __syncthreads();
     if (tid < rows) {
         uint64_t d = 0;
-        for (int k = -m; k <= m; ++k) d |= occ_bits64(s_occ + 6 * tid, FS + k);
+        for (int k = -m; k <= m; ++k) d |= occ_bits64(s_occ + 6 * tid, BR_EDGE + k);
         s_wide[tid] = d;
     }
     __syncthreads();
-    if (tid < FS) {
+    if (tid < BR_EDGE) {
         uint64_t d = 0;
         for (int dx = 0; dx <= 2 * m; ++dx) d |= s_wide[tid + dx];
         s_near[tid] = d;
     }
     __syncthreads();
-    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = FS * bx + i;   // box-relative row
+    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = BR_EDGE * bx + i;   // box-relative row
     int n = 0;
     if (ri < a.nx) {
         const uint32_t near = (uint32_t)(s_near[i] >> j0);
         const int8_t* c = s_v + (i + 1) * FVS + j0 + 1;
-        int32_t* out = a.lab + (size_t)pi * a.lab_stride + (size_t)(ri + 1) * a.cw + FS * by + j0 + 1;
+        int32_t* out = a.ras + (size_t)pi * a.ras_stride + (size_t)(ri + 1) * a.cw + BR_EDGE * by + j0 + 1;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            const int rj = FS * by + j0 + k;
+            const int rj = BR_EDGE * by + j0 + k;
             if (rj >= a.ny) break;
             if (c[k] < 0 && !((near >> k) & 1u) && (c[k - FVS] == 0 || c[k + FVS] == 0 || c[k - 1] == 0 || c[k + 1] == 0)) {
                 out[k] = ri * a.ny + rj;
@@ -104,72 +97,25 @@ __global__ __launch_bounds__(FB) void frontier_mask_kernel(DevView v, FrontierAr
     if (__syncthreads_or(n) && tid == 0) a.dirty[(size_t)pi * a.nbx * a.nby + blockIdx.x] = 1;   // parity 0: the first round reads it
 }
 
-// cell k of the lane's row from the rows above (u), of (c) and below (d) it; index k + 1 is the cell
-#define FRONTIER_MIN(k)                                                                                  \
-    if ((fb >> (k)) & 1u) {                                                                              \
-        const int b_ = min(min(min(u[k], u[(k) + 1]), min(u[(k) + 2], c[k])),                            \
-                           min(min(c[(k) + 2], d[k]), min(d[(k) + 1], d[(k) + 2])));                     \
-        if (b_ < c[(k) + 1]) { c[(k) + 1] = b_; changed = 1; }                                           \
+struct FrontierRule {
+    static const bool MASK_FROM_WINDOW = true;
+    __device__ __forceinline__ uint32_t mask(const int32_t* sc) const {   // the lane's frontier cells: they alone ever hold a label
+        uint32_t m = 0u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m |= (uint32_t)(sc[k + 1] != FRONTIER_NONE) << k;
+        return m;
     }
-
-__global__ __launch_bounds__(FB) void frontier_label_kernel(FrontierArgs a, int parity, int32_t* count) {
-    __shared__ int32_t s_c[FW * FSTRIDE];
-    const int tid = threadIdx.x, pi = blockIdx.y, nblk = a.nbx * a.nby;
-    const int bx = blockIdx.x / a.nby, by = blockIdx.x - bx * a.nby;
-    const uint8_t* __restrict__ din = a.dirty + ((size_t)parity * a.n_part + pi) * nblk;
-    uint8_t* __restrict__ dout = a.dirty + ((size_t)(parity ^ 1) * a.n_part + pi) * nblk;
-    int run = 0;
-    for (int ex = max(bx - 1, 0); ex <= min(bx + 1, a.nbx - 1); ++ex)
-        for (int ey = max(by - 1, 0); ey <= min(by + 1, a.nby - 1); ++ey) run |= din[ex * a.nby + ey];
-    if (!run) {                                            // (uniform over the workgroup)
-        if (tid == 0) dout[blockIdx.x] = 0;
-        return;
-    }
-    int32_t* __restrict__ base = a.lab + (size_t)pi * a.lab_stride + (size_t)(FS * bx) * a.cw + FS * by;   // window cell [0][0]: the halo's corner
-    for (int k = tid; k < FW * FW; k += FB) {
-        const int r = k / FW, q = k - FW * r;
-        s_c[r * FSTRIDE + q] = base[(size_t)r * a.cw + q];
-    }
-    const int i = tid >> 2, seg = tid & 3;
-    const int32_t* su = s_c + i * FSTRIDE + 16 * seg;      // the row above the lane's, from the column left of its first cell
-    int32_t* sc = s_c + (i + 1) * FSTRIDE + 16 * seg;
-    const int32_t* sd = s_c + (i + 2) * FSTRIDE + 16 * seg;
-    __syncthreads();
-    uint32_t fb = 0u;                                      // the lane's frontier cells: they alone ever hold a label
-#pragma unroll
-    for (int k = 0; k < 16; ++k) fb |= (uint32_t)(sc[k + 1] != FRONTIER_NONE) << k;
-    int c[18], any = 0;
-    for (int sweep = 0; sweep < SWEEP_CAP; ++sweep) {
-        int changed = 0;
-        if (fb) {
-            int u[18], d[18];
-#pragma unroll
-            for (int k = 0; k < 18; ++k) { u[k] = su[k]; c[k] = sc[k]; d[k] = sd[k]; }
-#pragma unroll
-            for (int k = 0; k < 16; ++k) FRONTIER_MIN(k)
-#pragma unroll
-            for (int k = 14; k >= 0; --k) FRONTIER_MIN(k)
-            if (changed) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) sc[k + 1] = c[k + 1];   // the lane's own cells: nobody else writes them
-            }
+    static __device__ __forceinline__ void cell(int k, uint32_t m, const int (&u)[18], int (&c)[18], const int (&d)[18], int& changed) {
+        if ((m >> k) & 1u) {
+            const int b_ = min(min(min(u[k], u[k + 1]), min(u[k + 2], c[k])), min(min(c[k + 2], d[k]), min(d[k + 1], d[k + 2])));
+            if (b_ < c[k + 1]) { c[k + 1] = b_; changed = 1; }
         }
-        if (!__syncthreads_or(changed)) break;
-        any = 1;
     }
-    if (any && fb) {                                       // c holds the last state of the lane's cells
-        int32_t* out = base + (size_t)(i + 1) * a.cw + 16 * seg + 1;
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if ((fb >> k) & 1u) out[k] = c[k + 1];
-    }
-    if (tid == 0) {
-        dout[blockIdx.x] = (uint8_t)any;
-        atomicAdd(count + 32, 1);                          // block runs of this round (rbpf_frontier_stats)
-        if (any) atomicAdd(count, 1);
-    }
+};
+
+__global__ __launch_bounds__(BR_LANES) void frontier_label_kernel(FrontierArgs a, int parity, int32_t* count) {
+    block_relax_round(a, FrontierRule{}, parity, count);
 }
-#undef FRONTIER_MIN
 
 // position in the label raster of the cell whose L is given
 __device__ __forceinline__ size_t frontier_at(const FrontierArgs& a, int L) {
@@ -180,7 +126,7 @@ __device__ __forceinline__ size_t frontier_at(const FrontierArgs& a, int L) {
 // The lane's 16 labels of the finished raster (FRONTIER_NONE beyond the box: nothing was ever written there) and the label all
 // frontier cells of the wave share: FRONTIER_NONE if the wave has none, -1 if they differ.  Every lane of the wave calls it.
 __device__ __forceinline__ int frontier_lane_labels(const FrontierArgs& a, int pi, int bx, int by, int i, int j0, int (&l)[16]) {
-    const int32_t* row = a.lab + (size_t)pi * a.lab_stride + (size_t)(FS * bx + i + 1) * a.cw + FS * by + j0 + 1;
+    const int32_t* row = a.ras + (size_t)pi * a.ras_stride + (size_t)(BR_EDGE * bx + i + 1) * a.cw + BR_EDGE * by + j0 + 1;
     int first = FRONTIER_NONE;
     bool same = true;
 #pragma unroll
@@ -208,15 +154,15 @@ __device__ __forceinline__ u64 wave_min64(u64 x) {
     return x;
 }
 
-__global__ __launch_bounds__(FB) void frontier_reduce_kernel(FrontierArgs a) {
+__global__ __launch_bounds__(BR_LANES) void frontier_reduce_kernel(FrontierArgs a) {
     const int tid = threadIdx.x, pi = blockIdx.y;
     const int bx = blockIdx.x / a.nby, by = blockIdx.x - bx * a.nby;
     const int i = tid >> 2, j0 = 16 * (tid & 3);
     int l[16];
     const int wl = frontier_lane_labels(a, pi, bx, by, i, j0, l);
     if (wl == FRONTIER_NONE) return;                       // (uniform over the wave)
-    int32_t* aux = a.aux + (size_t)pi * a.lab_stride;
-    const int own = (FS * bx + i) * a.ny + FS * by + j0;   // L of the lane's first cell
+    int32_t* aux = a.aux + (size_t)pi * a.ras_stride;
+    const int own = (BR_EDGE * bx + i) * a.ny + BR_EDGE * by + j0;   // L of the lane's first cell
     int n = 0, roots = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { n += l[k] != FRONTIER_NONE; roots += l[k] == own + k; }
@@ -242,7 +188,7 @@ __global__ __launch_bounds__(FB) void frontier_reduce_kernel(FrontierArgs a) {
 __device__ __forceinline__ void frontier_sort(u64* s, int tid) {
     for (int k = 2; k <= SEL_N; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < SEL_N; t += FB) {
+            for (int t = tid; t < SEL_N; t += BR_LANES) {
                 const int x = t ^ j;
                 if (x > t) {
                     const u64 p = s[t], q = s[x];
@@ -255,20 +201,20 @@ __device__ __forceinline__ void frontier_sort(u64* s, int tid) {
 
 static const u64 ROW_UNSET = ~0ull;   // a minimum nothing was offered to yet
 
-__global__ __launch_bounds__(FB) void frontier_select_kernel(FrontierArgs a) {
+__global__ __launch_bounds__(BR_LANES) void frontier_select_kernel(FrontierArgs a) {
     __shared__ u64 s_key[SEL_N];                           // size << 32 | ~label of a candidate root: larger is better; 0 = free
     __shared__ int s_n;                                    // keys in s_key
     __shared__ u64 s_floor;                                // once max_regions keys are held: the smallest of them
     const int tid = threadIdx.x, pi = blockIdx.x, K = a.max_regions;
-    int32_t* aux = a.aux + (size_t)pi * a.lab_stride;
-    for (int k = tid; k < SEL_N; k += FB) s_key[k] = 0;
+    int32_t* aux = a.aux + (size_t)pi * a.ras_stride;
+    for (int k = tid; k < SEL_N; k += BR_LANES) s_key[k] = 0;
     if (tid == 0) { s_n = 0; s_floor = 0; }
     __syncthreads();
     const long long ncell = (long long)a.nx * a.ny;
-    for (long long base = 0; base < ncell; base += 4 * FB) {
+    for (long long base = 0; base < ncell; base += 4 * BR_LANES) {
         const u64 floor_key = s_floor;
         for (int q = 0; q < 4; ++q) {
-            const long long t = base + q * FB + tid;
+            const long long t = base + q * BR_LANES + tid;
             if (t >= ncell) break;
             const int sz = aux[frontier_at(a, (int)t)];    // 0 wherever no root is
             if (sz < a.min_size) continue;
@@ -278,9 +224,9 @@ __global__ __launch_bounds__(FB) void frontier_select_kernel(FrontierArgs a) {
         __syncthreads();
         const int held = s_n;                              // read between two barriers: the same in every lane, whatever the waves' pace
         __syncthreads();                                   // nobody appends for the next pass before everybody has read it
-        if (held > SEL_N - 4 * FB) {                       // the next pass could overflow: keep the K best
+        if (held > SEL_N - 4 * BR_LANES) {                       // the next pass could overflow: keep the K best
             frontier_sort(s_key, tid);
-            for (int k = K + tid; k < SEL_N; k += FB) s_key[k] = 0;
+            for (int k = K + tid; k < SEL_N; k += BR_LANES) s_key[k] = 0;
             if (tid == 0 && held >= K) { s_n = K; s_floor = s_key[K - 1]; }
             __syncthreads();
         }
@@ -288,7 +234,7 @@ __global__ __launch_bounds__(FB) void frontier_select_kernel(FrontierArgs a) {
     frontier_sort(s_key, tid);
     const int kept = min(s_n, K);
     if (tid == 0) a.counts[3 * (size_t)pi + 2] = kept;
-    for (int k = tid; k < K; k += FB) {
+    for (int k = tid; k < K; k += BR_LANES) {
         u64* row = a.table + ((size_t)pi * K + k) * 10;
         if (k < kept) {
             const u64 key = s_key[k];
@@ -305,7 +251,7 @@ __global__ __launch_bounds__(FB) void frontier_select_kernel(FrontierArgs a) {
 
 // the table row of the region with this label, or null if the table does not keep it
 __device__ __forceinline__ u64* frontier_row(const FrontierArgs& a, int pi, int label) {
-    const int r = a.aux[(size_t)pi * a.lab_stride + frontier_at(a, label)];
+    const int r = a.aux[(size_t)pi * a.ras_stride + frontier_at(a, label)];
     return r < 0 ? a.table + ((size_t)pi * a.max_regions + (-r - 1)) * 10 : nullptr;
 }
 
@@ -314,10 +260,10 @@ __device__ __forceinline__ void frontier_add_moments(u64* row, int sdx, int sdy,
     atomicMin(row + 4, (u64)x_lo); atomicMax(row + 5, (u64)x_hi); atomicMin(row + 6, (u64)y_lo); atomicMax(row + 7, (u64)y_hi);
 }
 
-__global__ __launch_bounds__(FB) void frontier_moment_kernel(FrontierArgs a) {
+__global__ __launch_bounds__(BR_LANES) void frontier_moment_kernel(FrontierArgs a) {
     const int tid = threadIdx.x, pi = blockIdx.y;
     const int bx = blockIdx.x / a.nby, by = blockIdx.x - bx * a.nby;
-    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = FS * bx + i, rj0 = FS * by + j0;
+    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = BR_EDGE * bx + i, rj0 = BR_EDGE * by + j0;
     int l[16];
     const int wl = frontier_lane_labels(a, pi, bx, by, i, j0, l);
     if (wl == FRONTIER_NONE) return;                       // (uniform over the wave)
@@ -357,10 +303,10 @@ __device__ __forceinline__ u64 frontier_rep_key(u64 centroid, int ri, int rj, in
     return ((u64)(ex * ex + ey * ey) << 27) | (u64)L;
 }
 
-__global__ __launch_bounds__(FB) void frontier_rep_kernel(FrontierArgs a) {
+__global__ __launch_bounds__(BR_LANES) void frontier_rep_kernel(FrontierArgs a) {
     const int tid = threadIdx.x, pi = blockIdx.y;
     const int bx = blockIdx.x / a.nby, by = blockIdx.x - bx * a.nby;
-    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = FS * bx + i, rj0 = FS * by + j0;
+    const int i = tid >> 2, j0 = 16 * (tid & 3), ri = BR_EDGE * bx + i, rj0 = BR_EDGE * by + j0;
     int l[16];
     const int wl = frontier_lane_labels(a, pi, bx, by, i, j0, l);
     if (wl == FRONTIER_NONE) return;                       // (uniform over the wave)
@@ -392,8 +338,8 @@ __global__ __launch_bounds__(FB) void frontier_rep_kernel(FrontierArgs a) {
     }
 }
 
-__global__ __launch_bounds__(FB) void frontier_finish_kernel(FrontierArgs a) {
-    const long long t = (long long)blockIdx.x * FB + threadIdx.x;
+__global__ __launch_bounds__(BR_LANES) void frontier_finish_kernel(FrontierArgs a) {
+    const long long t = (long long)blockIdx.x * BR_LANES + threadIdx.x;
     if (t >= (long long)a.n_part * a.max_regions) return;
     const int pi = (int)(t / a.max_regions), k = (int)(t - (long long)pi * a.max_regions);
     if (k >= a.counts[3 * (size_t)pi + 2]) return;
@@ -404,33 +350,31 @@ __global__ __launch_bounds__(FB) void frontier_finish_kernel(FrontierArgs a) {
     row[8] = x0 + (u64)ri; row[9] = y0 + (u64)(L - ri * a.ny);
 }
 
-__global__ __launch_bounds__(FB) void frontier_label_out_kernel(FrontierArgs a) {
-    const long long t = (long long)blockIdx.x * FB + threadIdx.x;
+__global__ __launch_bounds__(BR_LANES) void frontier_label_out_kernel(FrontierArgs a) {
+    const long long t = (long long)blockIdx.x * BR_LANES + threadIdx.x;
     if (t >= (long long)a.nx * a.ny) return;
-    const int32_t lv = a.lab[frontier_at(a, (int)t)];
+    const int32_t lv = a.ras[frontier_at(a, (int)t)];
     a.label_out[t] = lv == FRONTIER_NONE ? -1 : lv;
 }
 
-static unsigned blocks_for(long long n) { return (unsigned)((n + FB - 1) / FB); }
-
 void launch_frontier_mask(const DevView& v, const FrontierArgs& a, hipStream_t s) {
-    frontier_mask_kernel<<<dim3((unsigned)(a.nbx * a.nby), (unsigned)a.n_part), FB, 0, s>>>(v, a);
+    frontier_mask_kernel<<<block_relax_grid(a), BR_LANES, 0, s>>>(v, a);
 }
 
 void launch_frontier_round(const FrontierArgs& a, int parity, int32_t* d_count, hipStream_t s) {
-    frontier_label_kernel<<<dim3((unsigned)(a.nbx * a.nby), (unsigned)a.n_part), FB, 0, s>>>(a, parity, d_count);
+    frontier_label_kernel<<<block_relax_grid(a), BR_LANES, 0, s>>>(a, parity, d_count);
 }
 
 void launch_frontier_output(const FrontierArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)(a.nbx * a.nby), (unsigned)a.n_part);
     if (a.table) {
-        frontier_reduce_kernel<<<grid, FB, 0, s>>>(a);
-        frontier_select_kernel<<<(unsigned)a.n_part, FB, 0, s>>>(a);
-        frontier_moment_kernel<<<grid, FB, 0, s>>>(a);
-        frontier_rep_kernel<<<grid, FB, 0, s>>>(a);
-        frontier_finish_kernel<<<blocks_for((long long)a.n_part * a.max_regions), FB, 0, s>>>(a);
+        frontier_reduce_kernel<<<grid, BR_LANES, 0, s>>>(a);
+        frontier_select_kernel<<<(unsigned)a.n_part, BR_LANES, 0, s>>>(a);
+        frontier_moment_kernel<<<grid, BR_LANES, 0, s>>>(a);
+        frontier_rep_kernel<<<grid, BR_LANES, 0, s>>>(a);
+        frontier_finish_kernel<<<br_blocks((long long)a.n_part * a.max_regions), BR_LANES, 0, s>>>(a);
     }
-    if (a.label_out) frontier_label_out_kernel<<<blocks_for((long long)a.nx * a.ny), FB, 0, s>>>(a);
+    if (a.label_out) frontier_label_out_kernel<<<br_blocks((long long)a.nx * a.ny), BR_LANES, 0, s>>>(a);
 }
 
 }  // namespace rbpf

@@ -1866,11 +1866,51 @@ int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int
     return RBPF_OK;
 }
 
-// ---- travel cost (kernels_travel.hip) -----------------------------------------------------------------------------------------
+}  // extern "C"
+
+// ---- block relaxation (rbpf_blockrelax.h): what rbpf_travel_cost and rbpf_frontier_regions share on the host ------------------
 // relaxation rounds queued between two reads of their counters.  A read costs a host wait; a round after convergence costs one
 // launch of workgroups that leave at once.  DESIGN.md 3.12 has the measurement behind the value.
 static const int TRAVEL_ROUNDS_PER_READ = 8;
+static const size_t RELAX_SCRATCH = (size_t)2 << 30;   // scratch of one batch of particles at the most
 
+// particles per batch: `fixed` bytes once and `per` bytes for every particle of the batch fit RELAX_SCRATCH (the caller has
+// checked that one particle does), a batch is one grid (gridDim.y), and the environment variable may cap it, for tests
+static long long relax_batch(int np_all, size_t fixed, size_t per, const char* cap_env) {
+    long long batch = std::min<long long>(std::min<long long>(np_all, 65535), (long long)((RELAX_SCRATCH - fixed) / per));
+    if (const char* e = getenv(cap_env)) batch = std::max(1LL, std::min<long long>(batch, atoll(e)));
+    return batch;
+}
+
+// The rounds of one batch, to the fixed point: queues per_read rounds, launch(r, counter of the round), reads their counters
+// into the pinned stage `st` (256 bytes: 32 counts of changed blocks, 32 of block runs) and stops at the first batch that
+// holds a round which changed no block.  Adds the rounds launched and the block runs to `launched` and `runs`.
+template <class Launch>
+static int relax_rounds(rbpf_handle* h, Staging& st, int32_t* d_count, long long round_limit, int per_read, const char* not_converged,
+                        Launch launch, long long& launched, long long& runs) {
+    const int32_t* h_count = reinterpret_cast<const int32_t*>(st.p);
+    bool done = false;
+    for (long long r = 0; !done; ) {
+        if (r > round_limit) return fail(h, RBPF_EDEVICE, not_converged);
+        HIP_TRY(h, hipMemsetAsync(d_count, 0, 256, h->stream));
+        for (int q = 0; q < per_read; ++q, ++r) launch(r, d_count + q);
+        HIP_TRY(h, hipGetLastError());
+        launched += per_read;
+        HIP_TRY(h, hipMemcpyAsync(st.p, d_count, 256, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int q = 0; q < per_read; ++q) {
+            done = done || h_count[q] == 0;                                                // a round that changed no block: the fixed point
+            runs += h_count[32 + q];
+        }
+    }
+    return RBPF_OK;
+}
+
+static void relax_stats(uint64_t (&s)[3], long long launched, long long runs, long long pairs) { s[0] = (uint64_t)launched; s[1] = (uint64_t)runs; s[2] = (uint64_t)pairs; }
+
+extern "C" {
+
+// ---- travel cost (kernels_travel.hip) -----------------------------------------------------------------------------------------
 int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, const double* start_xy, int32_t n_start,
                      const double* goal_xy, int32_t n_goals, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* cost,
                      uint16_t* clearance, int32_t* goal_cost, int32_t* rounds) {
@@ -1890,9 +1930,7 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
     const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
     if (ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must hold at most 2^27 cells");
-    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
-    if (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge)
-        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    if (!box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
     const int ng = goal_cost ? n_goals : 0;                                // goals are read only when their cost is asked for
     for (long long k = 0; k < 2LL * n_start; ++k)
         if (!std::isfinite(start_xy[k])) return fail(h, RBPF_EINVAL, "start coordinates must be finite");
@@ -1915,10 +1953,9 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     const size_t per = cost_b + t_b + 2 * dirty_b;
     const size_t in_b = pad(((size_t)n_start + ng) * 8);
     const size_t out_b = dev_out ? 0 : pad(cost ? (size_t)ncell * 4 : 0) + pad(clearance ? (size_t)ncell * 2 : 0) + pad((size_t)np_all * ng * 4);
-    const size_t fixed = in_b + 256 + out_b, limit = (size_t)2 << 30;
-    if (fixed + per > limit) return fail(h, RBPF_ENOMEM, "one particle's travel cost over this box needs more than 2 GiB of scratch: use a smaller box");
-    long long batch = std::min<long long>(std::min<long long>(np_all, 65535), (long long)((limit - fixed) / per));
-    if (const char* e = getenv("RBPF_TRAVEL_BATCH")) batch = std::max(1LL, std::min<long long>(batch, atoll(e)));
+    const size_t fixed = in_b + 256 + out_b;
+    if (fixed + per > RELAX_SCRATCH) return fail(h, RBPF_ENOMEM, "one particle's travel cost over this box needs more than 2 GiB of scratch: use a smaller box");
+    const long long batch = relax_batch(np_all, fixed, per, "RBPF_TRAVEL_BATCH");
     int per_read = TRAVEL_ROUNDS_PER_READ;
     if (const char* e = getenv("RBPF_TRAVEL_ROUNDS_PER_READ")) per_read = std::max(1, std::min(32, atoi(e)));   // measurement switch (tools/README.md)
     HIP_TRY(h, h->reserve(B_TRAVEL, fixed + (size_t)batch * per));
@@ -1947,39 +1984,26 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     unsigned char* work = d.p + at;
     a.cost_out = o_cost; a.clearance = o_clear;
     long long launched = 0, runs = 0;
-    const int32_t* h_count = reinterpret_cast<const int32_t*>(st.p);
     for (long long p0 = 0; p0 < np_all; p0 += batch) {
         const long long nb = std::min<long long>(batch, np_all - p0);
         a.particle = all ? (int)p0 : particle; a.n_part = (int)nb;
-        a.cost = reinterpret_cast<int32_t*>(work); a.cost_stride = (long long)(cost_b / 4);
+        a.ras = reinterpret_cast<int32_t*>(work); a.ras_stride = (long long)(cost_b / 4);
         a.tbits = reinterpret_cast<uint16_t*>(work + (size_t)nb * cost_b); a.t_stride = (long long)(t_b / 2);
         a.dirty = work + (size_t)nb * (cost_b + t_b);
         a.goal_out = o_goal ? o_goal + (size_t)p0 * ng : nullptr;
-        HIP_TRY(h, hipMemsetAsync(a.cost, 0x3f, (size_t)nb * cost_b, h->stream));          // TRAVEL_INF everywhere
+        HIP_TRY(h, hipMemsetAsync(a.ras, 0x3f, (size_t)nb * cost_b, h->stream));          // TRAVEL_INF everywhere
         HIP_TRY(h, hipMemsetAsync(a.dirty, 0, 2 * (size_t)nb * dirty_b, h->stream));
         launch_travel_mask(v, a, h->stream);
         HIP_TRY(h, hipGetLastError());
         // dirty flags: [2][nb][nblk] packed without the padding of dirty_b (2 * nb * nblk <= 2 * nb * dirty_b)
-        bool done = false;
-        for (long long r = 0; !done; ) {
-            if (r > ncell + 1) return fail(h, RBPF_EDEVICE, "internal error: the travel cost did not converge");
-            HIP_TRY(h, hipMemsetAsync(d_count, 0, 256, h->stream));
-            for (int q = 0; q < per_read; ++q, ++r) launch_travel_round(a, (int)(r & 1), d_count + q, h->stream);
-            HIP_TRY(h, hipGetLastError());
-            launched += per_read;
-            HIP_TRY(h, hipMemcpyAsync(st.p, d_count, 256, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (int q = 0; q < per_read; ++q) {
-                done = done || h_count[q] == 0;                                            // a round that changed no block: the fixed point
-                runs += h_count[32 + q];
-            }
-        }
+        if (int rc = relax_rounds(h, st, d_count, ncell + 1, per_read, "internal error: the travel cost did not converge",
+                                  [&](long long r, int32_t* c) { launch_travel_round(a, (int)(r & 1), c, h->stream); }, launched, runs)) return rc;
         launch_travel_output(a, h->stream);
         HIP_TRY(h, hipGetLastError());
         a.clearance = nullptr;
     }
     if (rounds) *rounds = (int32_t)std::min<long long>(launched, INT32_MAX);
-    h->travel_stats[0] = (uint64_t)launched; h->travel_stats[1] = (uint64_t)runs; h->travel_stats[2] = (uint64_t)(nblk * np_all);
+    relax_stats(h->travel_stats, launched, runs, nblk * np_all);
     if (dev_out) return RBPF_OK;
     if (cost) HIP_TRY(h, hipMemcpyAsync(cost, o_cost, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
     if (clearance) HIP_TRY(h, hipMemcpyAsync(clearance, o_clear, (size_t)ncell * 2, hipMemcpyDeviceToHost, h->stream));
@@ -2012,9 +2036,7 @@ int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4,
     if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
     const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
     if (nx > 32768 || ny > 32768 || ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must be at most 32768 cells on a side and hold at most 2^27 cells");
-    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
-    if (box4[0] + off < 0 || box4[1] + off > edge || box4[2] + off < 0 || box4[3] + off > edge)
-        return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    if (!box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
     if (h->scan_begun) return fail(h, RBPF_ESTATE, "frontier regions between rbpf_scan_update_begin and rbpf_scan_update_end");
 
     FrontierArgs a;
@@ -2030,10 +2052,9 @@ int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4,
     const size_t per = lab_b * (table ? 2 : 1) + 2 * dirty_b;
     const size_t counts_b = pad((size_t)np_all * 12), table_b = table ? pad((size_t)np_all * max_regions * 80) : 0;
     const size_t label_b = label && !dev_out ? pad((size_t)ncell * 4) : 0;
-    const size_t fixed = 256 + counts_b + table_b + label_b, limit = (size_t)2 << 30;
-    if (fixed + per > limit) return fail(h, RBPF_ENOMEM, "one particle's frontier regions over this box need more than 2 GiB of scratch: use a smaller box");
-    long long batch = std::min<long long>(std::min<long long>(np_all, 65535), (long long)((limit - fixed) / per));
-    if (const char* e = getenv("RBPF_FRONTIER_BATCH")) batch = std::max(1LL, std::min<long long>(batch, atoll(e)));
+    const size_t fixed = 256 + counts_b + table_b + label_b;
+    if (fixed + per > RELAX_SCRATCH) return fail(h, RBPF_ENOMEM, "one particle's frontier regions over this box need more than 2 GiB of scratch: use a smaller box");
+    const long long batch = relax_batch(np_all, fixed, per, "RBPF_FRONTIER_BATCH");
     HIP_TRY(h, h->reserve(B_FRONTIER, fixed + (size_t)batch * per));
     const Block& d = h->buf[B_FRONTIER];
     Staging& st = h->stage[S_FRONTIER];
@@ -2046,38 +2067,25 @@ int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4,
     unsigned char* work = d.p + fixed;
     HIP_TRY(h, hipMemsetAsync(o_counts, 0, (size_t)np_all * 12, h->stream));
     long long launched = 0, runs = 0;
-    const int32_t* h_count = reinterpret_cast<const int32_t*>(st.p);
     for (long long p0 = 0; p0 < np_all; p0 += batch) {
         const long long nb = std::min<long long>(batch, np_all - p0);
         a.particle = all ? (int)p0 : particle; a.n_part = (int)nb;
-        a.lab = reinterpret_cast<int32_t*>(work); a.lab_stride = (long long)(lab_b / 4);
+        a.ras = reinterpret_cast<int32_t*>(work); a.ras_stride = (long long)(lab_b / 4);
         a.aux = table ? reinterpret_cast<int32_t*>(work + (size_t)nb * lab_b) : nullptr;
         a.dirty = work + (size_t)nb * lab_b * (table ? 2 : 1);
         a.counts = o_counts + 3 * (size_t)p0;
         a.table = table ? o_table + (size_t)p0 * max_regions * 10 : nullptr;
-        HIP_TRY(h, hipMemsetAsync(a.lab, 0x7f, (size_t)nb * lab_b, h->stream));           // FRONTIER_NONE everywhere
+        HIP_TRY(h, hipMemsetAsync(a.ras, 0x7f, (size_t)nb * lab_b, h->stream));           // FRONTIER_NONE everywhere
         HIP_TRY(h, hipMemsetAsync(work + (size_t)nb * lab_b, 0, (size_t)nb * (per - lab_b), h->stream));   // sizes and dirty flags
         launch_frontier_mask(v, a, h->stream);
         HIP_TRY(h, hipGetLastError());
-        // dirty flags: [2][nb][nblk] packed without the padding of dirty_b, as in rbpf_travel_cost
-        bool done = false;
-        for (long long r = 0; !done; ) {
-            if (r > ncell + 1) return fail(h, RBPF_EDEVICE, "internal error: the frontier labels did not converge");
-            HIP_TRY(h, hipMemsetAsync(d_count, 0, 256, h->stream));
-            for (int q = 0; q < TRAVEL_ROUNDS_PER_READ; ++q, ++r) launch_frontier_round(a, (int)(r & 1), d_count + q, h->stream);
-            HIP_TRY(h, hipGetLastError());
-            launched += TRAVEL_ROUNDS_PER_READ;
-            HIP_TRY(h, hipMemcpyAsync(st.p, d_count, 256, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (int q = 0; q < TRAVEL_ROUNDS_PER_READ; ++q) {
-                done = done || h_count[q] == 0;                                            // a round that changed no block: the fixed point
-                runs += h_count[32 + q];
-            }
-        }
+        // dirty flags: [2][nb][nblk] packed without the padding of dirty_b
+        if (int rc = relax_rounds(h, st, d_count, ncell + 1, TRAVEL_ROUNDS_PER_READ, "internal error: the frontier labels did not converge",
+                                  [&](long long r, int32_t* c) { launch_frontier_round(a, (int)(r & 1), c, h->stream); }, launched, runs)) return rc;
         launch_frontier_output(a, h->stream);
         HIP_TRY(h, hipGetLastError());
     }
-    h->frontier_stats[0] = (uint64_t)launched; h->frontier_stats[1] = (uint64_t)runs; h->frontier_stats[2] = (uint64_t)(nblk * np_all);
+    relax_stats(h->frontier_stats, launched, runs, nblk * np_all);
     if (dev_out) return RBPF_OK;
     if (label) HIP_TRY(h, hipMemcpyAsync(label, a.label_out, (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
     if (regions) HIP_TRY(h, hipMemcpyAsync(regions, o_table, (size_t)np_all * max_regions * 80, hipMemcpyDeviceToHost, h->stream));

@@ -6,6 +6,7 @@
 
 #include "../../include/rbpf_hip.h"
 #include "rbpf_math.h"
+#include "rbpf_blockrelax.h"
 
 namespace rbpf {
 
@@ -208,11 +209,9 @@ struct AlignArgs {
 // map, or of a batch of particles' maps.  The box is cut into 64 x 64 blocks, block k = bx * nby + by; a particle of the batch
 // is blockIdx.y.  Cells are box-relative: (i, j) = (X - x0, Y - y0).
 static const int TRAVEL_INF = 0x3f3f3f3f;   // "not reached" in the cost field (the byte 0x3f four times: a memset fills it); 7 * 2^27 < it
-struct TravelArgs {
+struct TravelArgs : BlockRelaxArgs {      // ras: the cost field, TRAVEL_INF on the rim and wherever no path is known yet
     int particle;                      // the first particle of this launch
-    int n_part;                        // particles of this launch (gridDim.y)
     int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
-    int nbx, nby;                      // blocks per axis: ceil(nx / 64), ceil(ny / 64)
     int m;                             // margin read round a block: ceil(clear_max / 5) <= 64
     int inflate, clear_max;            // T needs d > inflate; the clearance output is min(d, clear_max)
     int through_unknown;               // 1: blocked = occupied; 0: blocked = v >= 0
@@ -220,9 +219,7 @@ struct TravelArgs {
     int n_goals;
     const int32_t* starts;             // [n_start][2] box-relative cell, (-1, -1) outside the box
     const int32_t* goals;              // [n_goals][2] likewise
-    int32_t* cost; long long cost_stride; int cw;   // [n_part][nbx * 64 + 2][cw = nby * 64 + 2]: cell (i, j) at [i + 1][j + 1]; the rim stays TRAVEL_INF
     uint16_t* tbits; long long t_stride;            // [n_part][nbx * 64][nby * 4]: bit j & 15 of halfword j >> 4 of row i: cell in T
-    uint8_t* dirty;                    // [2][n_part][nbx * nby]: block changed in the previous / in this round
     uint16_t* clearance;               // [nx][ny] output or null (single particle only)
     int32_t* cost_out;                 // [nx][ny] output or null (single particle only)
     int32_t* goal_out;                 // [n_part][n_goals] output or null
@@ -232,16 +229,12 @@ struct TravelArgs {
 // maps, their connected components and a table of the largest.  Blocks, particles of the batch and box-relative cells as in
 // TravelArgs; the label of a cell is L = i * ny + j.
 static const int FRONTIER_NONE = 0x7f7f7f7f;   // "no frontier cell" in the label raster (the byte 0x7f four times); 2^27 < it
-struct FrontierArgs {
+struct FrontierArgs : BlockRelaxArgs {    // ras: the labels, FRONTIER_NONE on the rim and wherever no frontier cell is
     int particle;                      // the first particle of this launch
-    int n_part;                        // particles of this launch (gridDim.y)
     int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
-    int nbx, nby;                      // blocks per axis: ceil(nx / 64), ceil(ny / 64)
     int clear;                         // no occupied cell within this Chebyshev distance of a frontier cell (0 .. 16)
     int min_size, max_regions;         // the table: regions of at least min_size cells, the max_regions largest
-    int32_t* lab; long long lab_stride; int cw;   // [n_part][nbx * 64 + 2][cw = nby * 64 + 2]: cell (i, j) at [i + 1][j + 1]; FRONTIER_NONE elsewhere
-    int32_t* aux;                      // same layout, preset to 0: at a root (lab == L) the region's size, then -(row + 1) if the table keeps it
-    uint8_t* dirty;                    // [2][n_part][nbx * nby]: block changed in the previous / in this round
+    int32_t* aux;                      // the layout of ras, preset to 0: at a root (ras == L) the region's size, then -(row + 1) if the table keeps it
     int32_t* counts;                   // [n_part][3] |F|, regions, kept regions; preset to 0
     unsigned long long* table;         // [n_part][max_regions][10] the rows of include/rbpf_hip.h (two's complement); null: no table
     int32_t* label_out;                // [nx][ny] output or null (single particle only)
@@ -310,10 +303,10 @@ void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
-void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.cost preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
-void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one relaxation round; d_count[0] += blocks it changed, d_count[32] += blocks that ran
+void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
+void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran
 void launch_travel_output(const TravelArgs& a, hipStream_t s);                   // cost_out and goal_out from the finished field
-void launch_frontier_mask(const DevView& v, const FrontierArgs& a, hipStream_t s);   // a.lab preset to FRONTIER_NONE, a.aux, a.dirty, a.counts to 0: F, its seeds, |F|
+void launch_frontier_mask(const DevView& v, const FrontierArgs& a, hipStream_t s);   // a.ras preset to FRONTIER_NONE, a.aux, a.dirty, a.counts to 0: F, its seeds, |F|
 void launch_frontier_round(const FrontierArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one labelling round; d_count as launch_travel_round
 void launch_frontier_output(const FrontierArgs& a, hipStream_t s);               // from the finished labels: sizes, the table, label_out
 }  // namespace rbpf
