@@ -555,6 +555,36 @@ int  rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4
  * block) pairs}, as rbpf_travel_stats. */
 int  rbpf_frontier_stats(rbpf_handle* h, uint64_t* out3);
 
+/* ---- map scores: how close is a particle's map to a reference map? ----------------------------------------------------------
+ * The box box4 (cells, raster layout and v(X, Y) as for rbpf_travel_cost) of the map of `particle`, v_p, compared cell by cell
+ * with the reference raster `ref`: int8 [x1-x0][y1-y0] in units of quantum as rbpf_load_map takes it, every value in
+ * [min_odds_emp, max_odds_occ] / quantum; r(c) is its value at cell c of the box, and there is no reference outside the box.
+ * occ(x) = x * quantum > occupied_threshold, strict, the test of the tiles' occupancy bits.  A value x has the class F = 0 if
+ * x < 0, O = 2 if occ(x), U = 1 otherwise (unknown cells, and cells that lean occupied but are not past the threshold).
+ *   n[a][b]   = #{c in box : class(v_p(c)) == a and class(r(c)) == b}
+ *   near_m(c) = some cell o with occ(v_p(o)) lies within Chebyshev distance tol of c.  The REAL map decides: o may lie outside
+ *               the box (the map is read over the box grown by tol cells, v = 0 outside the lattice)
+ *   near_r(c) = some cell o IN THE BOX with occ(r(o)) lies within Chebyshev distance tol of c
+ *   hit_m     = #{c in box : occ(v_p(c)) and near_r(c)}        the particle's walls the reference confirms
+ *   hit_r     = #{c in box : occ(r(c)) and near_m(c)}          the reference's walls the particle has found
+ *   l1        = sum over the box of |v_p(c) - r(c)|
+ *   tab       = sum over the box of value_tab[v_p(c) - vmin], vmin = min_odds_emp / quantum; 0 when value_tab is NULL
+ *   scores[13] = {n[F][F], n[F][U], n[F][O], n[U][F], n[U][U], n[U][O], n[O][F], n[O][U], n[O][O], hit_m, hit_r, l1, tab}
+ * particle >= 0: scores is [13].  particle == -1: scores is [P][13], every particle in its own map against the same reference;
+ * exact duplicates left by a resample are computed again.  0 <= tol <= 16.  value_tab is rbpf_view_gain's table (same length,
+ * entries in 0 .. 2^20) or NULL.  The box must hold at least one and at most 2^27 cells and lie in the tile lattice.  Every value
+ * is an exact integer and an order-free sum: bit-identical from call to call.  DESIGN.md 3.14 has the kernels.
+ * A NULL box4, ref or scores, a bad particle, box, tol, table entry or flag, or a reference value out of range is RBPF_EINVAL (a
+ * device reference is checked on the device, and the call waits for the verdict, as rbpf_place_map does); a call between
+ * rbpf_scan_update_begin and _end is RBPF_ESTATE; everything is checked before anything is written.  The call changes no engine
+ * state (maps, tile pool, particles, random streams, counters, duplicate grouping).  It runs on the handle's stream; without
+ * RBPF_SCORE_DEVICE_OUT scores is a host array, complete on return. */
+#define RBPF_SCORE_DEVICE_IN  1u   /* ref is a device pointer, read in stream order, validated on the device */
+#define RBPF_SCORE_DEVICE_OUT 2u   /* scores is a device pointer, written in stream order, no host wait */
+#define RBPF_SCORE_FIELDS 13
+int  rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* ref, int32_t tol,
+                     const int32_t* value_tab, uint32_t flags, int64_t* scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ RBPF_ALIGN_DEVICE_OUT = 1
 RBPF_GAIN_DEVICE_OUT = 1
 RBPF_TRAVEL_DEVICE_OUT, RBPF_TRAVEL_THROUGH_UNKNOWN = 1, 2
 RBPF_FRONTIER_DEVICE_OUT = 1
+RBPF_SCORE_DEVICE_IN, RBPF_SCORE_DEVICE_OUT, RBPF_SCORE_FIELDS = 1, 2, 13
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -134,6 +135,7 @@ PROTOTYPES = {
     "rbpf_travel_stats": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "rbpf_frontier_regions": (C.c_int, [_H, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_frontier_stats": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
+    "rbpf_score_maps": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_int32, _I, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

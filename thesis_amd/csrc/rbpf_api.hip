@@ -2101,4 +2101,74 @@ int rbpf_frontier_stats(rbpf_handle* h, uint64_t* out3) {
     return RBPF_OK;
 }
 
+// ---- map scores (kernels_score.hip) -------------------------------------------------------------------------------------------
+int rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* ref, int32_t tol, const int32_t* value_tab,
+                    uint32_t flags, int64_t* scores) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!box4 || !ref || !scores) return fail(h, RBPF_EINVAL, "box4, ref or scores is NULL");
+    if (flags & ~(RBPF_SCORE_DEVICE_IN | RBPF_SCORE_DEVICE_OUT)) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (tol < 0 || tol > 16) return fail(h, RBPF_EINVAL, "0 <= tol <= 16 is required");
+    if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
+    if (ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must hold at most 2^27 cells");
+    if (!box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
+    const int nv = v.cc.vmax - v.cc.vmin + 1;                              // one entry per lattice value
+    if (v.cc.vmin > 0 || v.cc.vmax < 0 || nv > 256) return fail(h, RBPF_EINVAL, "the lattice values must include 0");
+    if (value_tab)
+        for (int k = 0; k < nv; ++k)
+            if (value_tab[k] < 0 || value_tab[k] > (1 << 20)) return fail(h, RBPF_EINVAL, "value_tab entries must lie in 0 .. 2^20");
+    const bool dev_in = (flags & RBPF_SCORE_DEVICE_IN) != 0, dev_out = (flags & RBPF_SCORE_DEVICE_OUT) != 0;
+    if (!dev_in)
+        for (long long i = 0; i < ncell; ++i)
+            if (ref[i] < v.cc.vmin || ref[i] > v.cc.vmax) return fail(h, RBPF_EINVAL, "reference value outside [min_odds_emp, max_odds_occ]");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map scores between rbpf_scan_update_begin and rbpf_scan_update_end");
+
+    ScoreArgs a;
+    a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
+    a.nbx = (int)((nx + 63) / 64); a.nby = (int)((ny + 63) / 64);
+    a.tol = tol; a.validate = dev_in;
+    const int np_all = particle < 0 ? v.P : 1;
+    const size_t nblk = (size_t)a.nbx * a.nby;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [flag] [table] [host reference] | [near rows] [block sums] [host scores]; the first three are one upload
+    const size_t tab_b = pad((size_t)nv * 4), ref_b = dev_in ? 0 : pad((size_t)ncell), in_b = 256 + tab_b + ref_b;
+    const size_t near_b = pad(nblk * BR_EDGE * 8), sums_b = pad(nblk * 16), out_n = (size_t)np_all * SCORE_FIELDS * 8;
+    HIP_TRY(h, h->reserve(B_SCORE, in_b + near_b + sums_b + (dev_out ? 0 : pad(out_n))));
+    const Block& d = h->buf[B_SCORE];
+    Staging& st = h->stage[S_SCORE];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    memset(st.p, 0, 256 + tab_b);
+    if (value_tab) memcpy(st.p + 256, value_tab, (size_t)nv * 4);
+    if (!dev_in) memcpy(st.p + 256 + tab_b, ref, (size_t)ncell);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    a.bad = d.as<int32_t>();
+    a.table = value_tab ? d.as<const int32_t>(256) : nullptr;
+    a.ref = dev_in ? ref : d.as<const int8_t>(256 + tab_b);
+    a.near_r = d.as<unsigned long long>(in_b);
+    a.ref_sums = d.as<int32_t>(in_b + near_b);
+    long long* o_scores = dev_out ? reinterpret_cast<long long*>(scores) : d.as<long long>(in_b + near_b + sums_b);
+    launch_score_ref(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_in) {                                                          // the verdict, before anything is written
+        int32_t bad = 0;
+        HIP_TRY(h, hipMemcpyAsync(&bad, a.bad, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (bad) return fail(h, RBPF_EINVAL, "reference value outside [min_odds_emp, max_odds_occ]");
+    }
+    HIP_TRY(h, hipMemsetAsync(o_scores, 0, out_n, h->stream));
+    for (int p0 = 0; p0 < np_all; p0 += 65535) {                           // gridDim.y
+        a.particle = particle < 0 ? p0 : particle; a.n_part = std::min(65535, np_all - p0);
+        a.scores = o_scores + (size_t)p0 * SCORE_FIELDS;
+        launch_score_maps(v, a, h->stream);
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(scores, o_scores, out_n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

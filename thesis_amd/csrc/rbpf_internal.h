@@ -240,6 +240,23 @@ struct FrontierArgs : BlockRelaxArgs {    // ras: the labels, FRONTIER_NONE on t
     int32_t* label_out;                // [nx][ny] output or null (single particle only)
 };
 
+// map scores (kernels_score.hip): a box of one particle's map, or of every particle's, compared cell by cell with
+// one reference raster.  Blocks, particles of a launch and box-relative cells as in TravelArgs.
+static const int SCORE_FIELDS = RBPF_SCORE_FIELDS;
+struct ScoreArgs {
+    int particle, n_part;              // the first particle of this launch (blockIdx.y counts from it), particles of the launch
+    int x0, y0, nx, ny;                // the box: first mosaic cell, rows (x1 - x0) and columns (y1 - y0)
+    int nbx, nby;                      // 64 x 64 blocks along x and y
+    int tol;                           // Chebyshev distance within which a wall confirms a wall (0 .. 16)
+    const int8_t* ref;                 // [nx][ny] the reference (device)
+    const int32_t* table;              // [vmax - vmin + 1] or null: tab = 0
+    unsigned long long* near_r;        // [nbx * nby][64] bit j of row i of a block: a reference-occupied cell of the box within tol
+    int32_t* ref_sums;                 // [nbx * nby][4] of the block's cells in the box: reference cells of class F, U, O; sum of |r|
+    int32_t* bad;                      // [1] != 0: a reference value out of range (written only when `validate`)
+    int validate;
+    long long* scores;                 // [n_part][SCORE_FIELDS] of this launch, preset to 0
+};
+
 // kernel launchers (one translation unit per kernel family)
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
                            double* d_out_w, hipStream_t s);
@@ -309,4 +326,6 @@ void launch_travel_output(const TravelArgs& a, hipStream_t s);                  
 void launch_frontier_mask(const DevView& v, const FrontierArgs& a, hipStream_t s);   // a.ras preset to FRONTIER_NONE, a.aux, a.dirty, a.counts to 0: F, its seeds, |F|
 void launch_frontier_round(const FrontierArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one labelling round; d_count as launch_travel_round
 void launch_frontier_output(const FrontierArgs& a, hipStream_t s);               // from the finished labels: sizes, the table, label_out
+void launch_score_ref(const DevView& v, const ScoreArgs& a, hipStream_t s);      // the reference's near_r rows and block sums; a.bad preset to 0
+void launch_score_maps(const DevView& v, const ScoreArgs& a, hipStream_t s);     // a.scores preset to 0; after launch_score_ref
 }  // namespace rbpf

@@ -812,6 +812,91 @@ class ParticleEngine:
         self._check(self._lib.rbpf_frontier_stats(self._h, out))
         return {"rounds": int(out[0]), "block_runs": int(out[1]), "blocks": int(out[2])}
 
+    # -- map scores (include/rbpf_hip.h: rbpf_score_maps; thesis_amd/mapeval.py) --------------------------------
+    def score_maps(self, reference, particle=None, box=None, tol_cells: int = 1, table=None, device: bool = False):
+        """How close the particles' maps are to `reference`: a MapRaster with int8 cells (its box is its own), an int8 array
+        [x1-x0, y1-y0] with `box` = (x0, x1, y0, y1) in mosaic cells, or an int8 torch tensor on the engine's device with `box`
+        (read on the GPU, in torch's stream order).  `particle`: None (every particle in its own map), an index or "best" (the
+        first argmax of weights()).  Returns mapeval.MapScores: the 3 x 3 table n[class of the map][class of the reference] over
+        the classes free, unknown, occupied; hit_m / hit_r, the occupied cells of the map / of the reference that have an
+        occupied cell of the other side within `tol_cells` (0 .. 16) on either axis; l1, the sum of |v - r|; tab, the sum of
+        table[v - vmin] over the box (`table` as view_gain's, default explore.entropy_table(cfg): tab / 65536 is the map's
+        entropy in bits).  All exact integers; leading shape [P] with particle=None.  device=True: the raw int64 tensor
+        [..., 13] on the engine's device (the fields in the order of include/rbpf_hip.h), ready for work on torch's current
+        stream; mapeval.MapScores.from_fields reads it."""
+        from .mapeval import MapScores
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        p = -1 if particle is None else int(particle)
+        cells = reference
+        if hasattr(reference, "cells") and hasattr(reference, "x0"):      # a MapRaster
+            if reference.cells is None:
+                raise ValueError("the reference raster has no int8 cells (a whole-filter render has prob / occ_frac): "
+                                 "mapeval.consensus converts them")
+            if abs(float(reference.quantum) - float(self.cfg.quantum)) > 1e-9 * abs(float(self.cfg.quantum)):
+                raise ValueError(f"reference quantum = {reference.quantum!r} differs from the engine's {self.cfg.quantum!r}")
+            cells = reference.cells
+            if box is None:
+                box = (reference.x0, reference.x0 + int(cells.shape[0]), reference.y0, reference.y0 + int(cells.shape[1]))
+        if box is None:
+            raise ValueError("an array reference needs box = (x0, x1, y0, y1)")
+        b = np.array([int(x) for x in box], dtype=np.int32)
+        if b.shape != (4,):
+            raise ValueError("box must be (x0, x1, y0, y1)")
+        shape = (int(b[1]) - int(b[0]), int(b[3]) - int(b[2]))
+        flags, cur, same_stream = 0, None, False
+        if hasattr(cells, "data_ptr"):                   # a torch tensor
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
+                raise ValueError(f"a tensor reference must be 2-D int8 on {dev}")
+            cells = cells.contiguous()
+            have, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr() or 1), _lib.RBPF_SCORE_DEVICE_IN
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+        else:
+            a = np.asarray(cells)
+            if a.ndim != 2:
+                raise ValueError("reference cells must be 2-D [nx][ny]")
+            if a.dtype != np.int8:
+                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
+                    raise ValueError("reference cells must be int8 lattice values")
+            cells = np.ascontiguousarray(a, dtype=np.int8)
+            have, ptr = cells.shape, C.c_void_p(cells.ctypes.data or 1)
+        if tuple(have) != shape:
+            raise ValueError(f"reference shape {tuple(have)} differs from the box's {shape}")
+        nv = int(round((float(self.cfg.max_odds_occ) - float(self.cfg.min_odds_emp)) / float(self.cfg.quantum))) + 1
+        if table is None:
+            from .explore import entropy_table
+            table = entropy_table(self.cfg)
+        tab = np.ascontiguousarray(table, dtype=np.int32)
+        if tab.shape != (nv,):
+            raise ValueError(f"table must have {nv} entries, one per lattice value")
+        oshape = ((self.P,) if p < 0 else ()) + (_lib.RBPF_SCORE_FIELDS,)
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            if cur is None:
+                cur = torch.cuda.current_stream(dev)
+                same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            out = torch.empty(oshape, dtype=torch.int64, device=dev)
+            optr = C.c_void_p(out.data_ptr())
+            flags |= _lib.RBPF_SCORE_DEVICE_OUT
+        else:
+            out = np.empty(oshape, dtype=np.int64)
+            optr = C.c_void_p(out.ctypes.data)
+        if cur is not None and not same_stream:
+            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
+        self._check(self._lib.rbpf_score_maps(self._h, p, _ip(b), ptr, int(tol_cells), _ip(tab), flags, optr))
+        if device and not same_stream:
+            self.synchronize()
+        del cells                                        # kept alive until the call returned
+        if device:
+            return out
+        return MapScores.from_fields(out, tuple(int(x) for x in b), int(tol_cells), float(self.cfg.quantum))
+
     # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
     def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):
         """Scores the scan (`ranges` [B], `angles` [B], sensor frame) at every observed-free cell and each of `n_rot`
