@@ -585,6 +585,76 @@ int  rbpf_frontier_stats(rbpf_handle* h, uint64_t* out3);
 int  rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const int8_t* ref, int32_t tol,
                      const int32_t* value_tab, uint32_t flags, int64_t* scores);
 
+/* ---- pose estimate and trajectory log: where is the robot, and where has every particle been? ----------------------------------
+ * The estimate row of a set of poses (x_j, y_j, th_j) with weights w_j >= 0.  weights_mode:
+ *   RBPF_W_UNIFORM   w_j = 1
+ *   RBPF_W_RESAMPLE  the distribution the resample draws from (main.py:52-56) of the filter's current weights: -inf -> 0, then,
+ *                    if the smallest value is negative, its magnitude is added to every non-zero value
+ *   RBPF_W_GIVEN     `weights`: P host float64, none negative (RBPF_EINVAL)
+ * A particle with w_j = 0, or with a non-finite pose or weight, contributes nothing.  Over the others, in float64:
+ *   W = sum w    mx = sum w x / W    my = sum w y / W    S = sum w sin th    C = sum w cos th    mth = atan2(S, C)    R = hypot(S, C) / W
+ *   d_j = (x_j - mx, y_j - my, wrap(th_j - mth)),  wrap(a) = remainder(a, 6.283185307179586) moved from -pi to pi: into (-pi, pi]
+ *   c   = sum w d d^T / W        n_eff = W^2 / sum w^2
+ *   f64 row [RBPF_EST_F64] = {mx, my, mth, cxx, cxy, cxth, cyy, cyth, cthth, R, W, n_eff, 0, 0, 0, 0}; with W = 0 the twelve values
+ *                            are NaN
+ *   i32 row [RBPF_EST_I32] = {best, n_used, n_alive, 0}: best = the first argmax of the filter's current raw weights whatever the
+ *                            mode (a NaN counts as the largest, as np.argmax), n_used = contributing particles, n_alive = -1
+ *                            wherever no lineage table is involved
+ * The sums run in a fixed order: two calls on the same state return identical bits.
+ * rbpf_estimate: the row of the current poses; needs no tracking, changes no engine state, complete on return. */
+#define RBPF_W_UNIFORM  0
+#define RBPF_W_RESAMPLE 1
+#define RBPF_W_GIVEN    2
+#define RBPF_EST_F64 16
+#define RBPF_EST_I32 4
+int  rbpf_estimate(rbpf_handle* h, int32_t weights_mode, const double* weights, double* out16, int32_t* out4);
+/* The log.  rbpf_track_begin allocates `capacity` (1 .. 65535 * RBPF_TRACK_CHUNK) records in device memory, 28 bytes per particle
+ * and record (rbpf_track_record_bytes), and writes record 0 from the current state.  A record holds bit copies of every particle's
+ * pose, parent[j] = the index in the record before of the particle that j continues (record 0: the identity), and the estimate row
+ * of that moment (RBPF_W_RESAMPLE, n_alive = -1).  Between records every local resample composes its ancestors onto a pending
+ * map on the device (it reads the device's did-resample flag; the host reads nothing, rbpf_resample without outputs stays
+ * asynchronous); a record takes parent = pending and resets it.  Records are written
+ *   by rbpf_track_begin (record 0) and rbpf_track_record;
+ *   at the end of rbpf_imu_update with RBPF_TRACK_IMU;
+ *   at the end of rbpf_scan_update / rbpf_scan_update_end with RBPF_TRACK_SCAN (never by rbpf_map_update or rbpf_weight_samples),
+ * all in stream order, nothing waits.  With the log full an implicit record is dropped and counted in `dropped` (the call it
+ * belongs to still succeeds and pending keeps composing); rbpf_track_record returns RBPF_ENOMEM.
+ * Off by default, and then the launches are exactly those of a handle that never heard of it; the same again after
+ * rbpf_track_end, which frees the log.  Lineages across ranks are not followed: while tracking is on,
+ * rbpf_apply_resample_local and rbpf_unpack_particles return RBPF_ESTATE.
+ * RBPF_ESTATE: any rbpf_track_* call but _begin and _record_bytes while tracking is off, and _begin while it is on.  RBPF_EINVAL: a
+ * bad capacity, flag, mode, NULL pattern, a range that is not 0 <= t0 < t1 <= n_records, a particle outside 0 .. P-1; checked
+ * before anything is queued, and nothing is written. */
+#define RBPF_TRACK_IMU   1u        /* rbpf_imu_update records */
+#define RBPF_TRACK_SCAN  2u        /* rbpf_scan_update / rbpf_scan_update_end record */
+#define RBPF_TRACK_CHUNK 64        /* records per chunk of the walk back */
+#define RBPF_TRACK_DEVICE_OUT 1u   /* out_idx / out_pose are device pointers, written in stream order, no host wait */
+int  rbpf_track_begin(rbpf_handle* h, int32_t capacity, uint32_t flags);
+int  rbpf_track_end(rbpf_handle* h);
+int  rbpf_track_record(rbpf_handle* h);
+/* any output may be NULL */
+int  rbpf_track_info(rbpf_handle* h, int32_t* n_records, int32_t* capacity, int32_t* dropped, uint32_t* flags);
+/* The lineage of the CURRENT particles `particles`[n] (NULL, 0: all P, n = P): out_idx[t - t0][k] (int32) = the index in record t
+ * of the ancestor of current particle particles[k], through every resample since, those after the last record included;
+ * out_pose[t - t0][k][3] (float64) = that ancestor's recorded pose.  Either output may be NULL, not both.  Without
+ * RBPF_TRACK_DEVICE_OUT the outputs are host arrays, complete on return. */
+int  rbpf_track_lineage(rbpf_handle* h, int32_t t0, int32_t t1, const int32_t* particles, int32_t n, void* out_idx, void* out_pose,
+                        uint32_t flags);
+/* The smoothed trajectory: out_f64[t - t0][RBPF_EST_F64], out_i32[t - t0][RBPF_EST_I32] = the estimate row over the poses at
+ * record t of the current particles' ancestors, with the FINAL weights (weights_mode / weights as rbpf_estimate); n_alive = the
+ * number of distinct ancestors at record t.  P <= 65536 (RBPF_EINVAL).  Host outputs, either may be NULL, complete on return. */
+int  rbpf_track_summary(rbpf_handle* h, int32_t t0, int32_t t1, int32_t weights_mode, const double* weights, double* out_f64,
+                        int32_t* out_i32);
+/* the rows stored at record time (the filtered trajectory); host outputs, either may be NULL, complete on return */
+int  rbpf_track_filtered(rbpf_handle* h, int32_t t0, int32_t t1, double* out_f64, int32_t* out_i32);
+/* Checkpoints.  rbpf_track_export copies the raw records [t0, t1) (0 <= t0 <= t1 <= n_records), rbpf_track_record_bytes(h) bytes
+ * each (a function of P alone, no tracking needed; -1 for a NULL handle), followed by the pending map (P int32) into host memory.
+ * rbpf_track_import replaces the log of a tracking handle by n such records (1 <= n <= capacity) followed by a pending map;
+ * n_records becomes n.  A parent or pending index outside 0 .. P-1 is RBPF_EINVAL and nothing is replaced. */
+int64_t rbpf_track_record_bytes(rbpf_handle* h);
+int  rbpf_track_export(rbpf_handle* h, int32_t t0, int32_t t1, void* records);
+int  rbpf_track_import(rbpf_handle* h, int32_t n, const void* records);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,9 @@ RBPF_GAIN_DEVICE_OUT = 1
 RBPF_TRAVEL_DEVICE_OUT, RBPF_TRAVEL_THROUGH_UNKNOWN = 1, 2
 RBPF_FRONTIER_DEVICE_OUT = 1
 RBPF_SCORE_DEVICE_IN, RBPF_SCORE_DEVICE_OUT, RBPF_SCORE_FIELDS = 1, 2, 13
+RBPF_W_UNIFORM, RBPF_W_RESAMPLE, RBPF_W_GIVEN = 0, 1, 2
+RBPF_EST_F64, RBPF_EST_I32 = 16, 4
+RBPF_TRACK_IMU, RBPF_TRACK_SCAN, RBPF_TRACK_CHUNK, RBPF_TRACK_DEVICE_OUT = 1, 2, 64, 1
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -136,6 +139,17 @@ PROTOTYPES = {
     "rbpf_frontier_regions": (C.c_int, [_H, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_frontier_stats": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "rbpf_score_maps": (C.c_int, [_H, C.c_int32, _I, C.c_void_p, C.c_int32, _I, C.c_uint32, C.c_void_p]),
+    "rbpf_estimate": (C.c_int, [_H, C.c_int32, _D, _D, _I]),
+    "rbpf_track_begin": (C.c_int, [_H, C.c_int32, C.c_uint32]),
+    "rbpf_track_end": (C.c_int, [_H]),
+    "rbpf_track_record": (C.c_int, [_H]),
+    "rbpf_track_info": (C.c_int, [_H, _I, _I, _I, C.POINTER(C.c_uint32)]),
+    "rbpf_track_lineage": (C.c_int, [_H, C.c_int32, C.c_int32, _I, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rbpf_track_summary": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _D, _D, _I]),
+    "rbpf_track_filtered": (C.c_int, [_H, C.c_int32, C.c_int32, _D, _I]),
+    "rbpf_track_record_bytes": (C.c_int64, [_H]),
+    "rbpf_track_export": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
+    "rbpf_track_import": (C.c_int, [_H, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

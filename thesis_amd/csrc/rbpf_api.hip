@@ -70,6 +70,21 @@ static int check_device_error(rbpf_handle* h) {
 
 static bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && strcmp(e, value) == 0; }
 
+// ---- trajectory log (kernels_track.hip): the pieces the step entry points queue while tracking is on ------------
+// one record from the current state, in stream order.  Log full: an implicit record (a step's own) is dropped and counted, an
+// explicit one is RBPF_ENOMEM; the host knows the count, nothing is read back
+static int track_record(rbpf_handle* h, bool implicit) {
+    if (h->track_n >= h->track_cap) {
+        if (!implicit) return fail(h, RBPF_ENOMEM, "the trajectory log is full");
+        h->track_dropped++;
+        return RBPF_OK;
+    }
+    launch_track_record(h->v, h->track_log(), h->track_n, h->track_pending(h->track_cur), h->stream);
+    HIP_TRY(h, hipGetLastError());
+    h->track_n++;
+    return RBPF_OK;
+}
+
 extern "C" {
 
 int rbpf_default_config(rbpf_config* c) {
@@ -301,6 +316,7 @@ int rbpf_destroy(rbpf_handle* h) {
     if (h->ev_weights_valid && hipEventSynchronize(h->ev_weights) != hipSuccess) (void)hipGetLastError();
     for (Block& b : h->allocs) b.release();
     for (Block& b : h->buf) b.release();
+    for (Block& b : h->track_mem) b.release();
     h->each_staging([](Staging& s) { s.release(); });
     h->each_staging([](Staging& s) { s.destroy_event(); });
     h->events.destroy();
@@ -492,6 +508,7 @@ int rbpf_imu_update(rbpf_handle* h, int32_t model, const double* d, double dt_ti
     if (model < 0 || model > 2) return fail(h, RBPF_EINVAL, "unknown motion model");
     launch_imu_update(h->v, model, d[0], d[1], d[2], dt_ticks, h->cfg.vel_noise, h->stream);
     HIP_TRY(h, hipGetLastError());
+    if (h->track_on && (h->track_flags & RBPF_TRACK_IMU)) return track_record(h, true);
     return RBPF_OK;
 }
 
@@ -639,11 +656,14 @@ int rbpf_scan_update_end(rbpf_handle* h) {
         launch_bad_weight(h->v, h->d_bad, h->stream);
         HIP_TRY(h, hipGetLastError());
         h->scan_updates++;
-        return RBPF_OK;
+    } else {
+        // HybridMap.update at the new mean pose (robot.py:115), then - in the same launch - the robot.py:73-78 weight
+        // increment of the particles on the NaN-covariance branch, on their updated maps
+        const int rc = run_map_update(h, h->d_bad);
+        if (rc) return rc;
     }
-    // HybridMap.update at the new mean pose (robot.py:115), then - in the same launch - the robot.py:73-78 weight
-    // increment of the particles on the NaN-covariance branch, on their updated maps
-    return run_map_update(h, h->d_bad);
+    if (h->track_on && (h->track_flags & RBPF_TRACK_SCAN)) return track_record(h, true);
+    return RBPF_OK;
 }
 
 // ---- read-out of the last proposal (tests): the frame propose_prep_kernel left, the samples of propose_samples_kernel,
@@ -825,6 +845,11 @@ static int resample_local(rbpf_handle* h, const double* d_w, double u, double sp
     h->prof_end(2);
     HIP_TRY(h, hipGetLastError());
     swap_state_buffers(h);
+    if (h->track_on) {                              // pending' = pending o ancestors where the device's flag says a resample happened
+        launch_track_compose(v.P, h->rs.did, h->rs.idx, h->track_pending(h->track_cur), h->track_pending(h->track_cur ^ 1), h->stream);
+        HIP_TRY(h, hipGetLastError());
+        h->track_cur ^= 1;
+    }
     v.dups_valid = h->dedup_enabled ? 1 : 0;
     if (h->match_rows == 2) h->match_rows = 0;      // the duplicate groups the matcher skipped are overwritten
     return RBPF_OK;
@@ -941,6 +966,7 @@ int rbpf_apply_resample_local(rbpf_handle* h, const int32_t* new_src, const int3
     if (!h || !new_src || !new_global_id) return RBPF_EINVAL;
     ON_DEVICE(h);
     DevView& v = h->v;
+    if (h->track_on) return fail(h, RBPF_ESTATE, "the trajectory log does not follow lineages across ranks: rbpf_track_end first");
     // sources must be sorted ascending with the arrivals (-1) last: duplicates of one ancestor are then adjacent
     for (int j = 1; j < v.P; ++j) {
         bool ok = new_src[j] < 0 ? true : (new_src[j - 1] >= 0 && new_src[j - 1] <= new_src[j]);
@@ -1062,6 +1088,7 @@ int rbpf_pack_particles_raw(rbpf_handle* h, const int32_t* local_idx, int32_t n,
 int rbpf_unpack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, const void* d_buf, const int32_t* meta_in) {
     if (!h || n < 0 || (n > 0 && (!local_idx || !d_buf || !meta_in))) return RBPF_EINVAL;
     ON_DEVICE(h);
+    if (h->track_on) return fail(h, RBPF_ESTATE, "the trajectory log does not follow lineages across ranks: rbpf_track_end first");
     if (n == 0) return RBPF_OK;
     DevView& v = h->v;
     const int LL = v.L * v.L, W = 2 + 6 * LL;
@@ -2168,6 +2195,241 @@ int rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     if (dev_out) return RBPF_OK;
     HIP_TRY(h, hipMemcpyAsync(scores, o_scores, out_n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+}  // extern "C"
+
+// ---- pose estimate and trajectory log (kernels_track.hip) -------------------------------------------------------
+static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int check_weights_mode(rbpf_handle* h, int32_t mode, const double* weights) {
+    if (mode != RBPF_W_UNIFORM && mode != RBPF_W_RESAMPLE && mode != RBPF_W_GIVEN) return fail(h, RBPF_EINVAL, "unknown weights_mode");
+    if ((mode == RBPF_W_GIVEN) != (weights != nullptr)) return fail(h, RBPF_EINVAL, "weights go with RBPF_W_GIVEN, and only with it");
+    if (weights)
+        for (int j = 0; j < h->v.P; ++j)
+            if (weights[j] < 0) return fail(h, RBPF_EINVAL, "a given weight is negative");
+    return RBPF_OK;
+}
+
+static int track_state_and_range(rbpf_handle* h, int32_t t0, int32_t t1) {
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    if (t0 < 0 || t0 >= t1 || t1 > h->track_n) return fail(h, RBPF_EINVAL, "0 <= t0 < t1 <= n_records is required");
+    return RBPF_OK;
+}
+
+// scratch of a walk over [t0, n_records): comp and start, rows counted from the chunk of t0
+static size_t track_walk_bytes(const rbpf_handle* h, int t0, int n) {
+    const size_t chunks = (size_t)((h->track_n - 1) / RBPF_TRACK_CHUNK - t0 / RBPF_TRACK_CHUNK + 1);
+    return pad256(chunks * h->v.P * 4) + pad256(chunks * (size_t)n * 4);
+}
+
+// queues the three stages; the scratch of track_walk_bytes starts at B_TRACK + off
+static int track_walk(rbpf_handle* h, int t0, int t1, const int32_t* d_particles, int n, size_t off, int32_t* d_idx, double* d_pose) {
+    TrackWalk q;
+    q.g = h->track_log();
+    q.t0 = t0; q.t1 = t1; q.N = h->track_n;
+    q.c0 = t0 / RBPF_TRACK_CHUNK; q.c1 = (h->track_n - 1) / RBPF_TRACK_CHUNK;
+    q.n = n; q.particles = d_particles; q.pending = h->track_pending(h->track_cur);
+    q.comp = h->buf[B_TRACK].as<int32_t>(off);
+    q.start = h->buf[B_TRACK].as<int32_t>(off + pad256((size_t)(q.c1 - q.c0 + 1) * h->v.P * 4));
+    q.out_idx = d_idx; q.out_pose = d_pose;
+    launch_track_walk(q, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return RBPF_OK;
+}
+
+extern "C" {
+
+int rbpf_estimate(rbpf_handle* h, int32_t mode, const double* weights, double* out16, int32_t* out4) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!out16 || !out4) return fail(h, RBPF_EINVAL, "out16 or out4 is NULL");
+    int rc = check_weights_mode(h, mode, weights);
+    if (rc) return rc;
+    const size_t w_b = pad256((size_t)h->v.P * 8);
+    HIP_TRY(h, h->reserve(B_TRACK, w_b + 256));
+    const Block& d = h->buf[B_TRACK];
+    if (weights) {
+        Staging& st = h->stage[S_TRACK];
+        HIP_TRY(h, st.begin(w_b));
+        memcpy(st.p, weights, (size_t)h->v.P * 8);
+        HIP_TRY(h, st.upload(d.p, (size_t)h->v.P * 8, h->stream));
+    }
+    launch_estimate(h->v, weights ? d.as<const double>() : nullptr, mode, d.as<double>(w_b), d.as<int32_t>(w_b + RBPF_EST_F64 * 8), h->stream);
+    HIP_TRY(h, hipGetLastError());
+    unsigned char row[RBPF_EST_F64 * 8 + RBPF_EST_I32 * 4];
+    HIP_TRY(h, hipMemcpyAsync(row, d.p + w_b, sizeof(row), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memcpy(out16, row, RBPF_EST_F64 * 8);
+    memcpy(out4, row + RBPF_EST_F64 * 8, RBPF_EST_I32 * 4);
+    return RBPF_OK;
+}
+
+int rbpf_track_begin(rbpf_handle* h, int32_t capacity, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (h->track_on) return fail(h, RBPF_ESTATE, "tracking is already on");
+    if (capacity < 1 || capacity > 65535 * RBPF_TRACK_CHUNK) return fail(h, RBPF_EINVAL, "1 <= capacity <= 65535 * RBPF_TRACK_CHUNK is required");
+    if (flags & ~(RBPF_TRACK_IMU | RBPF_TRACK_SCAN)) return fail(h, RBPF_EINVAL, "unknown flags");
+    const size_t P = h->v.P, stride = track_record_stride(h->v.P);
+    if (h->track_mem[rbpf_handle::T_LOG].reserve((size_t)capacity * stride) != hipSuccess ||
+        h->track_mem[rbpf_handle::T_PENDING].reserve(2 * P * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        for (Block& b : h->track_mem) b.release();
+        return fail(h, RBPF_ENOMEM, "no device memory for " + std::to_string(capacity) + " records of " + std::to_string(stride) + " bytes");
+    }
+    std::vector<int32_t> id(P);
+    for (size_t j = 0; j < P; ++j) id[j] = (int32_t)j;
+    HIP_TRY(h, hipMemcpyAsync(h->track_pending(0), id.data(), P * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));           // id dies on return
+    h->track_on = true; h->track_flags = flags; h->track_cap = capacity; h->track_n = 0; h->track_dropped = 0; h->track_cur = 0;
+    return track_record(h, false);
+}
+
+int rbpf_track_end(rbpf_handle* h) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));           // queued records and walks still use the log
+    for (Block& b : h->track_mem) b.release();
+    h->track_on = false; h->track_flags = 0; h->track_cap = h->track_n = h->track_dropped = h->track_cur = 0;
+    return RBPF_OK;
+}
+
+int rbpf_track_record(rbpf_handle* h) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    return track_record(h, false);
+}
+
+int rbpf_track_info(rbpf_handle* h, int32_t* n_records, int32_t* capacity, int32_t* dropped, uint32_t* flags) {
+    if (!h) return RBPF_EINVAL;
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    if (n_records) *n_records = h->track_n;
+    if (capacity) *capacity = h->track_cap;
+    if (dropped) *dropped = h->track_dropped;
+    if (flags) *flags = h->track_flags;
+    return RBPF_OK;
+}
+
+int rbpf_track_lineage(rbpf_handle* h, int32_t t0, int32_t t1, const int32_t* particles, int32_t n, void* out_idx, void* out_pose,
+                       uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    int rc = track_state_and_range(h, t0, t1);
+    if (rc) return rc;
+    const int P = h->v.P;
+    if (flags & ~RBPF_TRACK_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (!out_idx && !out_pose) return fail(h, RBPF_EINVAL, "out_idx and out_pose are both NULL");
+    if (particles ? n < 1 : n != 0) return fail(h, RBPF_EINVAL, "particles needs n >= 1; NULL goes with n = 0 (all particles)");
+    for (int k = 0; k < n; ++k)
+        if (particles[k] < 0 || particles[k] >= P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (!particles) n = P;
+    const bool dev_out = (flags & RBPF_TRACK_DEVICE_OUT) != 0;
+    const size_t T = (size_t)(t1 - t0), list_b = particles ? pad256((size_t)n * 4) : 0, walk_b = track_walk_bytes(h, t0, n);
+    const size_t idx_n = T * n * 4, pose_n = T * n * 24;
+    const size_t idx_b = (out_idx && !dev_out) ? pad256(idx_n) : 0, pose_b = (out_pose && !dev_out) ? pad256(pose_n) : 0;
+    HIP_TRY(h, h->reserve(B_TRACK, list_b + walk_b + idx_b + pose_b));
+    const Block& d = h->buf[B_TRACK];
+    if (particles) {
+        Staging& st = h->stage[S_TRACK];
+        HIP_TRY(h, st.begin(list_b));
+        memcpy(st.p, particles, (size_t)n * 4);
+        HIP_TRY(h, st.upload(d.p, (size_t)n * 4, h->stream));
+    }
+    int32_t* d_idx = !out_idx ? nullptr : dev_out ? static_cast<int32_t*>(out_idx) : d.as<int32_t>(list_b + walk_b);
+    double* d_pose = !out_pose ? nullptr : dev_out ? static_cast<double*>(out_pose) : d.as<double>(list_b + walk_b + idx_b);
+    rc = track_walk(h, t0, t1, particles ? d.as<const int32_t>() : nullptr, n, list_b, d_idx, d_pose);
+    if (rc || dev_out) return rc;
+    if (out_idx) HIP_TRY(h, hipMemcpyAsync(out_idx, d_idx, idx_n, hipMemcpyDeviceToHost, h->stream));
+    if (out_pose) HIP_TRY(h, hipMemcpyAsync(out_pose, d_pose, pose_n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_track_summary(rbpf_handle* h, int32_t t0, int32_t t1, int32_t mode, const double* weights, double* out_f64, int32_t* out_i32) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    int rc = track_state_and_range(h, t0, t1);
+    if (rc) return rc;
+    const int P = h->v.P;
+    if (P > TRACK_SUMMARY_MAX_P) return fail(h, RBPF_EINVAL, "rbpf_track_summary needs P <= 65536");
+    if ((rc = check_weights_mode(h, mode, weights))) return rc;
+    const size_t T = (size_t)(t1 - t0), w_b = weights ? pad256((size_t)P * 8) : 0, walk_b = track_walk_bytes(h, t0, P);
+    const size_t lin_b = pad256(T * P * 4), f_n = T * RBPF_EST_F64 * 8, i_n = T * RBPF_EST_I32 * 4;
+    HIP_TRY(h, h->reserve(B_TRACK, w_b + walk_b + lin_b + pad256(f_n) + i_n));
+    const Block& d = h->buf[B_TRACK];
+    if (weights) {
+        Staging& st = h->stage[S_TRACK];
+        HIP_TRY(h, st.begin(w_b));
+        memcpy(st.p, weights, (size_t)P * 8);
+        HIP_TRY(h, st.upload(d.p, (size_t)P * 8, h->stream));
+    }
+    int32_t* d_lin = d.as<int32_t>(w_b + walk_b);
+    double* d_f = d.as<double>(w_b + walk_b + lin_b);
+    int32_t* d_i = d.as<int32_t>(w_b + walk_b + lin_b + pad256(f_n));
+    if ((rc = track_walk(h, t0, t1, nullptr, P, w_b, d_lin, nullptr))) return rc;
+    launch_track_summary(h->track_log(), t0, t1, d_lin, h->v.weight, weights ? d.as<const double>() : nullptr, mode, d_f, d_i, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (out_f64) HIP_TRY(h, hipMemcpyAsync(out_f64, d_f, f_n, hipMemcpyDeviceToHost, h->stream));
+    if (out_i32) HIP_TRY(h, hipMemcpyAsync(out_i32, d_i, i_n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_track_filtered(rbpf_handle* h, int32_t t0, int32_t t1, double* out_f64, int32_t* out_i32) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const int rc = track_state_and_range(h, t0, t1);
+    if (rc) return rc;
+    const TrackLog g = h->track_log();
+    const unsigned char* first = g.base + (size_t)t0 * g.stride;
+    const size_t T = (size_t)(t1 - t0), fw = RBPF_EST_F64 * 8, iw = RBPF_EST_I32 * 4;
+    if (out_f64) HIP_TRY(h, hipMemcpy2DAsync(out_f64, fw, first + (size_t)g.P * 24, g.stride, fw, T, hipMemcpyDeviceToHost, h->stream));
+    if (out_i32) HIP_TRY(h, hipMemcpy2DAsync(out_i32, iw, first + track_parent_offset(g.P) + (size_t)g.P * 4, g.stride, iw, T, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int64_t rbpf_track_record_bytes(rbpf_handle* h) { return h ? (int64_t)track_record_stride(h->v.P) : -1; }
+
+int rbpf_track_export(rbpf_handle* h, int32_t t0, int32_t t1, void* records) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    if (!records || t0 < 0 || t0 > t1 || t1 > h->track_n) return fail(h, RBPF_EINVAL, "records is NULL, or not 0 <= t0 <= t1 <= n_records");
+    const TrackLog g = h->track_log();
+    const size_t bytes = (size_t)(t1 - t0) * g.stride;
+    if (bytes) HIP_TRY(h, hipMemcpyAsync(records, g.base + (size_t)t0 * g.stride, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(static_cast<unsigned char*>(records) + bytes, h->track_pending(h->track_cur), (size_t)g.P * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_track_import(rbpf_handle* h, int32_t n, const void* records) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!h->track_on) return fail(h, RBPF_ESTATE, "tracking is off: rbpf_track_begin first");
+    if (!records || n < 1 || n > h->track_cap) return fail(h, RBPF_EINVAL, "records is NULL, or not 1 <= n <= capacity");
+    const TrackLog g = h->track_log();
+    const unsigned char* src = static_cast<const unsigned char*>(records);
+    const size_t bytes = (size_t)n * g.stride, P = (size_t)g.P;
+    for (int t = 0; t <= n; ++t) {                         // the parents of every record, then the pending map: the walk gathers through them
+        int32_t k[64];
+        const unsigned char* row = t < n ? src + (size_t)t * g.stride + track_parent_offset(g.P) : src + bytes;
+        for (size_t j = 0; j < P; j += 64) {
+            const size_t m = std::min<size_t>(64, P - j);
+            memcpy(k, row + j * 4, m * 4);
+            for (size_t i = 0; i < m; ++i)
+                if (k[i] < 0 || k[i] >= g.P) return fail(h, RBPF_EINVAL, "a parent or pending index lies outside 0 .. P-1");
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(g.base, src, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->track_pending(h->track_cur), src + bytes, P * 4, hipMemcpyHostToDevice));
+    h->track_n = n;
     return RBPF_OK;
 }
 

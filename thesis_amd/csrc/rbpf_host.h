@@ -41,8 +41,9 @@ struct Block {
 // outputs of an alignment; poses, beams, table and host outputs of a view gain; start and goal cells, round counters, cost fields,
 // traversable bits, dirty flags and host outputs of a travel cost; round counters, region counts, tables, label and size rasters,
 // dirty flags and the host label output of a frontier labelling; reference raster, table, flag, near rows, block sums and the
-// host score output of a map scoring
-enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_SCORE, B_COUNT };
+// host score output of a map scoring; particle list or weights, chunk maps, chunk starts, lineage table and host outputs of a
+// trajectory read-out or an estimate
+enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_SCORE, B_TRACK, B_COUNT };
 
 // A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
 // early error return cannot pull memory from under queued work.
@@ -75,8 +76,8 @@ struct Staging : Block {
 // job lists of the pack / unpack kernels and the landing zone of the early resample read-back (pinned); the blocks uploaded
 // into B_RENDER, B_CAST, B_LOAD, B_LOCATE, B_PLACE, B_ALIGN and B_GAIN (pageable); the round counters a travel cost reads back
 // and, behind them, the block it uploads into B_TRAVEL (pinned); the round counters a frontier labelling reads back (pinned);
-// the table and the host reference uploaded into B_SCORE (pageable)
-enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_SCORE, S_COUNT };
+// the table and the host reference uploaded into B_SCORE (pageable); the particle list or the weights uploaded into B_TRACK (pageable)
+enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_SCORE, S_TRACK, S_COUNT };
 
 // Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
 // copy that read it has completed (its event), so uploading never drains the stream.
@@ -129,7 +130,7 @@ struct rbpf_handle {
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;
@@ -180,4 +181,11 @@ struct rbpf_handle {
     double* d_prop_w = nullptr;
     uint64_t travel_stats[3] = {0, 0, 0};      // rbpf_travel_stats: rounds, block runs, (particle, block) pairs of the last rbpf_travel_cost
     uint64_t frontier_stats[3] = {0, 0, 0};    // rbpf_frontier_stats: the same of the last rbpf_frontier_regions
+    // rbpf_track_*: the trajectory log.  Off unless rbpf_track_begin was called
+    bool track_on = false; uint32_t track_flags = 0;
+    int track_cap = 0, track_n = 0, track_dropped = 0, track_cur = 0;   // records allocated, written, dropped; which half of T_PENDING is current
+    enum { T_LOG, T_PENDING, T_COUNT };
+    Block track_mem[T_COUNT];                  // the records; pending[2][P], swapped after every local resample
+    rbpf::TrackLog track_log() const { return {track_mem[T_LOG].p, rbpf::track_record_stride(v.P), v.P}; }
+    int32_t* track_pending(int which) const { return track_mem[T_PENDING].as<int32_t>((size_t)which * v.P * 4); }
 };

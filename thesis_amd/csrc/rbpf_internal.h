@@ -257,7 +257,33 @@ struct ScoreArgs {
     long long* scores;                 // [n_part][SCORE_FIELDS] of this launch, preset to 0
 };
 
+// trajectory log (kernels_track.hip).  A record is `stride` bytes: x[P], y[P], th[P] float64, the estimate row's
+// 16 float64, parent[P] int32, the estimate row's 4 int32, padded to a multiple of 16.
+static const int TRACK_SUMMARY_MAX_P = 65536;   // the P-bit bitmap of track_summary_kernel: 8 KB of LDS
+__host__ __device__ inline size_t track_parent_offset(int P) { return (size_t)P * 24 + RBPF_EST_F64 * 8; }
+__host__ __device__ inline size_t track_record_stride(int P) { return (track_parent_offset(P) + (size_t)P * 4 + RBPF_EST_I32 * 4 + 15) & ~(size_t)15; }
+struct TrackLog { unsigned char* base; size_t stride; int P; };
+// the walk back from the current particles through the records (rbpf_track_lineage, rbpf_track_summary); chunk c = records
+// c * RBPF_TRACK_CHUNK .. + RBPF_TRACK_CHUNK - 1, rows of comp and start are counted from chunk c0
+struct TrackWalk {
+    TrackLog g;
+    int t0, t1, N;                     // records written out [t0, t1); records in the log
+    int c0, c1;                        // chunk of t0, chunk of N - 1
+    int n;                             // walked particles
+    const int32_t* particles;          // [n] current particle indices, or null: all (n == P)
+    const int32_t* pending;            // [P] index at record N - 1 of every current particle
+    int32_t* comp;                     // [c1 - c0 + 1][P] row c - c0: index at the last record of chunk c -> at the last of chunk c - 1 (row 0 unused)
+    int32_t* start;                    // [c1 - c0 + 1][n] row c - c0: index of walked particle j's ancestor at the last record of chunk c
+    int32_t* out_idx; double* out_pose;   // [t1 - t0][n], [t1 - t0][n][3]; either may be null
+};
+
 // kernel launchers (one translation unit per kernel family)
+void launch_track_compose(int P, const int32_t* d_did, const int32_t* d_idx, const int32_t* d_pend, int32_t* d_pend2, hipStream_t s);
+void launch_track_record(const DevView& v, const TrackLog& g, int t, int32_t* d_pend, hipStream_t s);   // record t from the current state; d_pend becomes the identity
+void launch_estimate(const DevView& v, const double* d_given, int mode, double* d_out16, int32_t* d_out4, hipStream_t s);
+void launch_track_walk(const TrackWalk& q, hipStream_t s);                        // the three stages
+void launch_track_summary(const TrackLog& g, int t0, int t1, const int32_t* d_lineage, const double* d_weight, const double* d_given,
+                          int mode, double* d_out_f, int32_t* d_out_i, hipStream_t s);   // d_lineage [t1 - t0][P]
 void launch_weight_samples(const DevView& v, const double* d_guesses, const double* d_prs, int K,
                            double* d_out_w, hipStream_t s);
 void launch_weight_samples_product(const DevView& v, const double* d_guesses, const double* d_prs, int K, double* d_out_w, hipStream_t s);

@@ -54,6 +54,39 @@ class Proposal(NamedTuple):
     raw_w: Any             # [K] raw sample weights (robot.py:138), or None without capture
 
 
+class Estimate(NamedTuple):
+    """ParticleEngine.estimate: the filter's weighted pose estimate (include/rbpf_hip.h: the estimate row)."""
+    pose: np.ndarray       # [3] weighted mean x, y and circular mean heading
+    cov: np.ndarray        # [3, 3] weighted covariance, the heading difference wrapped into (-pi, pi]
+    resultant: float       # mean resultant length of the headings, 1 = all equal
+    n_eff: float           # effective sample size W^2 / sum w^2
+    best: int              # the first argmax of the raw weights
+    n_used: int            # particles that contributed (weight > 0, finite pose and weight)
+    weight_sum: float      # W
+
+
+class TrajectorySummary(NamedTuple):
+    """ParticleEngine.trajectory_summary / filtered_trajectory: one estimate row per record, leading axis T."""
+    pose: np.ndarray       # [T, 3]
+    cov: np.ndarray        # [T, 3, 3]
+    resultant: np.ndarray  # [T]
+    n_eff: np.ndarray      # [T]
+    best: np.ndarray       # [T] int32
+    n_used: np.ndarray     # [T] int32
+    n_alive: np.ndarray    # [T] int32 distinct ancestors of the current particles at the record; -1 in filtered_trajectory
+    weight_sum: np.ndarray  # [T]
+
+
+def _cov_from_rows(f: np.ndarray) -> np.ndarray:
+    """[..., 16] estimate rows -> [..., 3, 3] symmetric covariances."""
+    return f[..., [3, 4, 5, 4, 6, 7, 5, 7, 8]].reshape(f.shape[:-1] + (3, 3))
+
+
+def _summary_from_rows(f: np.ndarray, i: np.ndarray) -> TrajectorySummary:
+    return TrajectorySummary(pose=f[:, 0:3].copy(), cov=_cov_from_rows(f), resultant=f[:, 9].copy(), n_eff=f[:, 11].copy(),
+                             best=i[:, 0].copy(), n_used=i[:, 1].copy(), n_alive=i[:, 2].copy(), weight_sum=f[:, 10].copy())
+
+
 class RbpfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"librbpf_hip error {code}: {msg}")
@@ -288,10 +321,11 @@ class ParticleEngine:
         self._check(self._lib.rbpf_native_sincosf(self._h, x.ctypes.data_as(fp), len(x), s.ctypes.data_as(fp), c.ctypes.data_as(fp)))
         return s, c
 
-    def resample(self, u: float = float("nan")) -> Tuple[bool, np.ndarray]:
-        idx = np.empty(self.P, dtype=np.int32)
+    def resample(self, u: float = float("nan"), indices: bool = True) -> Tuple[bool, Optional[np.ndarray]]:
+        """(did it resample, ancestor index of every new particle); indices=False reads only the flag back: (did, None)."""
+        idx = np.empty(self.P, dtype=np.int32) if indices else None
         did = C.c_int32()
-        self._check(self._lib.rbpf_resample(self._h, float(u), _ip(idx), C.byref(did)))
+        self._check(self._lib.rbpf_resample(self._h, float(u), None if idx is None else _ip(idx), C.byref(did)))
         return bool(did.value), idx
 
     def resample_async(self, u: float = float("nan")):
@@ -489,7 +523,8 @@ class ParticleEngine:
 
     def save_checkpoint(self, path: str):
         """Everything needed to continue the run bit-identically, as one compressed .npz: configuration, particle
-        state, the position of the random streams and every tile (cropped to its non-zero box)."""
+        state, the position of the random streams and every tile (cropped to its non-zero box); with tracking on also the
+        trajectory log (track_state, track_records), so that a continued run has the trajectories of an uninterrupted one."""
         import json
         su, rd = C.c_uint64(), C.c_uint64()
         self._check(self._lib.rbpf_get_rng_state(self._h, C.byref(su), C.byref(rd)))
@@ -506,7 +541,8 @@ class ParticleEngine:
                             rng_state=np.array([su.value, rd.value], dtype=np.uint64), map_updates=np.array(int(self.map_updates)),
                             tile_owner=np.array(owner, dtype=np.int32), tile_centre=np.array(centre, dtype=np.float64).reshape(-1, 2),
                             tile_box=np.array(box, dtype=np.int32).reshape(-1, 4),
-                            tile_cells=np.concatenate(chunks) if chunks else np.empty(0, dtype=np.int8))
+                            tile_cells=np.concatenate(chunks) if chunks else np.empty(0, dtype=np.int8),
+                            **(self._track_export() or {}))
 
     @classmethod
     def from_checkpoint(cls, path: str, device: int = 0) -> "ParticleEngine":
@@ -530,6 +566,8 @@ class ParticleEngine:
                 cells[b[0]:b[1], b[2]:b[3]] = d["tile_cells"][off:off + n].reshape(b[1] - b[0], b[3] - b[2])
                 off += n
                 e.set_tile(int(p), c, cells)
+            if "track_records" in d.files:               # absent in older checkpoints and without tracking: no log
+                e._track_import(d["track_state"], d["track_records"])
         return e
 
     # -- map read-out (include/rbpf_hip.h: rbpf_map_extent, rbpf_render_map; thesis_amd/mapio.py) -----------------------
@@ -1024,6 +1062,136 @@ class ParticleEngine:
             return self.align_points(occ_xy, free_xy, particle=p, box=bx, n_rot=nr, rot_window=(r_begin, r_count))[:2]
         return align.align_map(search, src, float(self.cfg.occupied_threshold), float(self.cfg.tile_len_m) / self.dim, box, limits,
                                k=k, n_rot=n_rot, refine=refine)
+
+    # -- pose estimate and trajectory log (include/rbpf_hip.h: rbpf_estimate, rbpf_track_*; thesis_amd/trajectory.py) --
+    WEIGHT_MODES = {"uniform": _lib.RBPF_W_UNIFORM, "resample": _lib.RBPF_W_RESAMPLE}
+
+    def _weights_arg(self, weights):
+        """(mode, array kept alive or None) of a `weights` argument: "resample", "uniform" or None (uniform), or P values."""
+        if weights is None:
+            return _lib.RBPF_W_UNIFORM, None
+        if isinstance(weights, str):
+            if weights not in self.WEIGHT_MODES:
+                raise ValueError(f"unknown weights {weights!r}")
+            return self.WEIGHT_MODES[weights], None
+        w = _f64(weights)
+        if w.shape != (self.P,):
+            raise ValueError(f"weights must have shape ({self.P},)")
+        return _lib.RBPF_W_GIVEN, w
+
+    def estimate(self, weights="resample") -> Estimate:
+        """The filter's pose estimate, computed on the device: weighted mean pose (circular mean heading), covariance, mean
+        resultant length, effective sample size and the heaviest particle.  `weights`: "resample" (resample_weights of
+        weights(), the distribution the resample draws from), "uniform" / None, or P non-negative values.  A particle with
+        weight 0 or a non-finite pose or weight is left out.  Needs no tracking; two calls on the same state agree bit for bit."""
+        mode, w = self._weights_arg(weights)
+        f, i = np.empty(_lib.RBPF_EST_F64), np.empty(_lib.RBPF_EST_I32, dtype=np.int32)
+        self._check(self._lib.rbpf_estimate(self._h, mode, None if w is None else _dp(w), _dp(f), _ip(i)))
+        return Estimate(pose=f[0:3].copy(), cov=_cov_from_rows(f), resultant=float(f[9]), n_eff=float(f[11]), best=int(i[0]),
+                        n_used=int(i[1]), weight_sum=float(f[10]))
+
+    def track(self, capacity: int, imu: bool = False, scan: bool = True):
+        """Starts the trajectory log on the device: room for `capacity` records of every particle's pose and parent (28 bytes per
+        particle and record), record 0 from the current state.  scan=True: every scan_update / scan_update_end records;
+        imu=True: every imu_update too; record() adds one at any time.  Nothing is read back while the filter runs.  Off by
+        default; untrack() frees the log."""
+        flags = (_lib.RBPF_TRACK_IMU if imu else 0) | (_lib.RBPF_TRACK_SCAN if scan else 0)
+        self._check(self._lib.rbpf_track_begin(self._h, int(capacity), flags))
+
+    def untrack(self):
+        self._check(self._lib.rbpf_track_end(self._h))
+
+    def record(self):
+        """One record of the current state; an RbpfError (RBPF_ENOMEM) when the log is full."""
+        self._check(self._lib.rbpf_track_record(self._h))
+
+    def track_info(self) -> Dict[str, int]:
+        """{"n_records", "capacity", "dropped" (records a full log refused), "imu", "scan"}; an RbpfError with tracking off."""
+        n, cap, dr, fl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint32()
+        self._check(self._lib.rbpf_track_info(self._h, C.byref(n), C.byref(cap), C.byref(dr), C.byref(fl)))
+        return {"n_records": n.value, "capacity": cap.value, "dropped": dr.value, "imu": bool(fl.value & _lib.RBPF_TRACK_IMU),
+                "scan": bool(fl.value & _lib.RBPF_TRACK_SCAN)}
+
+    def lineage(self, particles=None, t0: int = 0, t1: Optional[int] = None, poses: bool = True, device: bool = False):
+        """Where the current particles come from: (idx, pose) with idx int32 [t1-t0, n], the index in record t of the ancestor of
+        current particle particles[k] (None: all P), and pose float64 [t1-t0, n, 3], that ancestor's recorded pose (None with
+        poses=False).  t1 defaults to the number of records.  device=True: torch tensors on the engine's device, ready for
+        work on torch's current stream."""
+        if t1 is None:
+            t1 = self.track_info()["n_records"]
+        pl = None
+        if particles is not None:
+            pl = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
+        n = self.P if pl is None else len(pl)
+        T = max(int(t1) - int(t0), 0)                     # a bad range is the library's to refuse
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            idx = torch.empty((T, n), dtype=torch.int32, device=dev)
+            pose = torch.empty((T, n, 3), dtype=torch.float64, device=dev) if poses else None
+            ptrs = [C.c_void_p(idx.data_ptr() or 1), None if pose is None else C.c_void_p(pose.data_ptr() or 1)]
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            idx = np.empty((T, n), dtype=np.int32)
+            pose = np.empty((T, n, 3), dtype=np.float64) if poses else None
+            ptrs = [C.c_void_p(idx.ctypes.data or 1), None if pose is None else C.c_void_p(pose.ctypes.data or 1)]
+        self._check(self._lib.rbpf_track_lineage(self._h, int(t0), int(t1), None if pl is None else _ip(pl), 0 if pl is None else len(pl),
+                                                 *ptrs, _lib.RBPF_TRACK_DEVICE_OUT if device else 0))
+        if device and not same_stream:
+            self.synchronize()
+        return idx, pose
+
+    def trajectory(self, particle="best") -> np.ndarray:
+        """[T, 3]: the recorded poses of the ancestors of one current particle (an index, or "best": estimate().best), one row
+        per record."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = self.estimate().best
+        return self.lineage([int(particle)])[1][:, 0, :]
+
+    def trajectory_summary(self, weights="resample", t0: int = 0, t1: Optional[int] = None) -> TrajectorySummary:
+        """The smoothed trajectory: per record the estimate (as estimate(), `weights` likewise) over the poses the current
+        particles' ancestors had there, weighted with the FINAL weights, and n_alive, the number of distinct ancestors
+        (trajectory.coalescence finds where the lineages merge).  P <= 65536."""
+        if t1 is None:
+            t1 = self.track_info()["n_records"]
+        mode, w = self._weights_arg(weights)
+        T = max(int(t1) - int(t0), 0)
+        f, i = np.empty((T, _lib.RBPF_EST_F64)), np.empty((T, _lib.RBPF_EST_I32), dtype=np.int32)
+        self._check(self._lib.rbpf_track_summary(self._h, int(t0), int(t1), mode, None if w is None else _dp(w), _dp(f), _ip(i)))
+        return _summary_from_rows(f, i)
+
+    def filtered_trajectory(self, t0: int = 0, t1: Optional[int] = None) -> TrajectorySummary:
+        """The filtered trajectory: the estimate each record stored when it was written (weights "resample" of that moment);
+        n_alive is -1."""
+        if t1 is None:
+            t1 = self.track_info()["n_records"]
+        T = max(int(t1) - int(t0), 0)
+        f, i = np.empty((T, _lib.RBPF_EST_F64)), np.empty((T, _lib.RBPF_EST_I32), dtype=np.int32)
+        self._check(self._lib.rbpf_track_filtered(self._h, int(t0), int(t1), _dp(f), _ip(i)))
+        return _summary_from_rows(f, i)
+
+    def _track_export(self) -> Optional[Dict[str, np.ndarray]]:
+        """The log as checkpoint entries, or None with tracking off."""
+        n, cap, dr, fl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint32()
+        if self._lib.rbpf_track_info(self._h, C.byref(n), C.byref(cap), C.byref(dr), C.byref(fl)) != 0:
+            return None
+        blob = np.empty(n.value * int(self._lib.rbpf_track_record_bytes(self._h)) + 4 * self.P, dtype=np.uint8)
+        self._check(self._lib.rbpf_track_export(self._h, 0, n.value, C.c_void_p(blob.ctypes.data)))
+        return {"track_state": np.array([n.value, cap.value, fl.value], dtype=np.int64), "track_records": blob}
+
+    def _track_import(self, state, blob):
+        n, cap, fl = (int(x) for x in state)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if blob.size != n * int(self._lib.rbpf_track_record_bytes(self._h)) + 4 * self.P:
+            raise ValueError("the checkpoint's trajectory log does not fit this engine")
+        self._check(self._lib.rbpf_track_begin(self._h, cap, fl))
+        self._check(self._lib.rbpf_track_import(self._h, n, C.c_void_p(blob.ctypes.data)))
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)

@@ -118,7 +118,10 @@ class ParticleFilter:
     """NUM_PARTICLES robots (main.py:44,87) as one batched engine."""
 
     def __init__(self, n_particles: int, angles, motion_model: str = "velocity", *, cell_size: float = 0.05,
-                 keep_history: bool = True, seed: int = 42, map_updates: bool = True, **engine_options):
+                 keep_history: bool = True, seed: int = 42, map_updates: bool = True, history: str = "host",
+                 history_capacity: int = 4096, **engine_options):
+        if history not in ("host", "device"):
+            raise ValueError(f"unknown history {history!r}")
         self.angles = np.ascontiguousarray(angles, dtype=np.float64)
         self.engine = ParticleEngine(n_particles, max_beams=len(self.angles), cell_size=cell_size, seed=seed,
                                      pool_tiles=engine_options.pop("pool_tiles", 4 * n_particles + 16), **engine_options)
@@ -126,8 +129,15 @@ class ParticleFilter:
         self.motion_model = motion_model
         self.particles = [Robot(self, i) for i in range(n_particles)]
         self.keep_history = keep_history
-        self._poses: List[np.ndarray] = [self.engine.poses()] if keep_history else []
-        self._ancestors: List[Optional[np.ndarray]] = [None] if keep_history else []
+        # "host": the poses are read back after every step and kept in lists; "device": the engine's trajectory log
+        # (ParticleEngine.track) of `history_capacity` records keeps them on the GPU and nothing is read back per step
+        self.history = history
+        self._on_device = keep_history and history == "device"
+        if self._on_device:
+            self.engine.track(history_capacity, imu=True, scan=True)
+        keep_lists = keep_history and not self._on_device
+        self._poses: List[np.ndarray] = [self.engine.poses()] if keep_lists else []
+        self._ancestors: List[Optional[np.ndarray]] = [None] if keep_lists else []
         self._urng = np.random.Generator(np.random.PCG64(seed))
 
     def imu_update(self, data, dt_ticks: float):                                  # main.py:144
@@ -140,8 +150,8 @@ class ParticleFilter:
         self._record(None)
 
     def resample(self, u: Optional[float] = None) -> bool:                        # main.py:160
-        did, idx = self.engine.resample(float(self._urng.random()) if u is None else u)
-        if did and self.keep_history:
+        did, idx = self.engine.resample(float(self._urng.random()) if u is None else u, indices=not self._on_device)
+        if did and self.keep_history and not self._on_device:
             self._poses.append(self.engine.poses()); self._ancestors.append(idx)
         return did
 
@@ -167,12 +177,19 @@ class ParticleFilter:
         self.engine.map_updates = on
 
     def _record(self, anc):
-        if self.keep_history:
+        if self.keep_history and not self._on_device:     # on the device the engine recorded the step itself
             self._poses.append(self.engine.poses()); self._ancestors.append(anc)
 
     def trajectory(self, index: int) -> List[np.ndarray]:
         """Pose history of the particle that is now at `index`, following its ancestry back (robot.py:141-146 copies
-        the history lists on every duplication; here they are reconstructed from the per-step ancestor indices)."""
+        the history lists on every duplication; here they are reconstructed from the per-step ancestor indices, on the
+        device with history="device").  A device log that ran full raises instead of returning a short path."""
+        if self._on_device:
+            info = self.engine.track_info()
+            if info["dropped"]:
+                raise RuntimeError(f"the trajectory log ran full: {info['dropped']} steps past its {info['capacity']} records were "
+                                   "not recorded (raise history_capacity)")
+            return list(self.engine.lineage([int(index)])[1][:, 0, :])
         out, i = [], index
         for poses, anc in zip(reversed(self._poses), reversed(self._ancestors)):
             if anc is not None:
