@@ -655,6 +655,44 @@ int64_t rbpf_track_record_bytes(rbpf_handle* h);
 int  rbpf_track_export(rbpf_handle* h, int32_t t0, int32_t t1, void* records);
 int  rbpf_track_import(rbpf_handle* h, int32_t n, const void* records);
 
+/* ---- map building: what map do these scans draw from these poses? ----------------------------------------------------------
+ * Hit and visit counts of n_scans scans (ranges [n_scans][n_beams], metres; angles [n_beams], sensor frame, as rbpf_set_scan) taken
+ * at the sensor poses poses_n3 [n_scans][3], rasterised at ANY cell size: inv = cells_per_m (finite, > 0), cell (X, Y) is the world
+ * square [X, X+1) x [Y, Y+1) / inv, and box4 = {x0, x1, y0, y1} is half-open in those cells.  With inv = dim / tile_len they are the
+ * mosaic cells of rbpf_render_map.  hits and seen are int32 [x1-x0][y1-y0], laid out like every raster here.  The call reads no
+ * particle map and changes no engine state (maps, particles, random streams, counters, duplicate grouping); the handle supplies
+ * the stream, scratch and staging.
+ * The ray of beam b of scan n is the ray of rbpf_cast_scans without a map to test: float64, no contraction, host
+ * libm cos / sin of theta and of each angle, the same ox, oy, dx, dy, X, Y, sx, sy, tdx, tdy, fx, fy, the same crossing parameters
+ * (n + f) * td and the same tie rule (a tie steps in y).  The walk visits cells C0, C1, ... entered at 0 = t0 < t1 <= t2 ...  With
+ * r = ranges[n][b]:
+ *   r is NaN, or r < min_range      the beam is skipped: it contributes nothing
+ *   r > max_range (+inf included)   a free beam:   tend = max_range * inv
+ *   otherwise                       a return beam: tend = r * inv
+ * Let k be the largest index with tk <= tend.  The beam PASSES C0 .. C(k-1) and ENDS in Ck; a return beam HITS Ck, a free beam only
+ * passes it.  Counts are per scan, not per beam (the set semantics of rbpf_view_gain: near the sensor hundreds of beams cross the
+ * same cells): H_n = the set of cells hit by any return beam of scan n, V_n = the set of cells passed or ended in by any of its
+ * beams that is not skipped, and for every cell c of the box
+ *   hits[c] = #{n : c in H_n}          seen[c] = #{n : c in V_n}
+ * Cells outside the box are dropped; the walk is not clipped, so a ray may start outside the box and enter it.  A cell one scan
+ * both passes and hits counts once in each: 0 <= hits <= seen <= n_scans everywhere.  Both are exact integers and integer adds
+ * commute: the result is bit-identical from call to call whatever the schedule.  Either output may be NULL, not both.
+ * Window limit: with M = ceil(max_range * inv) + 2 every cell of V_n lies within M cells of the pose's cell on each axis, and the
+ * kernel keeps a scan's (2M + 1)^2 window as a bitmap in one workgroup's LDS: ceil(max_range * inv) <= 509 is required, otherwise
+ * RBPF_EINVAL; the message gives the largest admissible max_range.
+ * A NULL poses_n3, ranges, angles or box4, hits and seen both NULL, n_scans < 1, n_beams < 1, n_scans * n_beams >= 2^31, an empty
+ * box, one of more than 2^31 cells or of 2^31 rows or columns, a non-finite pose or angle, cells_per_m, min_range or max_range not
+ * finite, cells_per_m <= 0, max_range <= 0, min_range < 0, an unknown flag or the window limit is RBPF_EINVAL; a call between
+ * rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked before anything is queued, and nothing is written.  A NaN or
+ * infinite RANGE is data, not an error.  More than 4 GiB of scratch (12 bytes per beam, and 4 per cell and host output) is
+ * RBPF_ENOMEM: build fewer scans per call.  It runs on the handle's stream; without RBPF_BUILD_DEVICE_OUT the outputs are host
+ * arrays, complete on return.  DESIGN.md 3.16 has the kernel. */
+#define RBPF_BUILD_DEVICE_OUT 1u   /* hits / seen are device pointers, written in stream order, no host wait */
+#define RBPF_BUILD_ACCUMULATE 2u   /* the outputs are added to, not zeroed first: the two halves of a log give exactly the whole */
+int  rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, const double* ranges, const double* angles,
+                    int32_t n_beams, double cells_per_m, const int32_t* box4, double min_range, double max_range,
+                    uint32_t flags, int32_t* hits, int32_t* seen);
+
 #ifdef __cplusplus
 }
 #endif

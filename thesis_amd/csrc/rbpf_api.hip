@@ -2433,4 +2433,81 @@ int rbpf_track_import(rbpf_handle* h, int32_t n, const void* records) {
     return RBPF_OK;
 }
 
+// ---- map building (kernels_build.hip) -----------------------------------------------------------------------------
+int rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, const double* ranges, const double* angles,
+                   int32_t n_beams, double cells_per_m, const int32_t* box4, double min_range, double max_range,
+                   uint32_t flags, int32_t* hits, int32_t* seen) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!poses_n3 || !ranges || !angles || !box4) return fail(h, RBPF_EINVAL, "poses, ranges, angles or box4 is NULL");
+    if (!hits && !seen) return fail(h, RBPF_EINVAL, "hits and seen are both NULL");
+    if (flags & ~(RBPF_BUILD_DEVICE_OUT | RBPF_BUILD_ACCUMULATE)) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_scans < 1 || n_beams < 1 || (long long)n_scans * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_scans >= 1, n_beams >= 1 and n_scans * n_beams < 2^31 are required");
+    if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
+    const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2];
+    if (nx > INT32_MAX || ny > INT32_MAX || nx > (1LL << 31) / ny)
+        return fail(h, RBPF_EINVAL, "box must hold at most 2^31 cells, in fewer than 2^31 rows and columns");
+    const long long ncell = nx * ny;
+    if (!std::isfinite(cells_per_m) || !(cells_per_m > 0.0)) return fail(h, RBPF_EINVAL, "cells_per_m must be finite and > 0");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
+    for (long long k = 0; k < 3LL * n_scans; ++k)
+        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    BuildArgs a;
+    a.inv = cells_per_m;
+    a.tlim = max_range * a.inv;
+    const double reach = ceil(a.tlim) + 2.0;                               // no cell of a scan lies farther from the origin cell on either axis
+    if (!(2.0 * reach + 1.0 <= 1024.0))
+        return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window of more than 1024 cells: the largest admissible "
+                                    "max_range is " + std::to_string(509.0 / a.inv) + " m (ceil(max_range * cells per metre) <= 509)");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map building between rbpf_scan_update_begin and rbpf_scan_update_end");
+    a.M = (int)reach; a.W = (2 * a.M + 1 + 31) / 32 + 1;
+    a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
+    a.min_range = min_range; a.max_range = max_range;
+    a.n_scans = n_scans; a.B = n_beams;
+    const bool dev_out = (flags & RBPF_BUILD_DEVICE_OUT) != 0, accumulate = (flags & RBPF_BUILD_ACCUMULATE) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [poses] [beams] [ranges] | [end cells] [host hits] [host seen]; the first three are one upload
+    const size_t nray = (size_t)n_scans * n_beams, pose_b = (size_t)n_scans * 32, beam_b = (size_t)n_beams * 16;
+    const size_t in_b = pose_b + beam_b + nray * 8, ends_b = pad(nray * 4), out_b = dev_out ? 0 : pad((size_t)ncell * 4);
+    const size_t total = pad(in_b) + ends_b + out_b * ((hits ? 1 : 0) + (seen ? 1 : 0));
+    if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "scans and box need more than 4 GiB of scratch: build fewer scans per call (RBPF_BUILD_ACCUMULATE) or a smaller box");
+    HIP_TRY(h, h->reserve(B_BUILD, total));
+    const Block& d = h->buf[B_BUILD];
+    Staging& st = h->stage[S_BUILD];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* sp = reinterpret_cast<double*>(st.p);
+    for (int n = 0; n < n_scans; ++n) {                                    // host libm, as rbpf_cast_scans
+        sp[4 * (size_t)n] = poses_n3[3 * (size_t)n]; sp[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
+        sp[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); sp[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
+    }
+    double* sb = sp + 4 * (size_t)n_scans;
+    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    a.pose4 = d.as<const double>();
+    a.beam2 = a.pose4 + 4 * (size_t)n_scans;
+    a.ranges = a.beam2 + 2 * (size_t)n_beams;
+    a.ends = d.as<uint32_t>(pad(in_b));
+    a.hits = !hits ? nullptr : dev_out ? hits : d.as<int32_t>(pad(in_b) + ends_b);
+    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(pad(in_b) + ends_b + (hits ? out_b : 0));
+    int32_t* const host_out[2] = {hits, seen};
+    int32_t* const dev[2] = {a.hits, a.seen};
+    for (int k = 0; k < 2; ++k) {
+        if (!dev[k]) continue;
+        if (!accumulate) HIP_TRY(h, hipMemsetAsync(dev[k], 0, (size_t)ncell * 4, h->stream));
+        else if (!dev_out) HIP_TRY(h, hipMemcpyAsync(dev[k], host_out[k], (size_t)ncell * 4, hipMemcpyHostToDevice, h->stream));   // read before the return below
+    }
+    launch_build_map(a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    for (int k = 0; k < 2; ++k)
+        if (dev[k]) HIP_TRY(h, hipMemcpyAsync(host_out[k], dev[k], (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

@@ -170,6 +170,20 @@ struct GainArgs {
     double inv, tlim;                  // cells per metre (dim / tile_len), max_range * inv
     int64_t* gain; int32_t *seen, *unknown;   // [particles][n_poses]; seen and unknown may be null
 };
+// map building (kernels_build.hip): hit and visit counts of n_scans scans taken at given poses, over a box of
+// cells of any size; one workgroup per scan.  No particle map is read.
+struct BuildArgs {
+    const double* pose4;               // [n_scans][4] x, y, cos(theta), sin(theta)
+    const double* beam2;               // [B][2] cos(angle), sin(angle)
+    const double* ranges;              // [n_scans][B] metres; NaN and +-inf are data
+    uint32_t* ends;                    // [n_scans][B] scratch: (row * 32 W + bit) << 1 | 1 of a return beam's end cell in the window, else 0
+    int n_scans, B;
+    int M, W;                          // window half-width in cells: ceil(max_range * inv) + 2; words per bitmap row
+    int x0, y0, nx, ny;                // the box: first cell, rows (x1 - x0) and columns (y1 - y0)
+    double inv, tlim;                  // cells per metre, max_range * inv
+    double min_range, max_range;
+    int32_t *hits, *seen;              // [nx][ny], added to; either may be null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -343,6 +357,7 @@ void launch_place_map(const DevView& v, const LoadArgs& a, const PlaceArgs& q, i
 void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
 size_t view_gain_lds_bytes(int M, int W);
 void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
+void launch_build_map(const BuildArgs& a, hipStream_t s);                       // adds to a.hits / a.seen
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

@@ -62,4 +62,38 @@ __device__ __forceinline__ int walk_ray(const DevView& v, const int32_t* __restr
     }
 }
 
+// The same ray with no map to test (kernels_build.hip).  ray_start is walk_ray's set-up, statement for statement;
+// walk_ray keeps its own copy because taking it from here changed the register allocation of cast_scans_kernel, and that
+// kernel is to compile as it did.  The origin cell (fX, fY) stays a double: it may lie outside any lattice.
+struct RayStart { double fX, fY, tdx, tdy, fx, fy; int sx, sy; };
+__device__ __forceinline__ RayStart ray_start(const double4 ps, const double2 bm, const double inv) {
+    RayStart r;
+    const double ox = ps.x * inv, oy = ps.y * inv;                        // origin in cells
+    const double dx = ps.z * bm.x - ps.w * bm.y, dy = ps.w * bm.x + ps.z * bm.y;
+    r.fX = __builtin_floor(ox); r.fY = __builtin_floor(oy);
+    r.sx = dx > 0 ? 1 : -1; r.sy = dy > 0 ? 1 : -1;
+    const double inf = __builtin_inf();
+    r.tdx = dx != 0 ? 1.0 / __builtin_fabs(dx) : inf; r.tdy = dy != 0 ? 1.0 / __builtin_fabs(dy) : inf;
+    r.fx = dx != 0 ? (dx > 0 ? (r.fX + 1.0) - ox : ox - r.fX) : 1.0;
+    r.fy = dy != 0 ? (dy > 0 ? (r.fY + 1.0) - oy : oy - r.fY) : 1.0;
+    return r;
+}
+
+// visit(kx, ky) for the origin cell and for every cell entered at a parameter t <= tend, in the order of the walk; (kx, ky) is
+// the cell's offset from the origin cell and, on return, the cell the ray ends in.  tend is finite and >= 0 and at least one of
+// tdx, tdy is finite, so the walk ends after at most 2 * (tend + 2) steps.
+template <class Visit>
+__device__ __forceinline__ void walk_free(const RayStart& r, const double tend, int& kx, int& ky, Visit&& visit) {
+    double nx = 0.0, ny = 0.0;                                            // step counts (exact in float64)
+    kx = ky = 0;
+    for (;;) {
+        visit(kx, ky);
+        const double tmx = (nx + r.fx) * r.tdx, tmy = (ny + r.fy) * r.tdy;
+        const bool step_x = tmx < tmy;                                    // a tie steps in y
+        if (!((step_x ? tmx : tmy) <= tend)) return;                      // (a NaN ends the walk as well)
+        nx += step_x ? 1.0 : 0.0; ny += step_x ? 0.0 : 1.0;
+        kx += step_x ? r.sx : 0; ky += step_x ? 0 : r.sy;
+    }
+}
+
 }  // namespace rbpf

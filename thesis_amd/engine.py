@@ -39,6 +39,17 @@ class ViewGain(NamedTuple):
     unknown: Any     # int32: how many of them have the lattice value 0
 
 
+class BuiltMap(NamedTuple):
+    """ParticleEngine.build_map: hit and visit counts over the cells [x0, x0 + nx) x [y0, y0 + ny) of size `cell_size`
+    (numpy arrays, or torch tensors on the GPU); thesis_amd/rebuild.py turns them into maps."""
+    hits: Any            # int32 [nx, ny]: scans with a beam that returned from the cell
+    seen: Any            # int32 [nx, ny]: scans with a beam that passed or ended in the cell; hits <= seen
+    x0: int
+    y0: int
+    cell_size: float     # metres; the engine's own when build_map was given none
+    cells_per_m: float   # what the walk multiplied by: 1 / cell_size, or the engine's dim / tile_len
+
+
 class Proposal(NamedTuple):
     """ParticleEngine.proposal: one particle's proposal frame and its K samples."""
     U: np.ndarray          # [3, 3] pseudo-inverse square root of the matcher covariance: maha = |(g - mean) U|^2
@@ -1192,6 +1203,73 @@ class ParticleEngine:
             raise ValueError("the checkpoint's trajectory log does not fit this engine")
         self._check(self._lib.rbpf_track_begin(self._h, cap, fl))
         self._check(self._lib.rbpf_track_import(self._h, n, C.c_void_p(blob.ctypes.data)))
+
+    # -- map building (include/rbpf_hip.h: rbpf_build_map; thesis_amd/rebuild.py) ------------------------------
+    def build_map(self, poses, ranges, angles, cell_size: Optional[float] = None, box=None, min_range: float = 0.0,
+                  max_range: Optional[float] = None, device: bool = False, into: Optional[BuiltMap] = None) -> BuiltMap:
+        """The map that the scans `ranges` [N, B] (beam directions `angles` [B]) draw from the sensor poses `poses` [N, 3]: per
+        cell of `box` = (x0, x1, y0, y1), in how many scans a beam returned from it (hits) and in how many a beam passed or ended
+        in it (seen), int32 [x1-x0, y1-y0].  No particle's map is read.  `cell_size` is any size in metres (cells per metre =
+        1 / cell_size); None is the engine's own dim / tile_len, and the cells are then those of render_map.  `box` defaults to
+        the smallest box holding every pose's window, floor(x * cells per metre) -+ (ceil(max_range * cells per metre) + 2) on
+        each axis.  Beams shorter than `min_range` or NaN are skipped, beams longer than `max_range` (default cfg.max_ray_m) are
+        free to max_range and hit nothing.  `into`: an earlier BuiltMap of the same geometry, added to in place (a long log in
+        chunks).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
+        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if rg.ndim == 1:
+            rg = rg.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
+            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        inv = self.dim / float(self.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
+        cs = float(self.cfg.cell_size) if cell_size is None else float(cell_size)
+        mr = float(self.cfg.max_ray_m if max_range is None else max_range)
+        if into is not None:
+            if box is not None and tuple(int(q) for q in box) != (into.x0, into.x0 + into.hits.shape[0], into.y0, into.y0 + into.hits.shape[1]):
+                raise ValueError("box differs from the box of `into`")
+            if into.cells_per_m != inv or into.hits.shape != into.seen.shape:
+                raise ValueError("`into` was built at another cell size")
+            box = (into.x0, into.x0 + into.hits.shape[0], into.y0, into.y0 + into.hits.shape[1])
+            device = not isinstance(into.hits, np.ndarray)
+        if box is None:
+            box = self.build_box(ps, inv, mr)
+        b4 =np.array([int(q) for q in box], dtype=np.int32)
+        shape = (max(int(b4[1]) - int(b4[0]), 0), max(int(b4[3]) - int(b4[2]), 0))       # an empty box is the library's to refuse
+        flags = (_lib.RBPF_BUILD_DEVICE_OUT if device else 0) | (_lib.RBPF_BUILD_ACCUMULATE if into is not None else 0)
+        same_stream = False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [into.hits, into.seen] if into is not None else [torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(2)]
+            if any(o.dtype != torch.int32 or not o.is_contiguous() or o.device != dev for o in outs):
+                raise ValueError("`into` must hold contiguous int32 tensors on the engine's device")
+            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated (or last written) in torch's stream order
+        else:
+            outs = [into.hits, into.seen] if into is not None else [np.empty(shape, dtype=np.int32) for _ in range(2)]
+            if any(o.dtype != np.int32 or not o.flags.c_contiguous or not o.flags.writeable for o in outs):
+                raise ValueError("`into` must hold contiguous, writeable int32 arrays")
+            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
+        self._check(self._lib.rbpf_build_map(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], inv, _ip(b4), float(min_range),
+                                             mr, flags, *ptrs))
+        if device and not same_stream:
+            self.synchronize()
+        return BuiltMap(outs[0], outs[1], int(b4[0]), int(b4[2]), cs, inv)
+
+    @staticmethod
+    def build_box(poses, cells_per_m: float, max_range: float) -> Tuple[int, int, int, int]:
+        """build_map's default box (x0, x1, y0, y1): the smallest one holding the window of every pose, the cells within
+        ceil(max_range * cells_per_m) + 2 of floor(x * cells_per_m) on each axis."""
+        ps = _f64(poses).reshape(-1, 3)
+        if not (len(ps) and np.all(np.isfinite(ps)) and np.isfinite(max_range * cells_per_m)):
+            raise ValueError("poses, cell size and max_range must be finite")
+        m = int(np.ceil(max_range * cells_per_m)) + 2
+        fx, fy = np.floor(ps[:, 0] * cells_per_m), np.floor(ps[:, 1] * cells_per_m)
+        return (int(fx.min()) - m, int(fx.max()) + m + 1, int(fy.min()) - m, int(fy.max()) + m + 1)
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)

@@ -119,9 +119,11 @@ class ParticleFilter:
 
     def __init__(self, n_particles: int, angles, motion_model: str = "velocity", *, cell_size: float = 0.05,
                  keep_history: bool = True, seed: int = 42, map_updates: bool = True, history: str = "host",
-                 history_capacity: int = 4096, **engine_options):
+                 history_capacity: int = 4096, keep_scans: bool = False, **engine_options):
         if history not in ("host", "device"):
             raise ValueError(f"unknown history {history!r}")
+        if keep_scans and not (keep_history and history == "device"):
+            raise ValueError('keep_scans needs history="device": scans are kept under the records of the trajectory log')
         self.angles = np.ascontiguousarray(angles, dtype=np.float64)
         self.engine = ParticleEngine(n_particles, max_beams=len(self.angles), cell_size=cell_size, seed=seed,
                                      pool_tiles=engine_options.pop("pool_tiles", 4 * n_particles + 16), **engine_options)
@@ -135,6 +137,12 @@ class ParticleFilter:
         self._on_device = keep_history and history == "device"
         if self._on_device:
             self.engine.track(history_capacity, imu=True, scan=True)
+        # keep_scans: every scan map_update takes is kept on the host under the record written for it (rebuild.ScanLog), so
+        # that rebuild.rebuild can draw the final map again from a trajectory
+        self.scans = None
+        if keep_scans:
+            from .rebuild import ScanLog
+            self.scans, self._dropped = ScanLog(), 0
         keep_lists = keep_history and not self._on_device
         self._poses: List[np.ndarray] = [self.engine.poses()] if keep_lists else []
         self._ancestors: List[Optional[np.ndarray]] = [None] if keep_lists else []
@@ -148,6 +156,11 @@ class ParticleFilter:
         self.engine.set_scan(ranges, self.angles)
         self.engine.scan_update(adj=adj, last_scan_xy=last_scan_xy if adj else None)
         self._record(None)
+        if self.scans is not None:
+            info = self.engine.track_info()
+            if info["dropped"] == self._dropped:          # else the log is full: this scan has no record
+                self.scans.append(info["n_records"] - 1, ranges)
+            self._dropped = info["dropped"]
 
     def resample(self, u: Optional[float] = None) -> bool:                        # main.py:160
         did, idx = self.engine.resample(float(self._urng.random()) if u is None else u, indices=not self._on_device)
