@@ -693,6 +693,49 @@ int  rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, con
                     int32_t n_beams, double cells_per_m, const int32_t* box4, double min_range, double max_range,
                     uint32_t flags, int32_t* hits, int32_t* seen);
 
+/* ---- pose refinement: which pose near each guess fits the map best? ----------------------------------------------------------
+ * n_scans scans (ranges [n_scans][n_beams], metres; angles [n_beams], sensor frame, as rbpf_set_scan) with n_scans guessed sensor
+ * poses poses_n3 [n_scans][3] = (gx, gy, gtheta) are matched against `particle`'s map: every candidate of a window of sub-cell
+ * translations and rotations round each guess is scored, and the best one is returned per scan.  The call reads one particle's
+ * map and changes no engine state (maps, particles, random streams, counters, duplicate grouping).
+ * Field: F(X, Y) = occ + dil in {0, 1, 2} of rbpf_locate_scan: 0 where there is no tile, outside a tile's written
+ * box and outside the lattice.
+ * Beams: beam b of scan n is used iff min_range < ranges[n][b] < max_range (NaN, +-inf, 0 and negative ranges are data and are not
+ * used); n_used[n] counts them.  ca = cos(angles[b]), sa = sin(angles[b]) from host libm, bx = r * ca, by = r * sa.
+ * Candidates: S = substeps in {1, 2, 4, 8, 16}, s = log2 S; W = n_trans in 0 .. 32; R = n_rot in 0 .. 100; candidate (i, j, k) has
+ * i, j in [-W, W], k in [-R, R].  inv = dim / tile_len, invS = inv * S (exact).  float64, every + - * rounded on its own:
+ *   theta_k = gtheta + (double)k * rot_step      ck = cos(theta_k), sk = sin(theta_k)       (host libm)
+ *   PX[k][b] = floor((gx + (ck * bx - sk * by)) * invS)      PY[k][b] = floor((gy + (sk * bx + ck * by)) * invS)
+ *   EX = (PX + i) >> s     EY = (PY + j) >> s                (arithmetic shift: floor division by S)
+ *   score(n, i, j, k) = sum over the used beams of F(EX, EY)      (duplicates count; 0 <= score <= 2 n_used)
+ * Candidate (i, j, k) stands for the pose (gx + i / invS, gy + j / invS, theta_k).
+ * Best: per scan the candidate of maximal score; ties go to the smallest |k|, then the smallest i^2 + j^2, then the
+ * lexicographically smallest (k, i, j).  A guess that attains the maximum is returned as it is: (0, 0, 0), the pose bit for bit
+ * (a coordinate of -0.0 comes back as +0.0).
+ * Outputs: out_pose_n3[n] = (gx + (double)i / invS, gy + (double)j / invS, theta_k) of the best candidate; out_n6[n] = {i, j, k,
+ * best score, score(0, 0, 0), n_used}; scores, if not NULL, the whole volume int32 [n_scans][2R+1][2W+1][2W+1], indexed
+ * [n][k + R][i + W][j + W].  One of out_pose_n3 and out_n6 may be NULL.
+ * Window limit: with Mw = ceil(max_range * inv) + ceil(W / S) + 2 every (EX, EY) of scan n lies within Mw cells of
+ * (floor(gx * inv), floor(gy * inv)) on each axis, and the kernel keeps that window of F in one workgroup's LDS, 2 Mw + 1 rows of
+ * WW = (((2 Mw + 32) >> 5) + 2) | 1 pairs of occ and dil words, beside a beam table of 16 KiB:
+ *   16384 + (2 Mw + 1) * WW * 8 <= 163776 bytes,  that is  Mw <= 367,
+ * is required, otherwise RBPF_EINVAL; the message gives the largest admissible max_range.  rbpf_refine_max_reach(S, W) is the
+ * largest admissible ceil(max_range * inv), 367 - ceil(W / S) - 2 (-1 for an S or W out of range): 18.1 m at 0.05 m cells and
+ * 9.05 m at 0.025 m with W / S = 3.
+ * A NULL poses_n3, ranges or angles, out_pose_n3 and out_n6 both NULL, n_scans < 1, n_beams < 1 or > 16384, n_scans * n_beams >=
+ * 2^31, a bad particle, substeps not one of the five values, n_trans or n_rot out of range, rot_step not finite or < 0, a non-finite
+ * pose or angle, min_range < 0, max_range <= 0 or either not finite, (|g| + max_range) * invS + W >= 2^30 on either axis, an unknown
+ * flag or the window limit is RBPF_EINVAL; a call between rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked before
+ * anything is queued, and nothing is written.  More than 4 GiB of scratch (32 bytes per scan and rotation, 8 per beam, the field
+ * of the windows' union, and a requested score volume, wherever it goes) is RBPF_ENOMEM: refine fewer scans per call.  It runs on
+ * the handle's stream; without RBPF_REFINE_DEVICE_OUT the outputs are host arrays, complete on return.  Each scan is matched
+ * against the map as it is: a map that holds the scan itself is not corrected for that.  DESIGN.md 3.17 has the kernel. */
+#define RBPF_REFINE_DEVICE_OUT 1u   /* out_pose_n3 / out_n6 / scores are device pointers, written in stream order, no host wait */
+int32_t rbpf_refine_max_reach(int32_t substeps, int32_t n_trans);
+int  rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_scans, const double* ranges,
+                       const double* angles, int32_t n_beams, double min_range, double max_range, int32_t substeps, int32_t n_trans,
+                       int32_t n_rot, double rot_step, double* out_pose_n3, int32_t* out_n6, int32_t* scores, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2510,4 +2510,136 @@ int rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, cons
     return RBPF_OK;
 }
 
+// ---- scan-to-map refinement (kernels_refine.hip) -------------------------------------------------------------------
+static const size_t REFINE_LDS_LIMIT = 160 * 1024 - 64;                    // dynamic LDS of the search kernel: 160 KiB less its statics
+static int refine_row_words(long long Mw) { return (int)((((2 * Mw + 1 + 31) >> 5) + 2) | 1); }
+static bool refine_substeps_ok(int32_t S) { return S == 1 || S == 2 || S == 4 || S == 8 || S == 16; }
+
+int32_t rbpf_refine_max_reach(int32_t substeps, int32_t n_trans) {
+    if (!refine_substeps_ok(substeps) || n_trans < 0 || n_trans > 32) return -1;
+    const int extra = (n_trans + substeps - 1) / substeps + 2;
+    int reach = -1;                                                        // the LDS need grows with Mw: the first failure ends the search
+    for (int c = 0; refine_lds_bytes(c + extra, refine_row_words(c + extra)) <= REFINE_LDS_LIMIT; ++c) reach = c;
+    return reach;
+}
+
+int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_scans, const double* ranges,
+                      const double* angles, int32_t n_beams, double min_range, double max_range, int32_t substeps, int32_t n_trans,
+                      int32_t n_rot, double rot_step, double* out_pose_n3, int32_t* out_n6, int32_t* scores, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!poses_n3 || !ranges || !angles) return fail(h, RBPF_EINVAL, "poses, ranges or angles is NULL");
+    if (!out_pose_n3 && !out_n6) return fail(h, RBPF_EINVAL, "out_pose_n3 and out_n6 are both NULL");
+    if (flags & ~RBPF_REFINE_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_scans < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
+    if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    if (!refine_substeps_ok(substeps)) return fail(h, RBPF_EINVAL, "substeps must be 1, 2, 4, 8 or 16");
+    if (n_trans < 0 || n_trans > 32) return fail(h, RBPF_EINVAL, "0 <= n_trans <= 32 is required");
+    if (n_rot < 0 || n_rot > 100) return fail(h, RBPF_EINVAL, "0 <= n_rot <= 100 is required");
+    if (!std::isfinite(rot_step) || rot_step < 0.0) return fail(h, RBPF_EINVAL, "rot_step must be finite and >= 0");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
+    for (long long k = 0; k < 3LL * n_scans; ++k)
+        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as lookup_cell_fast forms it
+    const double invS = inv * (double)substeps;                            // exact: a power of two
+    for (int n = 0; n < n_scans; ++n)
+        for (int c = 0; c < 2; ++c)
+            if (!((fabs(poses_n3[3 * (size_t)n + c]) + max_range) * invS + (double)n_trans < 1073741824.0))
+                return fail(h, RBPF_EINVAL, "(|pose| + max_range) * cells per metre * substeps + n_trans < 2^30 is required");
+    const int extra = (n_trans + substeps - 1) / substeps + 2;
+    const double reach = ceil(max_range * inv);
+    const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
+    if (!(reach <= (double)max_reach)) {
+        double most = (double)max_reach / inv;                             // the largest max_range with ceil(max_range * inv) <= max_reach
+        if (ceil(most * inv) > (double)max_reach) most = nextafter(most, 0.0);
+        char num[32];
+        snprintf(num, sizeof num, "%.17g", most);
+        return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window that does not fit one workgroup's LDS: the largest "
+                                    "admissible max_range is " + num + " m (ceil(max_range * cells per metre) <= " + std::to_string(max_reach) + ")");
+    }
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "pose refinement between rbpf_scan_update_begin and rbpf_scan_update_end");
+    RefineArgs a;
+    a.N = n_scans; a.B = n_beams; a.Wt = n_trans; a.R = n_rot; a.nk = 2 * n_rot + 1;
+    a.s = substeps == 1 ? 0 : substeps == 2 ? 1 : substeps == 4 ? 2 : substeps == 8 ? 3 : 4;
+    a.Mw = (int)reach + extra; a.WW = refine_row_words(a.Mw);
+    a.invS = invS; a.min_range = min_range; a.max_range = max_range;
+    // rotations per workgroup: as many tasks as a workgroup has lanes, fewer while the grid would not fill the GPU
+    const int nw = 2 * n_trans + 1, t1 = nw * refine_runs(nw, a.s);
+    a.kpw = std::max(1, std::min(std::min(16, a.nk), REFINE_BLOCK / t1));
+    while (a.kpw > 1 && (long long)n_scans * ((a.nk + a.kpw - 1) / a.kpw) < 1024) --a.kpw;
+    if (const char* e = getenv("RBPF_REFINE_KPW")) a.kpw = std::max(1, std::min(std::min(16, a.nk), atoi(e)));   // for tests
+    // the field: the union of the windows, cut to the lattice grown by 2 (F = 0 farther out)
+    const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
+    long long lo[2] = {INT64_MAX, INT64_MAX}, hi[2] = {INT64_MIN, INT64_MIN};
+    for (int n = 0; n < n_scans; ++n)
+        for (int c = 0; c < 2; ++c) {
+            const long long cell = (long long)floor(poses_n3[3 * (size_t)n + c] * inv);
+            lo[c] = std::min(lo[c], cell); hi[c] = std::max(hi[c], cell);
+        }
+    LocateArgs f;
+    long long ext[2];
+    for (int c = 0; c < 2; ++c) {
+        lo[c] = std::max(lo[c] - a.Mw, -off - 2); hi[c] = std::min(hi[c] + a.Mw + 1, edge - off + 2);
+        ext[c] = std::max(0LL, hi[c] - lo[c]);
+    }
+    const bool any_field = ext[0] > 0 && ext[1] > 0;
+    f.particle = particle; f.M = 0; f.x0 = a.fx0 = any_field ? (int)lo[0] : 0; f.y0 = a.fy0 = any_field ? (int)lo[1] : 0;
+    f.rows = a.frows = any_field ? (int)ext[0] : 0; f.W = a.fW = any_field ? (int)((ext[1] + 31) / 32) : 0;
+    const bool dev_out = (flags & RBPF_REFINE_DEVICE_OUT) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [guesses] [rotations] [beams] [ranges] [centre cells] | [field] [merge words] [guess scores] [n_used] | host outputs
+    const size_t N = (size_t)n_scans, nray = N * n_beams, vol = N * a.nk * nw * nw;
+    const size_t guess_b = N * 16, rot_b = N * a.nk * 32, beam_b = (size_t)n_beams * 16, cell_at = guess_b + rot_b + beam_b + nray * 8;
+    const size_t in_b = cell_at + N * 8, field_b = pad((size_t)a.frows * a.fW * 8), merge_b = pad(N * 8) + 2 * pad(N * 4);
+    const size_t pose_b = !dev_out && out_pose_n3 ? pad(N * 24) : 0, n6_b = !dev_out && out_n6 ? pad(N * 24) : 0;
+    const size_t total = pad(in_b) + field_b + merge_b + pose_b + n6_b + (scores && !dev_out ? pad(vol * 4) : 0);
+    if (total + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
+        return fail(h, RBPF_ENOMEM, "scans, field and score volume need more than 4 GiB: refine fewer scans per call");
+    HIP_TRY(h, h->reserve(B_REFINE, total));
+    const Block& d = h->buf[B_REFINE];
+    Staging& st = h->stage[S_REFINE];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* sg = reinterpret_cast<double*>(st.p);
+    double* sr = sg + 2 * N;
+    int32_t* sc = reinterpret_cast<int32_t*>(st.p + cell_at);
+    for (size_t n = 0; n < N; ++n) {
+        const double gx = poses_n3[3 * n], gy = poses_n3[3 * n + 1], gth = poses_n3[3 * n + 2];
+        sg[2 * n] = gx; sg[2 * n + 1] = gy;
+        sc[2 * n] = (int32_t)floor(gx * inv); sc[2 * n + 1] = (int32_t)floor(gy * inv);
+        for (int q = 0; q < a.nk; ++q) {                                   // host libm: the device never sees an angle
+            const double th = gth + (double)(q - n_rot) * rot_step;
+            double* o = sr + (n * a.nk + q) * 4;
+            o[0] = cos(th); o[1] = sin(th); o[2] = th; o[3] = 0.0;
+        }
+    }
+    double* sb = sr + 4 * N * a.nk;
+    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    a.guess = d.as<const double>(); a.rot = a.guess + 2 * N; a.beam2 = a.rot + 4 * N * a.nk; a.ranges = a.beam2 + 2 * (size_t)n_beams;
+    a.cell0 = d.as<const int32_t>(cell_at);
+    size_t at = pad(in_b);
+    a.field = f.field = d.as<uint2>(at); at += field_b;
+    a.packed = d.as<unsigned long long>(at);
+    a.guess_score = d.as<int32_t>(at + pad(N * 8)); a.n_used = d.as<int32_t>(at + pad(N * 8) + pad(N * 4));
+    HIP_TRY(h, hipMemsetAsync(a.packed, 0, merge_b, h->stream));
+    at += merge_b;
+    a.out_pose = !out_pose_n3 ? nullptr : dev_out ? out_pose_n3 : d.as<double>(at); at += pose_b;
+    a.out_n6 = !out_n6 ? nullptr : dev_out ? out_n6 : d.as<int32_t>(at); at += n6_b;
+    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(at);
+    launch_refine_poses(v, f, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    if (out_pose_n3) HIP_TRY(h, hipMemcpyAsync(out_pose_n3, a.out_pose, N * 24, hipMemcpyDeviceToHost, h->stream));
+    if (out_n6) HIP_TRY(h, hipMemcpyAsync(out_n6, a.out_n6, N * 24, hipMemcpyDeviceToHost, h->stream));
+    if (scores) HIP_TRY(h, hipMemcpyAsync(scores, a.scores, vol * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

@@ -184,6 +184,31 @@ struct BuildArgs {
     double min_range, max_range;
     int32_t *hits, *seen;              // [nx][ny], added to; either may be null
 };
+// scan-to-map refinement (kernels_refine.hip): N scans with N guessed poses against one particle's map, every
+// candidate (i, j, k) of a window of sub-cell translations and rotations.  The field is locate's over the union of the scans'
+// windows cut to the lattice: a LocateArgs with particle, x0, y0, M = 0, rows, W and field set describes it
+static const int REFINE_BLOCK = 512;   // lanes of a workgroup, one task (rotation, i, run of j) each
+static const int REFINE_RUN = 8;       // values of j of one task, substeps apart
+static const int REFINE_TABLE = 2048;  // (PX, PY) entries of the beam table in LDS: rotations of the workgroup x beams of a chunk
+// runs of j per i: the 2 W + 1 values of j fall into S residue classes, each cut into runs of REFINE_RUN
+__host__ __device__ inline int refine_runs(int nw, int s) { return ((((nw + (1 << s) - 1) >> s) + REFINE_RUN - 1) / REFINE_RUN) << s; }
+struct RefineArgs {
+    int N, B;                          // scans, beams per scan
+    int Wt, R, s, nk, kpw;             // n_trans, n_rot, log2 substeps, rotations 2 R + 1, rotations per workgroup (<= 16)
+    int Mw, WW;                        // window half-width in cells; {occ, dil} word pairs per window row (odd)
+    int fx0, fy0, frows, fW;           // the field: first cell, rows, word pairs per row; frows = 0: no window meets the lattice
+    double invS, min_range, max_range; // sub-cells per metre (dim / tile_len * substeps); a beam is used iff min < r < max
+    const double* guess;               // [N][2] gx, gy
+    const int32_t* cell0;              // [N][2] floor(gx * inv), floor(gy * inv): the window's centre cell (host)
+    const double* rot;                 // [N][nk][4] cos, sin of theta_k and theta_k itself (host libm), one pad
+    const double* beam2;               // [B][2] cos, sin of the beam angles (host libm)
+    const double* ranges;              // [N][B] metres; NaN and +-inf are data
+    const uint2* field;                // [frows][fW]
+    unsigned long long* packed;        // [N] max over candidates of score << 41 | complemented tie key, preset to 0
+    int32_t *guess_score, *n_used;     // [N] scratch: score(0, 0, 0) and the number of used beams
+    int32_t* scores;                   // [N][nk][2 Wt + 1][2 Wt + 1] or null
+    double* out_pose; int32_t* out_n6; // [N][3], [N][6]; either may be null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -358,6 +383,8 @@ void launch_cast_scans(const DevView& v, const CastArgs& a, hipStream_t s);
 size_t view_gain_lds_bytes(int M, int W);
 void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
 void launch_build_map(const BuildArgs& a, hipStream_t s);                       // adds to a.hits / a.seen
+size_t refine_lds_bytes(int Mw, int WW);
+void launch_refine_poses(const DevView& v, const LocateArgs& f, const RefineArgs& a, hipStream_t s);   // a.packed preset to 0
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

@@ -50,6 +50,19 @@ class BuiltMap(NamedTuple):
     cells_per_m: float   # what the walk multiplied by: 1 / cell_size, or the engine's dim / tile_len
 
 
+class RefineResult(NamedTuple):
+    """ParticleEngine.refine_poses: per scan [N] (numpy arrays, or torch tensors on the GPU); thesis_amd/refine.py reads them."""
+    poses: Any           # float64 [N, 3]: the best candidate's pose, the guess itself (bit for bit) where index is (0, 0, 0)
+    index: Any           # int32 [N, 3]: (i, j, k) of the best candidate, in steps of cell_size / substeps and of rot_step
+    score: Any           # int32 [N]: its score, the sum of F = occ + dil over the used beams
+    score_guess: Any     # int32 [N]: the guess's own score
+    n_used: Any          # int32 [N]: beams with min_range < range < max_range; score <= 2 n_used
+    scores: Any          # int32 [N, 2 rotations + 1, 2 window + 1, 2 window + 1] indexed [n, k, i, j], or None
+    substeps: int
+    rot_step: float
+    cell_size: float     # metres: a translation step is cell_size / substeps
+
+
 class Proposal(NamedTuple):
     """ParticleEngine.proposal: one particle's proposal frame and its K samples."""
     U: np.ndarray          # [3, 3] pseudo-inverse square root of the matcher covariance: maha = |(g - mean) U|^2
@@ -1270,6 +1283,67 @@ class ParticleEngine:
         m = int(np.ceil(max_range * cells_per_m)) + 2
         fx, fy = np.floor(ps[:, 0] * cells_per_m), np.floor(ps[:, 1] * cells_per_m)
         return (int(fx.min()) - m, int(fx.max()) + m + 1, int(fy.min()) - m, int(fy.max()) + m + 1)
+
+    # -- pose refinement (include/rbpf_hip.h: rbpf_refine_poses; thesis_amd/refine.py) --------------------------
+    def refine_poses(self, poses, ranges, angles, particle="best", substeps: int = 4, window: int = 12, rotations: int = 10,
+                     rot_step: float = 0.004363323129985824, min_range: Optional[float] = None, max_range: Optional[float] = None,
+                     return_scores: bool = False, device: bool = False) -> RefineResult:
+        """The pose near each guess `poses` [N, 3] that fits the scan `ranges` [N, B] (beam directions `angles` [B]) best in a
+        particle's map: `particle` an index or "best" (the first argmax of weights()).  Every translation of -window .. window
+        steps of cell_size / substeps on each axis and every rotation of -rotations .. rotations steps of `rot_step` radians
+        (default 0.25 degrees) is scored by the sum of F = occ + dil at the end cells of the beams with min_range < range <
+        max_range (defaults cfg.match_min_range, cfg.match_max_range); ties go to the smallest rotation, then the shortest
+        translation, so a guess that is already best comes back bit for bit.  A [3] pose with a [B] scan is N = 1.
+        return_scores: the whole score volume as well.  max_range is limited by the window that fits one workgroup's LDS
+        (refine_max_range).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
+        if isinstance(particle, str):
+            if particle != "best":
+                raise ValueError(f"unknown particle {particle!r}")
+            particle = int(np.argmax(self.weights()))
+        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if rg.ndim == 1:
+            rg = rg.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
+            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        n, nw, nk = ps.shape[0], 2 * int(window) + 1, 2 * int(rotations) + 1
+        lo = float(self.cfg.match_min_range if min_range is None else min_range)
+        hi = float(self.cfg.match_max_range if max_range is None else max_range)
+        shapes = [(n, 3), (n, 6)] + ([(n, max(nk, 0), max(nw, 0), max(nw, 0))] if return_scores else [])   # a bad window is the library's to refuse
+        same_stream = False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [torch.empty(sh, dtype=torch.float64 if k == 0 else torch.int32, device=dev) for k, sh in enumerate(shapes)]
+            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            outs = [np.empty(sh, dtype=np.float64 if k == 0 else np.int32) for k, sh in enumerate(shapes)]
+            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
+        if not return_scores:
+            ptrs.append(None)
+        self._check(self._lib.rbpf_refine_poses(self._h, int(particle), _dp(ps), n, _dp(rg), _dp(a), a.shape[0], lo, hi, int(substeps),
+                                                int(window), int(rotations), float(rot_step), *ptrs,
+                                                _lib.RBPF_REFINE_DEVICE_OUT if device else 0))
+        if device and not same_stream:
+            self.synchronize()
+        n6 = outs[1]
+        return RefineResult(outs[0], n6[:, 0:3], n6[:, 3], n6[:, 4], n6[:, 5], outs[2] if return_scores else None, int(substeps),
+                            float(rot_step), float(self.cfg.cell_size))
+
+    def refine_max_range(self, substeps: int = 4, window: int = 12) -> float:
+        """The largest max_range refine_poses admits at this cell size for a window of `window` steps of cell_size / substeps:
+        ceil(max_range * cells per metre) + ceil(window / substeps) + 2 <= 367 (include/rbpf_hip.h, the window limit)."""
+        reach = int(self._lib.rbpf_refine_max_reach(int(substeps), int(window)))
+        if reach < 0:
+            raise ValueError("substeps must be 1, 2, 4, 8 or 16 and 0 <= window <= 32")
+        inv = self.dim / float(self.cfg.tile_len_m)
+        most = reach / inv
+        return float(np.nextafter(most, 0.0)) if np.ceil(most * inv) > reach else most
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)

@@ -143,3 +143,20 @@ def rebuild(engine, log: ScanLog, angles, particle="best", cell_size: Optional[f
     for k in range(0, len(records), CHUNK):
         built = engine.build_map(poses[k:k + CHUNK], ranges[k:k + CHUNK], angles, cell_size=cell_size, into=built, **build_args)
     return built
+
+
+def rebuild_at(engine, poses, ranges, angles, cell_size: Optional[float] = None, **build_args) -> BuiltMap:
+    """The counts of the scans `ranges` [n, B] at the explicit poses `poses` [n, 3]: rebuild()'s loop without a trajectory log
+    (thesis_amd/refine.py draws the map again from refined poses with it).  One box for every chunk, chunks of at most CHUNK."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    ranges = np.ascontiguousarray(ranges, dtype=np.float64).reshape(len(poses), -1)
+    if len(poses) == 0:
+        raise ValueError("no scan to build a map from")
+    if build_args.get("box") is None:
+        inv = engine.dim / float(engine.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
+        mr = build_args.get("max_range")
+        build_args["box"] = engine.build_box(poses, inv, float(engine.cfg.max_ray_m if mr is None else mr))
+    built = None
+    for k in range(0, len(poses), CHUNK):
+        built = engine.build_map(poses[k:k + CHUNK], ranges[k:k + CHUNK], angles, cell_size=cell_size, into=built, **build_args)
+    return built
