@@ -736,6 +736,50 @@ int  rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3,
                        const double* angles, int32_t n_beams, double min_range, double max_range, int32_t substeps, int32_t n_trans,
                        int32_t n_rot, double rot_step, double* out_pose_n3, int32_t* out_n6, int32_t* scores, uint32_t flags);
 
+/* ---- pair matching: where does a scan sit among earlier scans? --------------------------------------------------------------
+ * n_pairs pairs over n_scans scans (ranges [n_scans][n_beams], angles [n_beams], as rbpf_refine_poses) whose current sensor poses
+ * are poses_n3 [n_scans][3] = (px, py, ptheta).  pairs_m3[m] = {q, r0, r1}: the query scan q is matched against the reference
+ * scans r0 .. r1 - 1 at their poses; 0 <= q < n_scans and 0 <= r0 < r1 <= n_scans.  q may lie inside its run (a self-match; the
+ * caller avoids it).  guess_m3[m] = (gx, gy, gtheta) is the guessed world pose of the query's sensor; NULL: poses_n3[q].  No
+ * particle's map is read and no engine state changes: the handle supplies the stream, scratch and staging.
+ * Everything is float64, every + - * rounded on its own; every cos and sin comes from host libm.
+ * Beams: a beam is used iff min_range < r < max_range (NaN, +-inf, 0 and negative ranges are data and are not used);
+ * ca = cos(angles[b]), sa = sin(angles[b]), bx = r * ca, by = r * sa.
+ * Field of pair m: inv = cells_per_m, any finite value > 0 as in rbpf_build_map.  Every used beam of every reference scan n of the
+ * run, with c = cos(ptheta), s = sin(ptheta), hits the cell
+ *   HX = floor((px + (c * bx - s * by)) * inv)      HY = floor((py + (s * bx + c * by)) * inv)
+ * occ(X, Y) = 1 iff some (HX, HY) equals (X, Y); dil is the OR of occ over the 3 x 3 cells round (X, Y);
+ * F = occ + dil in {0, 1, 2}, defined on the whole plane.  n_ref is the number of used reference beams of the run: beams, not
+ * cells.
+ * Candidates, score, best and pose are rbpf_refine_poses's with this inv, invS = inv * S (exact), and the query's used beams:
+ *   theta_k = gtheta + (double)k * rot_step      PX = floor((gx + (ck * bx - sk * by)) * invS)      PY alike
+ *   EX = (PX + i) >> s     EY = (PY + j) >> s     score(m, i, j, k) = sum over the query's used beams of F(EX, EY)
+ * with S = substeps in {1, 2, 4, 8, 16}, W = n_trans in 0 .. 32, R = n_rot in 0 .. 100; ties go to the smallest |k|, then the
+ * smallest i^2 + j^2, then the lexicographically smallest (k, i, j): a guess that attains the maximum comes back bit for bit.
+ * Outputs: out_pose_m3[m] = (gx + (double)i / invS, gy + (double)j / invS, theta_k); out_m8[m] = {i, j, k, best score,
+ * score(0, 0, 0), n_used of the query, n_ref, 0}; scores, if not NULL, int32 [n_pairs][2R+1][2W+1][2W+1].  One of out_pose_m3 and
+ * out_m8 may be NULL.
+ * Self-match: with q in its own run and a NULL guess, floor(floor(v * inv * S) / S) = floor(v * inv) for every v (inv * S is
+ * exact), so every used beam of q ends in a cell it drew itself: score(0, 0, 0) = 2 n_used, the result is (0, 0, 0) and the pose
+ * comes back bit for bit, for any S, W and R.
+ * Window limit: rbpf_refine_poses's, unchanged: Mw = ceil(max_range * inv) + ceil(W / S) + 2 <= 367 round the guess's cell
+ * (rbpf_refine_max_reach(S, W) is the largest admissible ceil(max_range * inv)), otherwise RBPF_EINVAL; the message gives the
+ * largest admissible max_range.  No candidate reads F outside that window, so reference points outside it change nothing.
+ * A NULL poses_n3, ranges, angles or pairs_m3, out_pose_m3 and out_m8 both NULL, n_scans, n_pairs or n_beams < 1, n_beams >
+ * 16384, n_scans * n_beams or n_pairs * (2R+1) >= 2^31, a bad pair, a non-finite pose, guess or angle, a bad substeps, n_trans,
+ * n_rot, rot_step, min_range, max_range or cells_per_m, (|coordinate| + max_range) * invS + W >= 2^30 for a guess or for the pose
+ * of a scan of a run, an unknown flag or the window limit is RBPF_EINVAL; a call between rbpf_scan_update_begin and _end is
+ * RBPF_ESTATE; both are checked before anything is queued, and nothing is written.  More than 4 GiB of scratch is RBPF_ENOMEM:
+ * match fewer pairs per call.  Scratch: per pair 56 bytes, 32 per rotation and the field, (2 Mw + 1) * WW * 8 with WW =
+ * (((2 Mw + 32) >> 5) + 2) | 1 (31 KiB at Mw = 150, 144 KiB at 367); per scan 32 bytes and 8 per beam; 16 per beam angle; host
+ * outputs 56 per pair; a requested score volume wherever it goes.  It runs on the handle's stream; without RBPF_PAIRS_DEVICE_OUT
+ * the outputs are host arrays, complete on return.  DESIGN.md 3.18 has the kernels. */
+#define RBPF_PAIRS_DEVICE_OUT 1u    /* out_pose_m3 / out_m8 / scores are device pointers, written in stream order, no host wait */
+int  rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, const double* ranges, const double* angles,
+                      int32_t n_beams, const int32_t* pairs_m3, int32_t n_pairs, const double* guess_m3, double cells_per_m,
+                      double min_range, double max_range, int32_t substeps, int32_t n_trans, int32_t n_rot, double rot_step,
+                      double* out_pose_m3, int32_t* out_m8, int32_t* scores, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

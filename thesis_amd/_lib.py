@@ -27,6 +27,7 @@ RBPF_EST_F64, RBPF_EST_I32 = 16, 4
 RBPF_TRACK_IMU, RBPF_TRACK_SCAN, RBPF_TRACK_CHUNK, RBPF_TRACK_DEVICE_OUT = 1, 2, 64, 1
 RBPF_BUILD_DEVICE_OUT, RBPF_BUILD_ACCUMULATE = 1, 2
 RBPF_REFINE_DEVICE_OUT = 1
+RBPF_PAIRS_DEVICE_OUT = 1
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -157,6 +158,8 @@ PROTOTYPES = {
     "rbpf_refine_max_reach": (C.c_int32, [C.c_int32, C.c_int32]),
     "rbpf_refine_poses": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _D, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rbpf_match_pairs": (C.c_int, [_H, _D, C.c_int32, _D, _D, C.c_int32, _I, C.c_int32, _D, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
 }
 
 _lib = None

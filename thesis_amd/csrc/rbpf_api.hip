@@ -2523,6 +2523,16 @@ int32_t rbpf_refine_max_reach(int32_t substeps, int32_t n_trans) {
     return reach;
 }
 
+// the window limit's message: the largest max_range with ceil(max_range * inv) <= max_reach
+static std::string refine_window_message(double max_range, double inv, int max_reach) {
+    double most = (double)max_reach / inv;
+    if (ceil(most * inv) > (double)max_reach) most = nextafter(most, 0.0);
+    char num[32];
+    snprintf(num, sizeof num, "%.17g", most);
+    return "max_range " + std::to_string(max_range) + " m needs a window that does not fit one workgroup's LDS: the largest "
+           "admissible max_range is " + num + " m (ceil(max_range * cells per metre) <= " + std::to_string(max_reach) + ")";
+}
+
 int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_scans, const double* ranges,
                       const double* angles, int32_t n_beams, double min_range, double max_range, int32_t substeps, int32_t n_trans,
                       int32_t n_rot, double rot_step, double* out_pose_n3, int32_t* out_n6, int32_t* scores, uint32_t flags) {
@@ -2554,14 +2564,7 @@ int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, 
     const int extra = (n_trans + substeps - 1) / substeps + 2;
     const double reach = ceil(max_range * inv);
     const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
-    if (!(reach <= (double)max_reach)) {
-        double most = (double)max_reach / inv;                             // the largest max_range with ceil(max_range * inv) <= max_reach
-        if (ceil(most * inv) > (double)max_reach) most = nextafter(most, 0.0);
-        char num[32];
-        snprintf(num, sizeof num, "%.17g", most);
-        return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window that does not fit one workgroup's LDS: the largest "
-                                    "admissible max_range is " + num + " m (ceil(max_range * cells per metre) <= " + std::to_string(max_reach) + ")");
-    }
+    if (!(reach <= (double)max_reach)) return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
     if (h->scan_begun) return fail(h, RBPF_ESTATE, "pose refinement between rbpf_scan_update_begin and rbpf_scan_update_end");
     RefineArgs a;
     a.N = n_scans; a.B = n_beams; a.Wt = n_trans; a.R = n_rot; a.nk = 2 * n_rot + 1;
@@ -2637,6 +2640,131 @@ int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, 
     if (dev_out) return RBPF_OK;
     if (out_pose_n3) HIP_TRY(h, hipMemcpyAsync(out_pose_n3, a.out_pose, N * 24, hipMemcpyDeviceToHost, h->stream));
     if (out_n6) HIP_TRY(h, hipMemcpyAsync(out_n6, a.out_n6, N * 24, hipMemcpyDeviceToHost, h->stream));
+    if (scores) HIP_TRY(h, hipMemcpyAsync(scores, a.scores, vol * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+// ---- scan-to-submap matching (kernels_pairs.hip) -------------------------------------------------------------------
+int rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, const double* ranges, const double* angles,
+                     int32_t n_beams, const int32_t* pairs_m3, int32_t n_pairs, const double* guess_m3, double cells_per_m,
+                     double min_range, double max_range, int32_t substeps, int32_t n_trans, int32_t n_rot, double rot_step,
+                     double* out_pose_m3, int32_t* out_m8, int32_t* scores, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!poses_n3 || !ranges || !angles || !pairs_m3) return fail(h, RBPF_EINVAL, "poses, ranges, angles or pairs is NULL");
+    if (!out_pose_m3 && !out_m8) return fail(h, RBPF_EINVAL, "out_pose_m3 and out_m8 are both NULL");
+    if (flags & ~RBPF_PAIRS_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_scans < 1 || n_pairs < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_scans >= 1, n_pairs >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
+    if (!refine_substeps_ok(substeps)) return fail(h, RBPF_EINVAL, "substeps must be 1, 2, 4, 8 or 16");
+    if (n_trans < 0 || n_trans > 32) return fail(h, RBPF_EINVAL, "0 <= n_trans <= 32 is required");
+    if (n_rot < 0 || n_rot > 100) return fail(h, RBPF_EINVAL, "0 <= n_rot <= 100 is required");
+    const int nk = 2 * n_rot + 1, nw = 2 * n_trans + 1;
+    if ((long long)n_pairs * nk >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_pairs * (2 n_rot + 1) < 2^31 is required");
+    if (!std::isfinite(rot_step) || rot_step < 0.0) return fail(h, RBPF_EINVAL, "rot_step must be finite and >= 0");
+    if (!std::isfinite(cells_per_m) || !(cells_per_m > 0.0)) return fail(h, RBPF_EINVAL, "cells_per_m must be finite and > 0");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
+    for (long long k = 0; k < 3LL * n_scans; ++k)
+        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
+    for (long long k = 0; guess_m3 && k < 3LL * n_pairs; ++k)
+        if (!std::isfinite(guess_m3[k])) return fail(h, RBPF_EINVAL, "guesses must be finite");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    for (int m = 0; m < n_pairs; ++m) {
+        const int32_t* p = pairs_m3 + 3 * (size_t)m;
+        if (p[0] < 0 || p[0] >= n_scans || p[1] < 0 || p[1] >= p[2] || p[2] > n_scans)
+            return fail(h, RBPF_EINVAL, "a pair {q, r0, r1} needs 0 <= q < n_scans and 0 <= r0 < r1 <= n_scans");
+    }
+    const double inv = cells_per_m, invS = inv * (double)substeps;         // exact: a power of two
+    auto in_reach = [&](double c) { return (fabs(c) + max_range) * invS + (double)n_trans < 1073741824.0; };
+    for (int m = 0; m < n_pairs; ++m) {                                    // the guesses and the poses of the runs' scans
+        const int32_t* p = pairs_m3 + 3 * (size_t)m;
+        const double* g = guess_m3 ? guess_m3 + 3 * (size_t)m : poses_n3 + 3 * (size_t)p[0];
+        bool ok = in_reach(g[0]) && in_reach(g[1]);
+        for (int n = p[1]; ok && n < p[2]; ++n) ok = in_reach(poses_n3[3 * (size_t)n]) && in_reach(poses_n3[3 * (size_t)n + 1]);
+        if (!ok) return fail(h, RBPF_EINVAL, "(|coordinate| + max_range) * cells per metre * substeps + n_trans < 2^30 is required of every guess and reference pose");
+    }
+    const int extra = (n_trans + substeps - 1) / substeps + 2;
+    const double reach = ceil(max_range * inv);
+    const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
+    if (!(reach <= (double)max_reach)) return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "pair matching between rbpf_scan_update_begin and rbpf_scan_update_end");
+    RefineArgs a;
+    a.N = n_pairs; a.B = n_beams; a.Wt = n_trans; a.R = n_rot; a.nk = nk;
+    a.s = substeps == 1 ? 0 : substeps == 2 ? 1 : substeps == 4 ? 2 : substeps == 8 ? 3 : 4;
+    a.Mw = (int)reach + extra; a.WW = refine_row_words(a.Mw);
+    a.invS = invS; a.min_range = min_range; a.max_range = max_range;
+    a.fx0 = a.fy0 = a.frows = a.fW = 0; a.field = nullptr;                 // every pair stages its own field
+    const int t1 = nw * refine_runs(nw, a.s);                              // rotations per workgroup: refinement's rule
+    a.kpw = std::max(1, std::min(std::min(16, a.nk), REFINE_BLOCK / t1));
+    while (a.kpw > 1 && (long long)n_pairs * ((a.nk + a.kpw - 1) / a.kpw) < 1024) --a.kpw;
+    if (const char* e = getenv("RBPF_PAIRS_KPW")) a.kpw = std::max(1, std::min(std::min(16, a.nk), atoi(e)));   // for tests
+    const bool dev_out = (flags & RBPF_PAIRS_DEVICE_OUT) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [guesses] [rotations] [scan poses] [beams] [ranges] [centre cells] [runs] [queries] | [fields] [merge words] [guess
+    // scores] [n_used] [n_ref] | host outputs
+    const size_t M = (size_t)n_pairs, N = (size_t)n_scans, nray = N * n_beams, vol = M * nk * nw * nw;
+    const size_t guess_b = M * 16, rot_b = M * nk * 32, pose_at = guess_b + rot_b, beam_at = pose_at + N * 32;
+    const size_t cell_at = beam_at + (size_t)n_beams * 16 + nray * 8, run_at = cell_at + M * 8, query_at = run_at + M * 8, in_b = query_at + M * 4;
+    const size_t field_b = pad(M * (2 * (size_t)a.Mw + 1) * a.WW * 8), merge_b = pad(M * 8) + 3 * pad(M * 4);
+    const size_t pose_b = !dev_out && out_pose_m3 ? pad(M * 24) : 0, m8_b = !dev_out && out_m8 ? pad(M * 32) : 0;
+    const size_t total = pad(in_b) + field_b + merge_b + pose_b + m8_b + (scores && !dev_out ? pad(vol * 4) : 0);
+    if (total + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
+        return fail(h, RBPF_ENOMEM, "pairs, fields and score volume need more than 4 GiB: match fewer pairs per call");
+    HIP_TRY(h, h->reserve(B_PAIRS, total));
+    const Block& d = h->buf[B_PAIRS];
+    Staging& st = h->stage[S_PAIRS];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* sg = reinterpret_cast<double*>(st.p);
+    double* sr = sg + 2 * M;
+    double* sp = reinterpret_cast<double*>(st.p + pose_at);
+    double* sb = reinterpret_cast<double*>(st.p + beam_at);
+    int32_t* sc = reinterpret_cast<int32_t*>(st.p + cell_at);
+    int32_t* sn = reinterpret_cast<int32_t*>(st.p + run_at);
+    int32_t* sq = reinterpret_cast<int32_t*>(st.p + query_at);
+    for (size_t m = 0; m < M; ++m) {
+        const int32_t* p = pairs_m3 + 3 * m;
+        const double* g = guess_m3 ? guess_m3 + 3 * m : poses_n3 + 3 * (size_t)p[0];
+        sg[2 * m] = g[0]; sg[2 * m + 1] = g[1];
+        sc[2 * m] = (int32_t)floor(g[0] * inv); sc[2 * m + 1] = (int32_t)floor(g[1] * inv);
+        sn[2 * m] = p[1]; sn[2 * m + 1] = p[2]; sq[m] = p[0];
+        for (int q = 0; q < nk; ++q) {                                     // host libm: the device never sees an angle
+            const double th = g[2] + (double)(q - n_rot) * rot_step;
+            double* o = sr + (m * nk + q) * 4;
+            o[0] = cos(th); o[1] = sin(th); o[2] = th; o[3] = 0.0;
+        }
+    }
+    for (size_t n = 0; n < N; ++n) {
+        sp[4 * n] = poses_n3[3 * n]; sp[4 * n + 1] = poses_n3[3 * n + 1];
+        sp[4 * n + 2] = cos(poses_n3[3 * n + 2]); sp[4 * n + 3] = sin(poses_n3[3 * n + 2]);
+    }
+    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    a.guess = d.as<const double>(); a.rot = a.guess + 2 * M; a.beam2 = d.as<const double>(beam_at); a.ranges = a.beam2 + 2 * (size_t)n_beams;
+    a.cell0 = d.as<const int32_t>(cell_at);
+    PairsArgs f;
+    f.M = n_pairs; f.B = n_beams; f.Mw = a.Mw; f.WW = a.WW; f.inv = inv; f.min_range = min_range; f.max_range = max_range;
+    f.pose4 = d.as<const double>(pose_at); f.beam2 = a.beam2; f.ranges = a.ranges; f.cell0 = a.cell0;
+    f.runs = d.as<const int32_t>(run_at); f.query = d.as<const int32_t>(query_at);
+    size_t at = pad(in_b);
+    f.fields = d.as<uint2>(at); at += field_b;
+    a.packed = d.as<unsigned long long>(at);
+    a.guess_score = d.as<int32_t>(at + pad(M * 8)); a.n_used = d.as<int32_t>(at + pad(M * 8) + pad(M * 4));
+    f.n_ref = d.as<int32_t>(at + pad(M * 8) + 2 * pad(M * 4));
+    HIP_TRY(h, hipMemsetAsync(a.packed, 0, merge_b, h->stream));
+    at += merge_b;
+    a.out_pose = nullptr; a.out_n6 = nullptr;                              // pairs_final_kernel writes the pair outputs
+    f.out_pose = !out_pose_m3 ? nullptr : dev_out ? out_pose_m3 : d.as<double>(at); at += pose_b;
+    f.out_m8 = !out_m8 ? nullptr : dev_out ? out_m8 : d.as<int32_t>(at); at += m8_b;
+    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(at);
+    launch_match_pairs(f, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    if (out_pose_m3) HIP_TRY(h, hipMemcpyAsync(out_pose_m3, f.out_pose, M * 24, hipMemcpyDeviceToHost, h->stream));
+    if (out_m8) HIP_TRY(h, hipMemcpyAsync(out_m8, f.out_m8, M * 32, hipMemcpyDeviceToHost, h->stream));
     if (scores) HIP_TRY(h, hipMemcpyAsync(scores, a.scores, vol * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return RBPF_OK;

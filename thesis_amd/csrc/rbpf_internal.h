@@ -209,6 +209,23 @@ struct RefineArgs {
     int32_t* scores;                   // [N][nk][2 Wt + 1][2 Wt + 1] or null
     double* out_pose; int32_t* out_n6; // [N][3], [N][6]; either may be null
 };
+// scan-to-submap matching (kernels_pairs.hip): M pairs of a query scan and a run of reference scans.  The search
+// is refinement's over a RefineArgs with N = M, one item per pair; this describes the field each pair draws for itself
+static const int PAIRS_BLOCK = 512;    // lanes of a field workgroup, one per pair
+struct PairsArgs {
+    int M, B;                          // pairs, beams per scan
+    int Mw, WW;                        // as RefineArgs: a pair's field is its window, 2 Mw + 1 rows of WW {occ, dil} word pairs
+    double inv, min_range, max_range;  // cells per metre; a beam is used iff min < r < max
+    const double* pose4;               // [n_scans][4] px, py, cos, sin of the scans' current poses (host libm)
+    const double* beam2;               // [B][2] cos, sin of the beam angles (host libm)
+    const double* ranges;              // [n_scans][B]
+    const int32_t* query;              // [M] the query scan of each pair
+    const int32_t* runs;               // [M][2] reference scans r0 .. r1 - 1
+    const int32_t* cell0;              // [M][2] floor(gx * inv), floor(gy * inv): the window's centre cell (host)
+    uint2* fields;                     // [M][2 Mw + 1][WW]; bit 0 of a row is cell Y0 - Mw
+    int32_t* n_ref;                    // [M] used reference beams of the run
+    double* out_pose; int32_t* out_m8; // [M][3], [M][8]; either may be null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -385,6 +402,8 @@ void launch_view_gain(const DevView& v, const GainArgs& a, hipStream_t s);
 void launch_build_map(const BuildArgs& a, hipStream_t s);                       // adds to a.hits / a.seen
 size_t refine_lds_bytes(int Mw, int WW);
 void launch_refine_poses(const DevView& v, const LocateArgs& f, const RefineArgs& a, hipStream_t s);   // a.packed preset to 0
+size_t pairs_field_lds_bytes(int Mw, int WW);
+void launch_match_pairs(const PairsArgs& p, const RefineArgs& a, hipStream_t s);  // a.packed preset to 0; a.field unused
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

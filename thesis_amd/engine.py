@@ -63,6 +63,20 @@ class RefineResult(NamedTuple):
     cell_size: float     # metres: a translation step is cell_size / substeps
 
 
+class PairResult(NamedTuple):
+    """ParticleEngine.match_pairs: per pair [M] (numpy arrays, or torch tensors on the GPU); thesis_amd/loops.py reads them."""
+    poses: Any           # float64 [M, 3]: the best candidate's pose of the query, the guess itself (bit for bit) where index is (0, 0, 0)
+    index: Any           # int32 [M, 3]: (i, j, k) of the best candidate, in steps of cell_size / substeps and of rot_step
+    score: Any           # int32 [M]: its score, the sum of F = occ + dil of the run's field over the query's used beams
+    score_guess: Any     # int32 [M]: the guess's own score
+    n_used: Any          # int32 [M]: the query's beams with min_range < range < max_range; score <= 2 n_used
+    n_ref: Any           # int32 [M]: the used beams of the run's scans (beams, not cells)
+    scores: Any          # int32 [M, 2 rotations + 1, 2 window + 1, 2 window + 1] indexed [m, k, i, j], or None
+    substeps: int
+    rot_step: float
+    cell_size: float     # metres: a translation step is cell_size / substeps
+
+
 class Proposal(NamedTuple):
     """ParticleEngine.proposal: one particle's proposal frame and its K samples."""
     U: np.ndarray          # [3, 3] pseudo-inverse square root of the matcher covariance: maha = |(g - mean) U|^2
@@ -1338,10 +1352,77 @@ class ParticleEngine:
     def refine_max_range(self, substeps: int = 4, window: int = 12) -> float:
         """The largest max_range refine_poses admits at this cell size for a window of `window` steps of cell_size / substeps:
         ceil(max_range * cells per metre) + ceil(window / substeps) + 2 <= 367 (include/rbpf_hip.h, the window limit)."""
+        return self.match_max_range(None, substeps, window)
+
+    # -- pair matching (include/rbpf_hip.h: rbpf_match_pairs; DESIGN.md 3.18; thesis_amd/loops.py) -------------------------------
+    def match_pairs(self, poses, ranges, angles, pairs, guesses=None, cell_size: Optional[float] = None, substeps: int = 1,
+                    window: int = 16, rotations: int = 20, rot_step: float = 0.008726646259971648, min_range: Optional[float] = None,
+                    max_range: Optional[float] = None, return_scores: bool = False, device: bool = False) -> PairResult:
+        """Where the query scan of each pair sits among the pair's reference scans: `pairs` [M, 3] = (q, r0, r1) matches scan q
+        of `ranges` [N, B] (beam directions `angles` [B]) against the scans r0 .. r1 - 1 drawn at their poses `poses` [N, 3].  No
+        particle's map is read: the run's end points are the map, as occ + dil over cells of `cell_size` metres (None: the
+        engine's tile_len / dim).  `guesses` [M, 3] are the guessed poses of the queries (None: poses[q]).  The search is
+        refine_poses's: every translation of -window .. window steps of cell_size / substeps and every rotation of -rotations ..
+        rotations steps of `rot_step` radians (default 0.5 degrees) round the guess, beams with min_range < range < max_range
+        (defaults cfg.match_min_range, cfg.match_max_range), the same tie order, so a guess that is already best comes back bit
+        for bit.  A [3] triple is M = 1.  return_scores: the whole score volume as well.  max_range is limited as in
+        refine_poses (match_max_range).  device=True: torch tensors on the engine's device, ready for work on torch's current
+        stream."""
+        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if rg.ndim == 1:
+            rg = rg.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
+            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32)
+        if pr.ndim == 1:
+            pr = pr.reshape(1, -1)
+        if pr.ndim != 2 or pr.shape[1] != 3:
+            raise ValueError("pairs must be [M, 3]")
+        m = pr.shape[0]
+        gs = None
+        if guesses is not None:
+            gs = _f64(guesses).reshape(-1, 3) if np.ndim(guesses) == 1 else _f64(guesses)
+            if gs.shape != (m, 3):
+                raise ValueError("guesses must be [M, 3]")
+        inv = self.dim / float(self.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
+        cs = float(self.cfg.cell_size) if cell_size is None else float(cell_size)
+        nw, nk = 2 * int(window) + 1, 2 * int(rotations) + 1
+        lo = float(self.cfg.match_min_range if min_range is None else min_range)
+        hi = float(self.cfg.match_max_range if max_range is None else max_range)
+        shapes = [(m, 3), (m, 8)] + ([(m, max(nk, 0), max(nw, 0), max(nw, 0))] if return_scores else [])   # a bad window is the library's to refuse
+        same_stream = False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            outs = [torch.empty(sh, dtype=torch.float64 if k == 0 else torch.int32, device=dev) for k, sh in enumerate(shapes)]
+            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            outs = [np.empty(sh, dtype=np.float64 if k == 0 else np.int32) for k, sh in enumerate(shapes)]
+            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
+        if not return_scores:
+            ptrs.append(None)
+        self._check(self._lib.rbpf_match_pairs(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], _ip(pr), m,
+                                               None if gs is None else _dp(gs), inv, lo, hi, int(substeps), int(window), int(rotations),
+                                               float(rot_step), *ptrs, _lib.RBPF_PAIRS_DEVICE_OUT if device else 0))
+        if device and not same_stream:
+            self.synchronize()
+        m8 = outs[1]
+        return PairResult(outs[0], m8[:, 0:3], m8[:, 3], m8[:, 4], m8[:, 5], m8[:, 6], outs[2] if return_scores else None, int(substeps),
+                          float(rot_step), cs)
+
+    def match_max_range(self, cell_size: Optional[float] = None, substeps: int = 1, window: int = 16) -> float:
+        """The largest max_range match_pairs admits at `cell_size` (None: the engine's) for a window of `window` steps of
+        cell_size / substeps: refine_max_range's limit at that cell size."""
         reach = int(self._lib.rbpf_refine_max_reach(int(substeps), int(window)))
         if reach < 0:
             raise ValueError("substeps must be 1, 2, 4, 8 or 16 and 0 <= window <= 32")
-        inv = self.dim / float(self.cfg.tile_len_m)
+        inv = self.dim / float(self.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
         most = reach / inv
         return float(np.nextafter(most, 0.0)) if np.ceil(most * inv) > reach else most
 

@@ -1,0 +1,208 @@
+"""Loops closed after the run (ParticleEngine.match_pairs; include/rbpf_hip.h, rbpf_match_pairs).
+
+A path that comes back to a place with accumulated drift draws that place twice, and refine_trajectory cannot mend it: each copy
+of a wall holds its own scans where they are.  Here a scan is matched against earlier scans only, over a window wide enough for
+the drift (candidates, match), the matches become constraints between poses, and a 2-D pose graph spreads them along the path
+(relax).  close_loops runs the three on a filter's trajectory log and draws the map again; refine_trajectory then polishes it:
+
+    closed = loops.close_loops(pf.engine, pf.scans, angles, min_gap=200, radius=3.0)
+    polished = refine.refine_trajectory(pf.engine, pf.scans, angles, poses=closed.poses)
+    raster = rebuild.as_raster(polished.built, engine=pf.engine)
+
+Candidates come from the poses, not from appearance: a loop whose drift exceeds `radius` plus the search window is not found.
+Everything here is host NumPy and SciPy; the search runs on the GPU.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, NamedTuple, Optional
+
+import numpy as np
+
+from . import rebuild as _rebuild
+from . import refine as _refine
+
+SCRATCH_BYTES = 1 << 30    # what match() lets one match_pairs call take of the library's 4 GiB
+
+
+class LoopEdges(NamedTuple):
+    q: np.ndarray              # [M] int32: the query scan of each pair
+    r: np.ndarray              # [M] int32: the middle scan of its run, whose frame z is in
+    z: np.ndarray              # [M, 3]: the matched pose of scan q seen from poses[r]: (R_r^T (t_q - t_r), theta_q - theta_r)
+    fraction: np.ndarray       # [M] score / (2 n_used) of the match, 0 where no beam was used
+    fraction_guess: np.ndarray # [M] the same of the guess
+    accepted: np.ndarray       # [M] bool
+
+
+class LoopRound(NamedTuple):
+    pairs: int                 # candidate pairs
+    accepted: int              # loop edges that went into the graph
+    moved: float               # the largest translation of a pose in the relaxation, metres
+
+
+class ClosedTrajectory(NamedTuple):
+    poses: np.ndarray          # [n, 3] the poses of the scans after the last round
+    records: np.ndarray        # [n] int64: the trajectory record of each
+    edges: LoopEdges           # the last round's pairs
+    built: object              # BuiltMap: the map the poses draw
+    rounds: List[LoopRound]
+
+
+def _wrap(a):
+    return (np.asarray(a) + math.pi) % (2.0 * math.pi) - math.pi
+
+
+def candidates(poses, min_gap: int, radius: float, half_run: int = 5, stride: int = 1, per_query: int = 1) -> np.ndarray:
+    """Pairs {q, r0, r1} int32 [M, 3] for match_pairs.  For every `stride`-th scan q: the earlier scans r with r + half_run <
+    q - min_gap (the whole run lies more than min_gap scans back) within `radius` metres of q's position, nearest first, ties
+    to the smaller r, `per_query` of them; each gives the run max(r - half_run, 0) .. r + half_run.  Empty [0, 3] if none."""
+    t = np.asarray(poses, dtype=np.float64).reshape(-1, 3)[:, :2]
+    if min_gap < 0 or half_run < 0 or stride < 1 or per_query < 1 or not radius >= 0.0:
+        raise ValueError("min_gap >= 0, radius >= 0, half_run >= 0, stride >= 1 and per_query >= 1 are required")
+    out = []
+    for q in range(0, len(t), int(stride)):
+        last = q - int(min_gap) - int(half_run)          # r < last
+        if last <= 0:
+            continue
+        d = np.hypot(t[:last, 0] - t[q, 0], t[:last, 1] - t[q, 1])
+        near = np.flatnonzero(d <= radius)
+        for r in near[np.argsort(d[near], kind="stable")][:int(per_query)]:
+            out.append((q, max(int(r) - int(half_run), 0), int(r) + int(half_run) + 1))
+    return np.array(out, dtype=np.int32).reshape(-1, 3)
+
+
+def pairs_per_call(engine, n_scans: int, n_beams: int, cell_size=None, substeps: int = 1, window: int = 16, rotations: int = 20,
+                   max_range=None, limit: Optional[int] = None, **_) -> int:
+    """How many pairs one match_pairs call takes within `limit` bytes of scratch (default SCRATCH_BYTES; include/rbpf_hip.h
+    has the terms): per pair 112 bytes with the host outputs, 32 per rotation and the field of its window; per scan 32 bytes
+    and 8 per beam."""
+    inv = engine.dim / float(engine.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
+    hi = float(engine.cfg.match_max_range if max_range is None else max_range)
+    mw = int(math.ceil(hi * inv)) + -(-int(window) // int(substeps)) + 2
+    ww = (((2 * mw + 32) >> 5) + 2) | 1
+    per_pair = 112 + 32 * (2 * int(rotations) + 1) + (2 * mw + 1) * ww * 8
+    fixed = n_scans * (32 + 8 * n_beams) + 16 * n_beams + 4096
+    return max(1, (int(SCRATCH_BYTES if limit is None else limit) - fixed) // per_pair)
+
+
+def match(engine, poses, ranges, angles, pairs, accept: float = 0.55, gain: float = 0.1, min_used: int = 30, **search) -> LoopEdges:
+    """match_pairs on `pairs` (from candidates) with the scans' current poses as guesses, in as many calls as the scratch limit
+    asks for.  Edge m says where scan q sits in the frame of poses[r], r = (r0 + r1) // 2 the middle of the run.  It is
+    accepted if its fraction score / (2 n_used) reaches `accept` with at least `min_used` beams, and the search either raised
+    the guess's fraction by `gain` or kept the guess: a match that moved the pose for nothing is noise.  `search` goes to
+    ParticleEngine.match_pairs (cell_size, substeps, window, rotations, rot_step, min_range, max_range)."""
+    for bad in ("return_scores", "device", "guesses"):
+        if bad in search:
+            raise ValueError(f"match() reads every result on the host and guesses from the poses: {bad} is not for it")
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    ranges = np.ascontiguousarray(ranges, dtype=np.float64).reshape(len(poses), -1)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 3)
+    M = len(pairs)
+    q, r = pairs[:, 0].copy(), ((pairs[:, 1] + pairs[:, 2]) // 2).astype(np.int32)
+    out, index, score, guess, used = np.empty((M, 3)), np.empty((M, 3), np.int32), np.empty(M, np.int64), np.empty(M, np.int64), np.empty(M, np.int64)
+    step = pairs_per_call(engine, len(poses), ranges.shape[1], **search)
+    for k in range(0, M, step):
+        res = engine.match_pairs(poses, ranges, angles, pairs[k:k + step], **search)
+        out[k:k + step], index[k:k + step] = res.poses, res.index
+        score[k:k + step], guess[k:k + step], used[k:k + step] = res.score, res.score_guess, res.n_used
+    some = used > 0
+    frac, frac_guess = np.zeros(M), np.zeros(M)
+    frac[some], frac_guess[some] = score[some] / (2.0 * used[some]), guess[some] / (2.0 * used[some])
+    c, s = np.cos(poses[r, 2]), np.sin(poses[r, 2])
+    dx, dy = out[:, 0] - poses[r, 0], out[:, 1] - poses[r, 1]
+    z = np.stack([c * dx + s * dy, -s * dx + c * dy, _wrap(out[:, 2] - poses[r, 2])], axis=1).reshape(M, 3)
+    stayed = ~np.any(index != 0, axis=1)
+    accepted = (frac >= accept) & (used >= min_used) & ((frac - frac_guess >= gain) | stayed)
+    return LoopEdges(q, r, z, frac, frac_guess, accepted)
+
+
+def relative(poses, i, j) -> np.ndarray:
+    """[E, 3]: pose j seen from pose i, (R_i^T (t_j - t_i), wrap(theta_j - theta_i)): the measurement an edge (i, j) holds when
+    the poses agree with it."""
+    p = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    c, s = np.cos(p[i, 2]), np.sin(p[i, 2])
+    dx, dy = p[j, 0] - p[i, 0], p[j, 1] - p[i, 1]
+    return np.stack([c * dx + s * dy, -s * dx + c * dy, _wrap(p[j, 2] - p[i, 2])], axis=-1)
+
+
+def relax(poses, edges_ij, z, sigma_t, sigma_th, iterations: int = 20, tol: float = 1e-9) -> np.ndarray:
+    """The poses [n, 3] that fit the edges best: Gauss-Newton on the sum over the edges (i, j) of |e_t|^2 / sigma_t^2 +
+    e_th^2 / sigma_th^2 with e = [R_i^T (t_j - t_i) - z_t; wrap(theta_j - theta_i - z_th)], analytic Jacobians, sparse normal
+    equations, pose 0 held where it is.  sigma_t, sigma_th: a number, or one per edge.  Stops when no component of a step
+    exceeds `tol`.  Poses no edge reaches from pose 0 make the system singular: the caller joins consecutive scans."""
+    from scipy import sparse
+    from scipy.sparse.linalg import spsolve
+    x = np.array(poses, dtype=np.float64).reshape(-1, 3)
+    ij = np.asarray(edges_ij, dtype=np.int64).reshape(-1, 2)
+    z = np.asarray(z, dtype=np.float64).reshape(-1, 3)
+    n, E = len(x), len(ij)
+    if E == 0 or n < 2:
+        return x
+    if len(z) != E or ij.min() < 0 or ij.max() >= n or np.any(ij[:, 0] == ij[:, 1]):
+        raise ValueError("edges must join two different poses and come with one measurement each")
+    wt = 1.0 / np.broadcast_to(np.asarray(sigma_t, dtype=np.float64), (E,))
+    wh = 1.0 / np.broadcast_to(np.asarray(sigma_th, dtype=np.float64), (E,))
+    i, j = ij[:, 0], ij[:, 1]
+    e3 = 3 * np.arange(E)
+    for _ in range(int(iterations)):
+        c, s = np.cos(x[i, 2]), np.sin(x[i, 2])
+        dx, dy = x[j, 0] - x[i, 0], x[j, 1] - x[i, 1]
+        ex, ey = (c * dx + s * dy - z[:, 0]) * wt, (-s * dx + c * dy - z[:, 1]) * wt
+        eh = _wrap(x[j, 2] - x[i, 2] - z[:, 2]) * wh
+        # rows 3e, 3e + 1, 3e + 2; columns 3i .. 3i + 2 and 3j .. 3j + 2
+        rows = np.concatenate([e3, e3, e3, e3, e3, e3 + 1, e3 + 1, e3 + 1, e3 + 1, e3 + 1, e3 + 2, e3 + 2])
+        cols = np.concatenate([3 * i, 3 * i + 1, 3 * i + 2, 3 * j, 3 * j + 1, 3 * i, 3 * i + 1, 3 * i + 2, 3 * j, 3 * j + 1, 3 * i + 2, 3 * j + 2])
+        vals = np.concatenate([-c * wt, -s * wt, (-s * dx + c * dy) * wt, c * wt, s * wt,
+                               s * wt, -c * wt, (-c * dx - s * dy) * wt, -s * wt, c * wt, -wh, wh])
+        J = sparse.csc_matrix((vals, (rows, cols)), shape=(3 * E, 3 * n))[:, 3:]       # pose 0 is fixed
+        e = np.stack([ex, ey, eh], axis=1).reshape(-1)
+        step = spsolve((J.T @ J).tocsc(), -(J.T @ e))
+        x[1:] += np.asarray(step).reshape(-1, 3)
+        if np.max(np.abs(step)) < tol:
+            break
+    return x
+
+
+def close_loops(engine, log, angles, particle="best", rounds: int = 1, odo_sigma=(0.02, 0.005), loop_sigma=(0.05, 0.01),
+                cell_size: Optional[float] = None, build_args: Optional[dict] = None, poses=None, **search) -> ClosedTrajectory:
+    """Closes the loops of a logged run.  refine.scan_poses picks the scans and the poses of `particle`'s trajectory (`poses`
+    [n, 3] replaces them).  Each round: odometry edges between consecutive scans hold the current poses' own relative poses
+    (sigmas `odo_sigma` = (metres, radians) per edge), candidates() proposes pairs, match() turns the accepted ones into loop
+    edges (`loop_sigma`), relax() spreads them.  Then rebuild.rebuild_at draws the map at the new poses (`build_args`:
+    min_range, max_range, box, device).  `search` holds candidates' min_gap (default 50), radius (2 m), half_run, stride and
+    per_query, match's accept, gain and min_used, and match_pairs' search arguments.  With no accepted edge the poses come
+    back as they went in, bit for bit."""
+    if rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    records, start, ranges = _refine.scan_poses(engine, log, particle)
+    if poses is not None:
+        start = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        if len(start) != len(records):
+            raise ValueError(f"{len(start)} poses for {len(records)} logged scans")
+    search = dict(search)
+    cand = {k: search.pop(k) for k in ("half_run", "stride", "per_query") if k in search}
+    min_gap, radius = search.pop("min_gap", 50), search.pop("radius", 2.0)
+    if cell_size is not None:
+        search["cell_size"] = cell_size
+    cur = np.array(start, dtype=np.float64)
+    n = len(cur)
+    chain = np.stack([np.arange(n - 1), np.arange(1, n)], axis=1)
+    out: List[LoopRound] = []
+    edges = None
+    for _ in range(rounds):
+        pairs = candidates(cur, min_gap, radius, **cand)
+        edges = match(engine, cur, ranges, angles, pairs, **search)
+        ok = edges.accepted
+        if not ok.any():
+            out.append(LoopRound(len(pairs), 0, 0.0))
+            break
+        n_ok = int(ok.sum())
+        ij = np.concatenate([chain, np.stack([edges.r[ok], edges.q[ok]], axis=1)])
+        z = np.concatenate([relative(cur, chain[:, 0], chain[:, 1]), edges.z[ok]])
+        st = np.concatenate([np.full(n - 1, float(odo_sigma[0])), np.full(n_ok, float(loop_sigma[0]))])
+        sh = np.concatenate([np.full(n - 1, float(odo_sigma[1])), np.full(n_ok, float(loop_sigma[1]))])
+        new = relax(cur, ij, z, st, sh)
+        out.append(LoopRound(len(pairs), n_ok, float(np.hypot(new[:, 0] - cur[:, 0], new[:, 1] - cur[:, 1]).max())))
+        cur = new
+    built = _rebuild.rebuild_at(engine, cur, ranges, angles, cell_size=cell_size, **dict(build_args or {}))
+    return ClosedTrajectory(cur, records, edges, built, out)

@@ -101,16 +101,20 @@ def _map_engine(engine, box, cell_size: float, n_beams: int):
 
 
 def refine_trajectory(engine, log, angles, particle="best", rounds: int = 2, cell_size: Optional[float] = None, map_engine=None,
-                      build_args: Optional[dict] = None, **search) -> RefinedTrajectory:
+                      build_args: Optional[dict] = None, poses=None, **search) -> RefinedTrajectory:
     """Refines the poses of every logged scan against the map of all scans, `rounds` times: build_map at the poses, the map
     (rebuild.as_source) placed into particle 0 of a one-particle engine of `cell_size` (default the engine's own; `map_engine`
     supplies that engine, otherwise one is created and closed), refine_poses on all scans in chunks of CHUNK, build_map again
     at the new poses.  `particle` picks the starting trajectory as rebuild.rebuild does.  `search` goes to refine_poses,
     `build_args` (min_range, max_range, device) to build_map: at 0.025 m its window admits a max_range of 12.7 m, less than
-    the default cfg.max_ray_m.  One box serves every round: the first poses' box grown by what `rounds` windows can move a pose."""
+    the default cfg.max_ray_m.  One box serves every round: the first poses' box grown by what `rounds` windows can move a pose.
+    `poses` [n, 3] replaces the chosen trajectory's poses of the logged scans (loops.close_loops hands its result on this way)."""
     if rounds < 1:
         raise ValueError("rounds must be at least 1")
-    records, poses, ranges = scan_poses(engine, log, particle)
+    records, chosen, ranges = scan_poses(engine, log, particle)
+    poses = chosen if poses is None else np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    if len(poses) != len(records):
+        raise ValueError(f"{len(poses)} poses for {len(records)} logged scans")
     cs = float(engine.cfg.cell_size if cell_size is None else cell_size)
     inv = engine.dim / float(engine.cfg.tile_len_m) if cell_size is None else 1.0 / cs
     build_args = dict(build_args or {})
