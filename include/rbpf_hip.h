@@ -377,6 +377,9 @@ int  rbpf_place_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
  * in either mode. */
 int  rbpf_set_map_updates(rbpf_handle* h, int32_t on);
 int  rbpf_get_map_updates(rbpf_handle* h, int32_t* on);
+/* Workgroups the event-walk map kernel was launched with in the last map update: min(P, CUs, RBPF_EV_GRID) resident ones, P with
+ * RBPF_EV_RESIDENT=0, 0 if that kernel did not run (tests of the launch shape; no device access). */
+int  rbpf_get_map_update_workgroups(rbpf_handle* h, int32_t* n);
 
 /* ---- scan casting: what a lidar at a pose would see in a particle's map ------------------------------------------------
  * particle >= 0: all n_poses poses (x, y, theta) are cast in that particle's map.  particle == -1: n_poses must equal P

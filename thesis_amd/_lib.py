@@ -130,6 +130,7 @@ PROTOTYPES = {
                        C.c_void_p, C.c_void_p]),
     "rbpf_set_map_updates": (C.c_int, [_H, C.c_int32]),
     "rbpf_get_map_updates": (C.c_int, [_H, _I]),
+    "rbpf_get_map_update_workgroups": (C.c_int, [_H, _I]),
     "rbpf_cast_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_locate_scan": (C.c_int, [_H, C.c_int32, _I, _D, _D, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_align_points": (C.c_int, [_H, C.c_int32, _I, _D, C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,

@@ -1,6 +1,6 @@
 // kernels_mapev.hip -- a5: HybridMap.update (hybridmap.py:95-145): the event-detecting walk (round 3).
 //
-// One 1024-thread workgroup per particle, LDS window of 8-bit hit fields in GLOBAL cell-index space (as
+// One 1024-thread workgroup at a time per particle (resident workgroups take particles from a queue), LDS window of 8-bit hit fields in GLOBAL cell-index space (as
 // kernels_mapray.hip: a ray step is pure arithmetic, the index map is folded in by the write-back).  Same exact
 // semantics as the other map kernels (kernels_mapupdate.hip has the ordered-replay argument).  What is different:
 //
@@ -24,6 +24,13 @@
 //   Reference: hybridmap.py:95-145 (update), :274-301 (Bresenham), gridmap.py:86-117 (clamped adds).
 #include <hip/hip_ext.h>
 
+#include <algorithm>
+#include <cstdio>
+#include <cstddef>
+#include <cstdlib>
+#include <type_traits>
+#include <vector>
+
 #include "rbpf_mapupdate.h"
 
 namespace rbpf {
@@ -31,6 +38,42 @@ namespace rbpf {
 #if defined(RBPF_STAMPS) && defined(EV_BARRIER_WAITS)   // diagnostic: cycles every wave spends at the workgroup's barriers (printed by workgroup 0)
 #undef BAR_LDS
 #define BAR_LDS() do { const long long t0_ = clock64(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); { const long long d_ = clock64() - t0_; bar_wait += d_; if (bar_n < 12) bar_w[bar_n] = (int)d_; } ++bar_n; } while (0)
+#endif
+
+// Diagnostic (-DRBPF_STAMPS -DEV_STAMP_TURNOVER): per particle the constant-rate clock and the cycle counter when its workgroup
+// takes it up and when the last of the sixteen waves is through with it, and the workgroup; the launcher writes the last launch's
+// records to the file RBPF_EV_TURNOVER_OUT names (tools/probe_stamps.py reads it).  The product build has none of this.
+#if defined(RBPF_STAMPS) && defined(EV_STAMP_TURNOVER)
+static const int EV_TURN_MAX = 16384, EV_TURN_WORDS = 5;
+__device__ unsigned long long ev_turn[EV_TURN_WORDS * EV_TURN_MAX];      // realtime in, realtime out, cycles in, cycles out, workgroup
+#define EV_TURN_IN(p) do { if (threadIdx.x == 0 && (p) < EV_TURN_MAX) { unsigned long long* r_ = ev_turn + EV_TURN_WORDS * (p); r_[0] = wall_clock64(); r_[2] = (unsigned long long)clock64(); r_[4] = blockIdx.x; } } while (0)
+#define EV_TURN_OUT(p) do { if ((threadIdx.x & 63) == 0 && (p) < EV_TURN_MAX) { unsigned long long* r_ = ev_turn + EV_TURN_WORDS * (p); atomicMax(&r_[1], (unsigned long long)wall_clock64()); atomicMax(&r_[3], (unsigned long long)clock64()); } } while (0)
+static void ev_turnover_begin(hipStream_t s) {
+    void* d = nullptr;
+    if (getenv("RBPF_EV_TURNOVER_OUT") && hipGetSymbolAddress(&d, HIP_SYMBOL(ev_turn)) == hipSuccess) (void)hipMemsetAsync(d, 0, sizeof(unsigned long long) * EV_TURN_WORDS * EV_TURN_MAX, s);
+}
+static void ev_turnover_end(const DevView& v, int grid, hipStream_t s) {
+    const char* path = getenv("RBPF_EV_TURNOVER_OUT");
+    void* d = nullptr;
+    if (!path || hipGetSymbolAddress(&d, HIP_SYMBOL(ev_turn)) != hipSuccess) return;
+    const int n = std::min(v.P, EV_TURN_MAX);
+    std::vector<unsigned long long> rec((size_t)EV_TURN_WORDS * n);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(rec.data(), d, rec.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    int dev = 0, cus = 0, khz = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) { (void)hipGetLastError(); khz = 0; }
+    if (FILE* f = fopen(path, "w")) {
+        fprintf(f, "particles %d workgroups %d cus %d wall_clock_khz %d\n", n, grid, cus, khz);
+        for (int p = 0; p < n; ++p) fprintf(f, "%llu %llu %llu %llu %llu\n", rec[5 * p], rec[5 * p + 1], rec[5 * p + 2], rec[5 * p + 3], rec[5 * p + 4]);
+        fclose(f);
+    }
+}
+#else
+#define EV_TURN_IN(p) do { } while (0)
+#define EV_TURN_OUT(p) do { } while (0)
+static inline void ev_turnover_begin(hipStream_t) { }
+static inline void ev_turnover_end(const DevView&, int, hipStream_t) { }
 #endif
 
 static const int EB = 1024;                    // threads per particle
@@ -136,9 +179,30 @@ __device__ __forceinline__ int ev_hash_find(const uint32_t* keys, int T, int log
 }
 
 
-__global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
+// What a particle's preamble needs from global memory before it can start: made by ONE wave, for the workgroup's next particle
+// while the current one is written back, so that the chains slot -> tile-table row and pose -> sine / cosine are through when
+// the next particle starts (rec->p says whose record it is).
+struct EvNext { double px, py, sn, cs; int p, slot; int32_t tab[49]; };
+__device__ __forceinline__ void ev_prefetch(const DevView& v, int p, EvNext* rec, int lane) {
+    const int LL = v.L * v.L, slot = v.slot[p];
+    if (lane < LL) rec->tab[lane] = v.tile_tab[(size_t)slot * LL + lane];
+    double sn, cs_;
+    sincos(v.upd_pose[2 * v.P + p], &sn, &cs_);
+    if (lane == 0) { rec->px = v.upd_pose[p]; rec->py = v.upd_pose[v.P + p]; rec->sn = sn; rec->cs = cs_; rec->slot = slot; rec->p = p; }
+}
+
+// One particle's update by the whole workgroup.  `draw`: thread 0 takes the workgroup's NEXT particle from the queue (its first
+// one is blockIdx.x, the queue hands out gridDim.x, gridDim.x + 1, ...) before anything else, so that the add's round trip
+// lies under the preamble's loads, and leaves it in *s_next (v.P or more: none) before the particle's first barrier - or
+// before it returns ahead of that barrier.  Every return is uniform over the workgroup; the caller's barrier follows.
+__device__ __forceinline__ void map_update_ev_particle(const DevView& v, const int p, const bool draw, int* s_next, EvNext* rec) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tid_ = threadIdx.x;
+    asm volatile("" : "+v"(tid_));                 // (what hangs on the thread's number is worked out per particle too: kept across the caller's loop it spilled)
+    __builtin_assume((unsigned)tid_ < (unsigned)EB);
+    const int tid = tid_, lane = tid & 63, wave = tid >> 6;
+    int nxt = v.P;
+    if (draw && tid == 0) nxt = (int)gridDim.x + (int)atomicAdd(&v.ev_queue[0], 1u);
     const EvGeom G = ev_geom(v.B, v.reach);
     uint32_t* const cnt = reinterpret_cast<uint32_t*>(smem + G.o_cnt);     // 8-bit fields: bit 0 = flagged, bits 1-7 = passes; [row = global x][col = global y]
     uint8_t*  const cnt8 = smem + G.o_cnt;
@@ -163,12 +227,20 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     __shared__ int s_lcnt[MAXLEV + 1], s_lfill[MAXLEV + 1], s_nk[MAXLEV + 2], s_lp[MAXLEV + 3], s_nlev;
     __shared__ int s_nev, s_written, s_wbq;
     __shared__ unsigned long long s_cells;
-    __shared__ double s_sincos[2];
     __shared__ uint8_t s_ggf[192];                    // per (tile column, 32-column group): a glitched column among its 33
 
     const int LL = v.L * v.L;
-    int32_t* tab = v.tile_tab + (size_t)v.slot[p] * LL;
     STAMP_DECL;
+    // No record of this particle (the workgroup's first one, or the one before it left early): wave 0 makes it on the spot.  Every wave
+    // reads rec->p while nobody writes the record - the last writer is behind the caller's barrier, the next one behind the first
+    // barrier here, which a wave reaches only after its read - so all sixteen take the same branch and the same barriers.
+    const int rec_p = UNI(rec->p);
+    if (rec_p != p) {
+        __syncthreads();                           // every wave has read rec->p
+        if (wave == 0) ev_prefetch(v, p, rec, lane);
+        __syncthreads();
+    }
+    int32_t* tab = v.tile_tab + (size_t)UNI(rec->slot) * LL;
 #if defined(RBPF_STAMPS) && defined(EV_BARRIER_WAITS)
     long long bar_wait = 0; int bar_n = 0; const long long t_begin = clock64(); int bar_w[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -178,18 +250,19 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     const double pre_x0 = pb0 < v.B ? v.bx[pb0] : 0.0, pre_y0 = pb0 < v.B ? v.by[pb0] : 0.0, pre_s0 = pb0 < v.B ? v.bscale[pb0] : 0.0;
     const double pre_x1 = pb1 < v.B ? v.bx[pb1] : 0.0, pre_y1 = pb1 < v.B ? v.by[pb1] : 0.0, pre_s1 = pb1 < v.B ? v.bscale[pb1] : 0.0;
     const int pre_f0 = pb0 < v.B ? v.bflags[pb0] : 0, pre_f1 = pb1 < v.B ? v.bflags[pb1] : 0;
-    const double s_px = v.upd_pose[p], s_py = v.upd_pose[v.P + p];
+    const double s_px = rec->px, s_py = rec->py;
     int x0, y0;
     // (the LUT must cover the index map's margin here, only the rays' reach in the other kernels: which poses are RBPF_ERANGE depends on it)
-    if (!fan_preamble<EB>(v, tab, p, tid, s_px, s_py, v.reach + 2, G.fanw, s_sincos, ux, uy, x0, y0)) return;
+    if (!fan_preamble_from<EB>(v, rec->tab, p, tid, s_px, s_py, v.reach + 2, G.fanw, ux, uy, x0, y0)) { if (tid == 0) *s_next = nxt; return; }
     const int fxl = x0 - v.reach - 2, fyl = y0 - v.reach - 2, nfx = 2 * v.reach + 5;
     uint16_t* const s_bins = reinterpret_cast<uint16_t*>(cnt);               // [8 NBIN] rays per (class, slope bucket) (the window is not in use yet)
     uint16_t* const s_far = s_bins + 8 * NBIN;                               // ... of the rays that reach the 8-bit fields
     if (tid == 0) {
         s_fan[0] = x0; s_fan[1] = x0; s_fan[2] = y0; s_fan[3] = y0;
         s_cells = 0; s_fb = 0; s_exact = 0; s_nev = 0; s_written = 0;
+        *s_next = nxt;
     }
-    for (int i = tid; i < LL; i += EB) { s_need[i] = 0; s_tab[i] = tab[i]; }
+    for (int i = tid; i < LL; i += EB) { s_need[i] = 0; s_tab[i] = rec->tab[i]; }
     for (int i = tid; i < 8 * NBIN; i += EB) reinterpret_cast<uint32_t*>(s_bins)[i] = 0;     // both bucket arrays
     if (tid < 192) s_ggf[tid] = 0;
     if (tid <= MAXLEV) s_lcnt[tid] = 0;
@@ -198,7 +271,8 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
 #ifndef EV_STAMP_FLAGS
     STAMP(0);
 #endif
-    const double s_s = s_sincos[0], s_c = s_sincos[1];
+    const double s_s = rec->sn, s_c = rec->cs;
+    const int nxt_p = UNI(*s_next);                // the workgroup's next particle (v.P or more: none)
 
     const int C = v.R * v.dim + v.dim / 2;
     const int Uxs = UNI(ux[x0 - fxl]), Uys = UNI(uy[y0 - fyl]);
@@ -561,6 +635,8 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
         }
         if (tid == 0) s_wbq = 0;
         BAR_LDS();
+        // the next particle's record, as one more item of the write-back's queue: the wave that makes it joins the others a batch or so later
+        if (S1 == S_hi && wave == EB / 64 - 1 && nxt_p < v.P) ev_prefetch(v, nxt_p, rec, lane);
         // ---- write-back (rbpf_mapupdate.h): the flagged cells get a value from their counts like all others; their real value
         //      follows after the windows ----
         strip_write_back<FIELD_COUNT_HI, true, true, false>(v, sg, S0, S1, gx_base, C, fxl, ggf_base, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
@@ -726,14 +802,74 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(DevView v) {
     }
 }
 
+// Resident workgroups (`resident` != 0, grid = min(P, CUs)): a workgroup fills a CU (1024 threads, ~157 KB of LDS), so with
+// one workgroup per particle nothing covers the time between a workgroup's last wave and the first instruction of the next
+// one on that CU.  Here a workgroup runs particle blockIdx.x, then whatever the queue word v.ev_queue[0] hands it, until an
+// index >= P comes back.  The barrier between two particles waits for LDS traffic only: the static __shared__ words and
+// the window are reused, the previous particle's stores to its own tiles stay in flight.  No workgroup waits for
+// another one, so nothing depends on how many of them run at the same time.  The queue re-arms itself: a workgroup
+// that leaves has made its last draw, so the one that counts itself last in v.ev_queue[1] puts both words back to
+// zero for the next launch in the stream.  resident == 0: one workgroup per particle, no draw (A/B runs, tests).
+// THE KERNEL HAS ONE ARGUMENT, this struct: the loop below reads `v` through the kernel-argument segment's own address, where a
+// sole argument lies by construction (and `v` first in it: the static_assert).  Do not add a second argument; add a member.
+struct EvKernArgs { DevView v; int resident; };
+static_assert(offsetof(EvKernArgs, v) == 0 && std::is_standard_layout<EvKernArgs>::value, "map_update_ev_kernel reads DevView at offset 0 of its argument segment");
+__global__ __launch_bounds__(EB) void map_update_ev_kernel(EvKernArgs ka_) {
+    const DevView& v = ka_.v;
+    const int resident = ka_.resident;
+    __shared__ int s_next[2];                      // the next particle, by parity of the round: a wave may still read one while thread 0 writes the other
+    __shared__ EvNext s_rec;
+    if (threadIdx.x == 0) s_rec.p = -1;
+    __syncthreads();
+    int p = blockIdx.x;
+    for (int it = 0; p < v.P; ++it) {
+        // The particle's code reads the kernel's arguments through a pointer the compiler cannot see through: whatever it works out
+        // from them is worked out per particle, as in a kernel of its own.  (Known to be the same for every particle it was kept in
+        // registers across the whole loop: 79 of them spilled to scratch.)
+#if __HIP_DEVICE_COMPILE__
+        const __attribute__((address_space(4))) DevView* ka = (const __attribute__((address_space(4))) DevView*)__builtin_amdgcn_kernarg_segment_ptr();   // (EvKernArgs::v, offset 0)
+        asm volatile("" : "+s"(ka));
+        const DevView& vp = *(const DevView*)ka;
+#else
+        const DevView& vp = v;
+#endif
+        EV_TURN_IN(p);
+        map_update_ev_particle(vp, p, resident != 0, &s_next[it & 1], &s_rec);
+        EV_TURN_OUT(p);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // (BAR_LDS; the barrier-wait diagnostic redefines that for the particle's own)
+        p = UNI(s_next[it & 1]);
+    }
+    if (resident && threadIdx.x == 0 && atomicAdd(&v.ev_queue[1], 1u) == gridDim.x - 1u) { atomicExch(&v.ev_queue[0], 0u); atomicExch(&v.ev_queue[1], 0u); }
+}
+
+static int device_cu_count() {
+    static int cus[MAX_DEVICES] = {};
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < MAX_DEVICES && cus[dev] > 0) return cus[dev];
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) { (void)hipGetLastError(); n = 1; }
+    if (dev >= 0 && dev < MAX_DEVICES) cus[dev] = n;
+    return n;
+}
+
 // t0 / t1 (or nullptr): timing events that take the kernel's own start and end (hipExtLaunchKernelGGL: the dispatch carries
 // them, no event records - and their barriers - in the stream)
-void launch_map_update_ev(const DevView& v, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+// Returns the workgroups it launched.
+int launch_map_update_ev(const DevView& v, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     const EvGeom g = ev_geom(v.B, v.reach);
     static size_t lds_set[MAX_DEVICES] = {};
     ensure_dynamic_lds(reinterpret_cast<const void*>(map_update_ev_kernel), (size_t)g.bytes, lds_set);
-    if (t0 && t1) hipExtLaunchKernelGGL(map_update_ev_kernel, dim3(v.P), dim3(EB), (size_t)g.bytes, s, t0, t1, 0, v);
-    else hipLaunchKernelGGL(map_update_ev_kernel, dim3(v.P), dim3(EB), (size_t)g.bytes, s, v);
+    int grid = v.P;
+    if (v.ev_resident) {
+        grid = std::min(v.P, device_cu_count());
+        if (v.ev_grid > 0) grid = std::min(grid, v.ev_grid);
+    }
+    ev_turnover_begin(s);
+    const EvKernArgs args = {v, v.ev_resident};
+    if (t0 && t1) hipExtLaunchKernelGGL(map_update_ev_kernel, dim3(grid), dim3(EB), (size_t)g.bytes, s, t0, t1, 0, args);
+    else hipLaunchKernelGGL(map_update_ev_kernel, dim3(grid), dim3(EB), (size_t)g.bytes, s, args);
+    ev_turnover_end(v, grid, s);
+    return grid;
 }
 
 }  // namespace rbpf

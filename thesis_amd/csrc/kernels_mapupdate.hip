@@ -645,15 +645,17 @@ int map_update_first_kernel(const DevView& v) {
 }
 
 // t0 / t1 (or nullptr): timing events for the FIRST kernel's own start and end (ignored when there is none)
-void launch_map_update_fused(const DevView& v, const uint8_t* d_bad, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+int launch_map_update_fused(const DevView& v, const uint8_t* d_bad, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     size_t lds = raycast_lds_bytes(v.B, v.reach);
     static size_t lds_set[MAX_DEVICES] = {};   // more than the default 64 KiB of dynamic LDS
     ensure_dynamic_lds(reinterpret_cast<const void*>(map_update_kernel), lds, lds_set);
     // the chain: the first kernel leaves mu_fallback[p] != 0 for the particles it could not hold, the window kernel takes those
     const int first = map_update_first_kernel(v);
-    if (first == 1) launch_map_update_ev(v, s, t0, t1);
+    int ev_workgroups = 0;
+    if (first == 1) ev_workgroups = launch_map_update_ev(v, s, t0, t1);
     else if (first == 2) launch_map_update_ray(v, nullptr, s, t0, t1);
     hipLaunchKernelGGL(map_update_kernel, dim3(v.P), dim3(MU_BLOCK), lds, s, v, first ? (const int32_t*)v.mu_fallback : (const int32_t*)nullptr, d_bad);
+    return ev_workgroups;
 }
 
 }  // namespace rbpf

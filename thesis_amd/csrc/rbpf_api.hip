@@ -245,12 +245,18 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
         ALLOC(h, v.prop_samp, 256 * P);
         ALLOC(h, v.stats, ST_COUNT); ALLOC(h, v.err, 1);
         ALLOC(h, v.mu_fallback, P); HIP_TRY(h, hipMemset(v.mu_fallback, 0, P * 4));
+        ALLOC(h, v.ev_queue, 2); HIP_TRY(h, hipMemset(v.ev_queue, 0, 8));   // zeroed once: every launch leaves it zero (kernels_mapev.hip)
         ALLOC(h, h->d_did_early, 1);
         HIP_TRY(h, hipMemset(h->d_did_early, 0, 4));
         HIP_TRY(h, h->events.create(&h->ev_weights, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
         {   // RBPF_MAP_KERNEL=window keeps the 128x128-window map update for every particle, =ray / =ev run that first kernel (and
             // windows behind it); default: the event-walk kernel, windows for what it gives back (tests, comparisons)
             v.mu_mode = env_is("RBPF_MAP_KERNEL", "window") ? MU_WINDOW : env_is("RBPF_MAP_KERNEL", "ray") ? MU_RAY : env_is("RBPF_MAP_KERNEL", "ev") ? MU_EV : MU_DEFAULT;
+            // the event walk's workgroups stay resident and draw particles from a queue; RBPF_EV_RESIDENT=0: one workgroup per
+            // particle (A/B runs, tests), RBPF_EV_GRID=n: at most n resident workgroups (tests: several particles in a row)
+            v.ev_resident = env_is("RBPF_EV_RESIDENT", "0") ? 0 : 1;
+            const char* eg = getenv("RBPF_EV_GRID");
+            v.ev_grid = eg ? std::max(0, atoi(eg)) : 0;
             v.match_stage_slow = env_is("RBPF_MATCH_STAGE", "slow") ? 1 : 0;    // the matcher's field is staged bit by bit (tests)
             const char* ws = getenv("RBPF_WSAFE");          // test knob: the weighting's guard band in cells (0 shows what the band is for)
             v.wsafe_override = ws ? (float)atof(ws) : -1.0f;
@@ -538,10 +544,10 @@ static int run_map_update(rbpf_handle* h, const uint8_t* d_bad = nullptr) {
     // The map update's timing events ride on the first kernel's dispatch (its own start and end: the dominant kernel, without
     // the follow-up launch that usually finds nothing to do) - two event records and their barriers less in the stream per step.
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (map_update_first_kernel(v) != 0 && h->prof_take(0, t0, t1)) launch_map_update_fused(v, d_bad, h->stream, t0, t1);
+    if (map_update_first_kernel(v) != 0 && h->prof_take(0, t0, t1)) h->ev_workgroups = launch_map_update_fused(v, d_bad, h->stream, t0, t1);
     else {
         h->prof_begin(0);
-        launch_map_update_fused(v, d_bad, h->stream);
+        h->ev_workgroups = launch_map_update_fused(v, d_bad, h->stream);
         h->prof_end(0);
     }
     HIP_TRY(h, hipGetLastError());
@@ -703,6 +709,12 @@ int rbpf_get_proposal(rbpf_handle* h, int32_t particle, double* frame24, double*
 int rbpf_set_map_updates(rbpf_handle* h, int32_t on) {
     if (!h) return RBPF_EINVAL;
     h->map_updates = on != 0;
+    return RBPF_OK;
+}
+
+int rbpf_get_map_update_workgroups(rbpf_handle* h, int32_t* n) {
+    if (!h || !n) return RBPF_EINVAL;
+    *n = h->ev_workgroups;
     return RBPF_OK;
 }
 

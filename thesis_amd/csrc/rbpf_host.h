@@ -157,6 +157,7 @@ struct rbpf_handle {
     int match_rows = 0;                        // d_match: 0 not written by the built-in matcher, 1 its rows, 2 its rows with duplicates skipped (dup_of)
     double* d_match = nullptr; uint8_t* d_bad = nullptr; double* d_guess_full = nullptr;
     unsigned long long resample_draws = 0;
+    int ev_workgroups = 0;                                    // workgroups of the event-walk kernel in the last map update (0: it did not run); rbpf_get_map_update_workgroups
     bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)

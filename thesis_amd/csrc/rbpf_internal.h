@@ -82,6 +82,8 @@ struct DevView {
     double*  prop_samp;                // [P][256] its K samples: cos, sin, pose, motion probability, single-precision frame
     int32_t* mu_fallback;              // [P] != 0: the map-update kernel that ran first gave the particle back to the next one
     MapKernelMode mu_mode;             // which map-update kernels run (RBPF_MAP_KERNEL)
+    uint32_t* ev_queue;                // [2] the event-walk kernel's particle queue: draws of this launch, workgroups that have left; zero between launches (the kernel re-arms it)
+    int ev_resident, ev_grid;          // 1: resident workgroups draw particles from ev_queue (0, RBPF_EV_RESIDENT=0: one workgroup per particle); > 0: cap on their number (RBPF_EV_GRID, tests)
     uint32_t* ndt_occ; double* ndt_aux; // NDT stage: the matcher's staged field per particle, its grid optimum (kernels_match.hip)
     int ndt_refine;                    // rbpf_config.ndt_refine: NDT stage of matchScanCustom.m:32-50 (0 off, 1 reference rule, 2 always)
     int32_t* dup_of; int dups_valid;    // representative of each particle's group of exact duplicates since the last resample (kernels_resample.hip); valid until the next proposal
@@ -344,14 +346,14 @@ void launch_weight_samples(const DevView& v, const double* d_guesses, const doub
                            double* d_out_w, hipStream_t s);
 void launch_weight_samples_product(const DevView& v, const double* d_guesses, const double* d_prs, int K, double* d_out_w, hipStream_t s);
 int map_update_first_kernel(const DevView& v);   // 0 none, 1 event walk, 2 global-index kernel
-void launch_map_update_fused(const DevView& v, const uint8_t* d_bad, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);   // picks the kernel(s) below; d_bad: NaN-branch weight increments after the update (or nullptr)
+int launch_map_update_fused(const DevView& v, const uint8_t* d_bad, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);   // returns the event walk's workgroups (0: it did not run); picks the kernel(s) below; d_bad: NaN-branch weight increments after the update (or nullptr)
 void launch_ingest(const void* mapped_src, void* d_dst, size_t bytes, hipStream_t s);   // bytes rounded up to 16
 void launch_ingest2(const int32_t* mapped_a, int32_t* d_a, const int32_t* mapped_b, int32_t* d_b, int n, hipStream_t s);
 void launch_readback(void* mapped_dst, const double* d_nan_elem, const int32_t* d_did, const int32_t* d_idx, int n, hipStream_t s);
 bool map_update_ray_available(const DevView& v);
 void launch_map_update_ray(const DevView& v, const int32_t* only, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 bool map_update_ev_available(const DevView& v);
-void launch_map_update_ev(const DevView& v, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+int launch_map_update_ev(const DevView& v, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);   // returns the workgroups launched
 void launch_get_odds(const DevView& v, int particle, const double* d_xy, int n, double* d_vals,
                      uint8_t* d_none, hipStream_t s);
 void launch_last_scan(const DevView& v, int particle, double* d_out_xy, hipStream_t s);

@@ -207,6 +207,11 @@ __device__ __forceinline__ bool lut_covers(const DevView& v, int x0, int y0, int
 // the caller's next barrier); the start cell (hybridmap.py:102); the home tile and LUT test (false: nothing to do, uniform);
 // the index map over everything a ray can reach, with a margin of two columns (the sources of a storage cell are its own
 // global index and the next one): ux[i] / uy[i] = U of global index x0 - reach - 2 + i / y0 - reach - 2 + i.
+// fan_preamble_from: the same for a caller that has the heading's sine and cosine already (kernels_mapev.hip: a record of the
+// particle's pose, sine, cosine and tile row is made while the particle before it is written back); tab may lie in LDS.
+template <int NT>
+__device__ __forceinline__ bool fan_preamble_from(const DevView& v, const int32_t* tab, int p, int tid, double px, double py, int lut_margin,
+                                                  int fanw, uint16_t* ux, uint16_t* uy, int& x0, int& y0);
 template <int NT>
 __device__ __forceinline__ bool fan_preamble(const DevView& v, const int32_t* tab, int p, int tid, double px, double py, int lut_margin,
                                              int fanw, double* s_sincos, uint16_t* ux, uint16_t* uy, int& x0, int& y0) {
@@ -215,6 +220,11 @@ __device__ __forceinline__ bool fan_preamble(const DevView& v, const int32_t* ta
         sincos(v.upd_pose[2 * v.P + p], &sn, &cs_);
         if (tid == 0) { s_sincos[0] = sn; s_sincos[1] = cs_; }
     }
+    return fan_preamble_from<NT>(v, tab, p, tid, px, py, lut_margin, fanw, ux, uy, x0, y0);
+}
+template <int NT>
+__device__ __forceinline__ bool fan_preamble_from(const DevView& v, const int32_t* tab, int p, int tid, double px, double py, int lut_margin,
+                                                  int fanw, uint16_t* ux, uint16_t* uy, int& x0, int& y0) {
     x0 = UNI(trunc_to_int(px / v.cs)); y0 = UNI(trunc_to_int(py / v.cs));
     bool ok = home_tile_ok(v, tab, px, py);
     if (ok && !lut_covers(v, x0, y0, lut_margin)) { if (tid == 0) atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }

@@ -552,6 +552,12 @@ class ParticleEngine:
         self._check(self._lib.rbpf_get_map_updates(self._h, C.byref(on)))
         return bool(on.value)
 
+    def map_update_workgroups(self) -> int:
+        """Workgroups the event-walk map kernel was launched with in the last map update (0: it did not run)."""
+        n = C.c_int32()
+        self._check(self._lib.rbpf_get_map_update_workgroups(self._h, C.byref(n)))
+        return int(n.value)
+
     @map_updates.setter
     def map_updates(self, on: bool):
         self._check(self._lib.rbpf_set_map_updates(self._h, int(bool(on))))
