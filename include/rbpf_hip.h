@@ -783,6 +783,45 @@ int  rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, c
                       double min_range, double max_range, int32_t substeps, int32_t n_trans, int32_t n_rot, double rot_step,
                       double* out_pose_m3, int32_t* out_m8, int32_t* scores, uint32_t flags);
 
+/* ---- places by appearance: which earlier scan looks like this one, and how is it turned? ----------------------------------------
+ * rbpf_describe_scans turns n_scans scans (ranges [n_scans][n_beams], angles [n_beams], as rbpf_refine_poses) into descriptors:
+ * polar occupancy images in the sensor frame of R = n_rings rings (1 <= R <= RBPF_PLACES_MAX_RINGS) and 64 sectors of 5.625
+ * degrees, one 64-bit word a ring, bit j of the word sector j.
+ * Beams: a beam is used iff min_range < r < max_range (NaN, +-inf, 0 and negative ranges are data and are not used).
+ * Sector (host, float64, every * and / rounded on its own, once per call): sector[b] = ((int64)floor(angles[b] * (32.0 / M_PI)))
+ * & 63; any finite angle is accepted.  Ring: min((int)floor(r * rings_per_m), R - 1) with rings_per_m = (double)R / max_range, one
+ * host division.  Bit sector of desc[n][ring] is set iff some used beam of scan n lands there.
+ * Outputs: desc [n_scans][R]; info_n2[n] = {n_used, n_bits}, n_bits the popcount over the R words.  Either may be NULL, not both.
+ * A NULL ranges or angles, both outputs NULL, n_scans < 1, n_beams < 1 or > 16384, n_scans * n_beams >= 2^31, R out of range, a
+ * non-finite angle, min_range < 0 or not finite, max_range <= 0 or not finite, or an unknown flag is RBPF_EINVAL; a call between
+ * rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked before anything is queued, and nothing is written.  More than
+ * 4 GiB of scratch (8 bytes per range, 4 per beam, the host outputs) is RBPF_ENOMEM.  No engine state changes.
+ *
+ * rbpf_match_places compares two descriptor tables, query_desc [n_queries][R] and ref_desc [n_refs][R] (they may be the same).
+ * Field of a reference with words D: D'[g] = OR over g' in {g - 1, g, g + 1} within [0, R) of (D[g'] | rotl(D[g'], 1) |
+ * rotr(D[g'], 1)), the 3 x 3 dilation with circular sectors and clipped rings; w_r = popcount(D) + popcount(D').
+ * Score of query q (words Q) against reference r turned by s sectors, s in 0 .. 63, rotl moving bit j to bit (j + s) & 63:
+ *   score(q, r, s) = sum over g of popcount(Q[g] & rotl(D[g], s)) + popcount(Q[g] & rotl(D'[g], s))   <= min(2 n_bits_q, w_r) <= 4096
+ * Best turn of a pair: the s of maximal score; ties go to the smaller min(s, 64 - s), then to the smaller s; v_r is that score.
+ * The query's heading is the reference's minus s sectors.
+ * Eligible: r < ref_limit[q] (NULL: every reference; an entry outside 0 .. n_refs is RBPF_EINVAL), w_r > 0 and v_r > 0.
+ * Rank per query: a is better than b iff v_a^2 * w_b > v_b^2 * w_a in uint64 (both sides below 2^37), ties to the smaller r:
+ * v^2 / w, a cosine-like similarity, without a division.
+ * Outputs: the k best, 1 <= k <= RBPF_PLACES_MAX_K: out_qk4[q][j] = {r, s, v_r, w_r} best first, unused slots {-1, 0, 0, 0};
+ * out_q2[q] = {n_bits_q, slots filled}.  Either may be NULL, not both.
+ * NULL tables, both outputs NULL, n_queries or n_refs < 1, n_queries * k >= 2^31, R or k out of range, a bad ref_limit entry or an
+ * unknown flag is RBPF_EINVAL; RBPF_ESTATE and RBPF_ENOMEM (8 bytes per word of a host table and per word of the reference table, 16
+ * k per query and chunk of references) as above.  ref_limit is a host array.  The environment variable RBPF_PLACES_CHUNK sets the
+ * references per chunk (default 256); the result does not depend on it.  DESIGN.md 3.19 has the kernels. */
+#define RBPF_PLACES_MAX_RINGS 32
+#define RBPF_PLACES_MAX_K 16
+#define RBPF_PLACES_DEVICE_OUT 1u   /* the outputs are device pointers, written in stream order, no host wait */
+#define RBPF_PLACES_DEVICE_IN 2u    /* rbpf_match_places: both descriptor tables are device pointers, read in stream order */
+int  rbpf_describe_scans(rbpf_handle* h, const double* ranges, int32_t n_scans, const double* angles, int32_t n_beams,
+                         double min_range, double max_range, int32_t n_rings, uint64_t* desc, int32_t* info_n2, uint32_t flags);
+int  rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_queries, const uint64_t* ref_desc, int32_t n_refs,
+                       int32_t n_rings, const int32_t* ref_limit, int32_t k, int32_t* out_qk4, int32_t* out_q2, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2782,4 +2782,107 @@ int rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, co
     return RBPF_OK;
 }
 
+// ---- places by appearance (kernels_places.hip) -------------------------------------------------------------------
+int rbpf_describe_scans(rbpf_handle* h, const double* ranges, int32_t n_scans, const double* angles, int32_t n_beams,
+                        double min_range, double max_range, int32_t n_rings, uint64_t* desc, int32_t* info_n2, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!ranges || !angles) return fail(h, RBPF_EINVAL, "ranges or angles is NULL");
+    if (!desc && !info_n2) return fail(h, RBPF_EINVAL, "desc and info_n2 are both NULL");
+    if (flags & ~RBPF_PLACES_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_scans < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
+        return fail(h, RBPF_EINVAL, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
+    if (n_rings < 1 || n_rings > RBPF_PLACES_MAX_RINGS) return fail(h, RBPF_EINVAL, "1 <= n_rings <= 32 is required");
+    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
+    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
+    for (int b = 0; b < n_beams; ++b)
+        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "scan description between rbpf_scan_update_begin and rbpf_scan_update_end");
+    const bool dev_out = (flags & RBPF_PLACES_DEVICE_OUT) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [sectors] [ranges] | host outputs
+    const size_t N = (size_t)n_scans, R = (size_t)n_rings, nray = N * n_beams;
+    const size_t range_at = pad((size_t)n_beams * 4), in_b = range_at + nray * 8;
+    const size_t desc_b = !dev_out && desc ? pad(N * R * 8) : 0, info_b = !dev_out && info_n2 ? pad(N * 8) : 0;
+    const size_t total = pad(in_b) + desc_b + info_b;
+    if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "the scans need more than 4 GiB: describe fewer scans per call");
+    HIP_TRY(h, h->reserve(B_PLACES, total));
+    const Block& d = h->buf[B_PLACES];
+    Staging& st = h->stage[S_PLACES];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    int32_t* ss = reinterpret_cast<int32_t*>(st.p);
+    const double per_rad = 32.0 / M_PI;
+    for (int b = 0; b < n_beams; ++b)                                      // host floating point: the device never sees an angle.  fmod is exact:
+        ss[b] = (int32_t)((long long)fmod(floor(angles[b] * per_rad), 64.0) & 63);   // ((int64)floor) & 63, also where the floor exceeds an int64
+    memcpy(st.p + range_at, ranges, nray * 8);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    size_t at = pad(in_b);
+    unsigned long long* o_desc = !desc ? nullptr : dev_out ? reinterpret_cast<unsigned long long*>(desc) : d.as<unsigned long long>(at);
+    at += desc_b;
+    int32_t* o_info = !info_n2 ? nullptr : dev_out ? info_n2 : d.as<int32_t>(at);
+    launch_describe_scans(d.as<const double>(range_at), d.as<const int32_t>(), n_scans, n_beams, n_rings, min_range, max_range,
+                          (double)n_rings / max_range, o_desc, o_info, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    if (desc) HIP_TRY(h, hipMemcpyAsync(desc, o_desc, N * R * 8, hipMemcpyDeviceToHost, h->stream));
+    if (info_n2) HIP_TRY(h, hipMemcpyAsync(info_n2, o_info, N * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
+int rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_queries, const uint64_t* ref_desc, int32_t n_refs,
+                      int32_t n_rings, const int32_t* ref_limit, int32_t k, int32_t* out_qk4, int32_t* out_q2, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!query_desc || !ref_desc) return fail(h, RBPF_EINVAL, "query_desc or ref_desc is NULL");
+    if (!out_qk4 && !out_q2) return fail(h, RBPF_EINVAL, "out_qk4 and out_q2 are both NULL");
+    if (flags & ~(RBPF_PLACES_DEVICE_OUT | RBPF_PLACES_DEVICE_IN)) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_queries < 1 || n_refs < 1) return fail(h, RBPF_EINVAL, "n_queries >= 1 and n_refs >= 1 are required");
+    if (n_rings < 1 || n_rings > RBPF_PLACES_MAX_RINGS) return fail(h, RBPF_EINVAL, "1 <= n_rings <= 32 is required");
+    if (k < 1 || k > RBPF_PLACES_MAX_K) return fail(h, RBPF_EINVAL, "1 <= k <= 16 is required");
+    if ((long long)n_queries * k >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_queries * k < 2^31 is required");
+    for (int q = 0; ref_limit && q < n_queries; ++q)
+        if (ref_limit[q] < 0 || ref_limit[q] > n_refs) return fail(h, RBPF_EINVAL, "0 <= ref_limit[q] <= n_refs is required");
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "place search between rbpf_scan_update_begin and rbpf_scan_update_end");
+    PlacesArgs a;
+    a.nq = n_queries; a.nr = n_refs; a.R = n_rings; a.k = k;
+    a.chunk = std::min(256, n_refs);
+    if (const char* e = getenv("RBPF_PLACES_CHUNK")) a.chunk = std::max(1, std::min(n_refs, atoi(e)));   // for tests
+    a.nch = (n_refs + a.chunk - 1) / a.chunk;
+    const bool dev_out = (flags & RBPF_PLACES_DEVICE_OUT) != 0, dev_in = (flags & RBPF_PLACES_DEVICE_IN) != 0;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [limits] [host query table] [host reference table] | [dilated references] [weights] [chunk lists] | host outputs
+    const size_t Q = (size_t)n_queries, N = (size_t)n_refs, R = (size_t)n_rings;
+    const size_t qd_at = pad(Q * 4), rd_at = qd_at + (dev_in ? 0 : pad(Q * R * 8)), in_b = rd_at + (dev_in ? 0 : pad(N * R * 8));
+    const size_t dil_b = pad(N * R * 8), w_b = pad(N * 4), part_b = pad(Q * a.nch * k * 16);
+    const size_t qk4_b = !dev_out && out_qk4 ? pad(Q * k * 16) : 0, q2_b = !dev_out && out_q2 ? pad(Q * 8) : 0;
+    const size_t total = in_b + dil_b + w_b + part_b + qk4_b + q2_b;
+    if (total > ((size_t)4 << 30) || (Q + 3) / 4 * a.nch >= ((size_t)1 << 31))
+        return fail(h, RBPF_ENOMEM, "tables and chunk lists need more than 4 GiB: match fewer queries per call");
+    HIP_TRY(h, h->reserve(B_PLACES, total));
+    const Block& d = h->buf[B_PLACES];
+    Staging& st = h->stage[S_PLACES];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    int32_t* sl = reinterpret_cast<int32_t*>(st.p);
+    for (size_t q = 0; q < Q; ++q) sl[q] = ref_limit ? ref_limit[q] : n_refs;
+    if (!dev_in) { memcpy(st.p + qd_at, query_desc, Q * R * 8); memcpy(st.p + rd_at, ref_desc, N * R * 8); }
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    a.limit = d.as<const int32_t>();
+    a.qd = dev_in ? reinterpret_cast<const unsigned long long*>(query_desc) : d.as<const unsigned long long>(qd_at);
+    a.rd = dev_in ? reinterpret_cast<const unsigned long long*>(ref_desc) : d.as<const unsigned long long>(rd_at);
+    size_t at = in_b;
+    a.dil = d.as<unsigned long long>(at); at += dil_b;
+    a.w = d.as<int32_t>(at); at += w_b;
+    a.partial = d.as<int4>(at); at += part_b;
+    a.out_qk4 = !out_qk4 ? nullptr : dev_out ? out_qk4 : d.as<int32_t>(at); at += qk4_b;
+    a.out_q2 = !out_q2 ? nullptr : dev_out ? out_q2 : d.as<int32_t>(at);
+    launch_match_places(a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    if (out_qk4) HIP_TRY(h, hipMemcpyAsync(out_qk4, a.out_qk4, Q * k * 16, hipMemcpyDeviceToHost, h->stream));
+    if (out_q2) HIP_TRY(h, hipMemcpyAsync(out_q2, a.out_q2, Q * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

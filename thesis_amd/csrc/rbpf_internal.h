@@ -228,6 +228,19 @@ struct PairsArgs {
     int32_t* n_ref;                    // [M] used reference beams of the run
     double* out_pose; int32_t* out_m8; // [M][3], [M][8]; either may be null
 };
+// places by appearance (kernels_places.hip): nq query descriptors against nr reference descriptors of R ring words,
+// the k best references of every query.  References are cut into chunks of `chunk`; a (query, chunk) leaves a list in `partial`
+struct PlacesArgs {
+    int nq, nr, R, k;
+    int chunk, nch;                    // references per chunk, chunks = ceil(nr / chunk)
+    const unsigned long long* qd;      // [nq][R]
+    const unsigned long long* rd;      // [nr][R]
+    const int32_t* limit;              // [nq] query q admits the references r < limit[q], 0 <= limit[q] <= nr
+    unsigned long long* dil;           // [nr][R] D', written by the field kernel
+    int32_t* w;                        // [nr] popcount(D) + popcount(D')
+    int4* partial;                     // [nq][nch][k] {r, s, v, w} best first, {-1, 0, 0, 0} behind the last
+    int32_t *out_qk4, *out_q2;         // [nq][k][4], [nq][2]; either may be null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -406,6 +419,9 @@ size_t refine_lds_bytes(int Mw, int WW);
 void launch_refine_poses(const DevView& v, const LocateArgs& f, const RefineArgs& a, hipStream_t s);   // a.packed preset to 0
 size_t pairs_field_lds_bytes(int Mw, int WW);
 void launch_match_pairs(const PairsArgs& p, const RefineArgs& a, hipStream_t s);  // a.packed preset to 0; a.field unused
+void launch_describe_scans(const double* d_ranges, const int32_t* d_sector, int n_scans, int n_beams, int n_rings, double min_range,
+                           double max_range, double rings_per_m, unsigned long long* d_desc, int32_t* d_info, hipStream_t s);   // either output may be null
+void launch_match_places(const PlacesArgs& a, hipStream_t s);                    // field, search and merge
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

@@ -77,6 +77,33 @@ class PairResult(NamedTuple):
     cell_size: float     # metres: a translation step is cell_size / substeps
 
 
+class ScanDescriptors(NamedTuple):
+    """ParticleEngine.describe_scans: per scan [N] (numpy arrays, or torch tensors on the GPU)."""
+    desc: Any            # [N, R]: ring g of scan n, bit j = sector j.  numpy uint64; on the GPU int64 with the same bits
+    n_used: Any          # int32 [N]: beams with min_range < range < max_range
+    n_bits: Any          # int32 [N]: the popcount over the R words
+
+
+class PlaceMatches(NamedTuple):
+    """ParticleEngine.match_places: per query [Q], its k best references best first (numpy arrays, or torch tensors on the GPU);
+    thesis_amd/loops.py reads them."""
+    ref: Any             # int32 [Q, k]: the reference, -1 in an unused slot
+    shift: Any           # int32 [Q, k]: its best turn s in 0 .. 63: the query's heading is the reference's minus s sectors
+    score: Any           # int32 [Q, k]: v, the score at that turn
+    weight: Any          # int32 [Q, k]: w = popcount(D) + popcount(D') of the reference
+    n_bits: Any          # int32 [Q]: the popcount of the query
+    count: Any           # int32 [Q]: slots filled
+
+    def similarity(self):
+        """score / sqrt(2 n_bits weight) in [0, 1] (score <= min(2 n_bits, weight)), 0 in an unused slot; float64 [Q, k]."""
+        if hasattr(self.score, "data_ptr"):
+            import torch
+            den = torch.sqrt(2.0 * self.n_bits.double()[:, None] * self.weight.double())
+            return torch.where(den > 0, self.score.double() / den.clamp(min=1.0), torch.zeros_like(den))
+        den = np.sqrt(2.0 * np.asarray(self.n_bits, dtype=np.float64)[:, None] * np.asarray(self.weight, dtype=np.float64))
+        return np.where(den > 0, np.asarray(self.score, dtype=np.float64) / np.maximum(den, 1.0), 0.0)
+
+
 class Proposal(NamedTuple):
     """ParticleEngine.proposal: one particle's proposal frame and its K samples."""
     U: np.ndarray          # [3, 3] pseudo-inverse square root of the matcher covariance: maha = |(g - mean) U|^2
@@ -1431,6 +1458,109 @@ class ParticleEngine:
         inv = self.dim / float(self.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
         most = reach / inv
         return float(np.nextafter(most, 0.0)) if np.ceil(most * inv) > reach else most
+
+    # -- places by appearance (include/rbpf_hip.h: rbpf_describe_scans, rbpf_match_places; thesis_amd/loops.py) ---
+    def _torch_stream(self):
+        """(torch, device, torch's current stream there, whether the engine runs on that very stream)."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        cur = torch.cuda.current_stream(dev)
+        return torch, dev, cur, self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+
+    def describe_scans(self, ranges, angles, rings: int = 24, min_range: Optional[float] = None, max_range: Optional[float] = None,
+                       device: bool = False) -> ScanDescriptors:
+        """What each scan looks like from where it was taken: `ranges` [N, B] (beam directions `angles` [B]) become polar
+        occupancy images of `rings` rings (1 .. 32) between 0 and max_range and 64 sectors of 5.625 degrees, one 64-bit word a
+        ring, bit j sector j, from the beams with min_range < range < max_range (defaults cfg.match_min_range,
+        cfg.match_max_range).  A [B] scan is N = 1.  match_places compares them.  device=True: torch tensors on the engine's
+        device, ready for work on torch's current stream, the words as int64 (torch has no arithmetic on uint64; the bits are
+        the same)."""
+        rg, a = _f64(ranges), _f64(angles)
+        if rg.ndim == 1:
+            rg = rg.reshape(1, -1)
+        if a.ndim != 1 or rg.ndim != 2 or rg.shape[1] != a.shape[0]:
+            raise ValueError("angles must be [B] and ranges [N, B]")
+        n, r = rg.shape[0], int(rings)
+        lo = float(self.cfg.match_min_range if min_range is None else min_range)
+        hi = float(self.cfg.match_max_range if max_range is None else max_range)
+        same_stream = False
+        if device:
+            torch, dev, cur, same_stream = self._torch_stream()
+            desc = torch.empty((n, max(r, 0)), dtype=torch.int64, device=dev)     # a bad ring count is the library's to refuse
+            info = torch.empty((n, 2), dtype=torch.int32, device=dev)
+            ptrs = [C.c_void_p(desc.data_ptr() or 1), C.c_void_p(info.data_ptr() or 1)]
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            desc, info = np.empty((n, max(r, 0)), dtype=np.uint64), np.empty((n, 2), dtype=np.int32)
+            ptrs = [C.c_void_p(desc.ctypes.data or 1), C.c_void_p(info.ctypes.data or 1)]
+        self._check(self._lib.rbpf_describe_scans(self._h, _dp(rg), n, _dp(a), a.shape[0], lo, hi, r, *ptrs,
+                                                  _lib.RBPF_PLACES_DEVICE_OUT if device else 0))
+        if device and not same_stream:
+            self.synchronize()
+        return ScanDescriptors(desc, info[:, 0], info[:, 1])
+
+    def match_places(self, queries, refs=None, ref_limit=None, k: int = 4, device: bool = False) -> PlaceMatches:
+        """Which references look like each query, and how they are turned: `queries` [Q, R] and `refs` [N, R] (None: the
+        queries themselves) are descriptors of describe_scans, each a uint64 array, the int64 tensor of a
+        describe_scans(device=True) or the ScanDescriptors itself, so a run's table never leaves the GPU.  Every query is
+        scored against every reference r < ref_limit[q] (int [Q], None: all) at all 64 turns: the score counts the query's
+        bits on the reference's bits and again on their 3 x 3 dilation.  Per query the `k` (1 .. 16) references of largest
+        score^2 / weight come back best first, ties to the smaller r, each with its best turn `shift`: the query's heading is
+        the reference's minus shift * 2 pi / 64.  device=True: torch tensors on the engine's device, ready for work on torch's
+        current stream."""
+        def table(t):
+            t = t.desc if isinstance(t, ScanDescriptors) else t
+            if hasattr(t, "data_ptr"):
+                import torch
+                if t.dtype != torch.int64 or t.dim() != 2 or t.device != torch.device("cuda", int(self.cfg.device)):
+                    raise ValueError("a descriptor tensor must be [N, R] int64 on the engine's device")
+                return t.contiguous()
+            t = np.asarray(t)
+            if t.ndim == 1:
+                t = t.reshape(1, -1)
+            if t.ndim != 2 or t.dtype.kind not in "iu" or t.dtype.itemsize != 8:
+                raise ValueError("descriptors must be [N, R] uint64")
+            return np.ascontiguousarray(t).view(np.uint64)
+        qd = table(queries)
+        rd = qd if refs is None else table(refs)
+        if qd.shape[1] != rd.shape[1]:
+            raise ValueError(f"queries have {qd.shape[1]} rings, references {rd.shape[1]}")
+        nq, nr, k = int(qd.shape[0]), int(rd.shape[0]), int(k)
+        lim = None
+        if ref_limit is not None:
+            lim = np.ascontiguousarray(ref_limit, dtype=np.int32)
+            if lim.shape != (nq,):
+                raise ValueError("ref_limit must be [Q]")
+        dev_in = hasattr(qd, "data_ptr") or hasattr(rd, "data_ptr")
+        flags, same_stream, cur = 0, False, None
+        if dev_in or device:
+            torch, dev, cur, same_stream = self._torch_stream()
+        if dev_in:
+            up = lambda t: t if hasattr(t, "data_ptr") else torch.from_numpy(t.view(np.int64)).to(dev)
+            qd, rd = up(qd), (up(rd) if rd is not qd else None)
+            rd = qd if rd is None else rd
+            flags |= _lib.RBPF_PLACES_DEVICE_IN
+            tabs = [C.c_void_p(qd.data_ptr() or 1), C.c_void_p(rd.data_ptr() or 1)]
+        else:
+            tabs = [C.c_void_p(qd.ctypes.data or 1), C.c_void_p(rd.ctypes.data or 1)]
+        kk = min(max(k, 0), _lib.RBPF_PLACES_MAX_K)          # a bad k is the library's to refuse
+        if device:
+            qk4 = torch.empty((nq, kk, 4), dtype=torch.int32, device=dev)
+            q2 = torch.empty((nq, 2), dtype=torch.int32, device=dev)
+            outs = [C.c_void_p(qk4.data_ptr() or 1), C.c_void_p(q2.data_ptr() or 1)]
+            flags |= _lib.RBPF_PLACES_DEVICE_OUT
+        else:
+            qk4, q2 = np.empty((nq, kk, 4), dtype=np.int32), np.empty((nq, 2), dtype=np.int32)
+            outs = [C.c_void_p(qk4.ctypes.data or 1), C.c_void_p(q2.ctypes.data or 1)]
+        if cur is not None and not same_stream:
+            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
+        self._check(self._lib.rbpf_match_places(self._h, tabs[0], nq, tabs[1], nr, int(qd.shape[1]), None if lim is None else _ip(lim), k,
+                                                *outs, flags))
+        if device and not same_stream:
+            self.synchronize()
+        del qd, rd                                       # kept alive until the call returned
+        return PlaceMatches(qk4[..., 0], qk4[..., 1], qk4[..., 2], qk4[..., 3], q2[:, 0], q2[:, 1])
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)

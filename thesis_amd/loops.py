@@ -9,8 +9,14 @@ the drift (candidates, match), the matches become constraints between poses, and
     polished = refine.refine_trajectory(pf.engine, pf.scans, angles, poses=closed.poses)
     raster = rebuild.as_raster(polished.built, engine=pf.engine)
 
-Candidates come from the poses, not from appearance: a loop whose drift exceeds `radius` plus the search window is not found.
-Everything here is host NumPy and SciPy; the search runs on the GPU.
+By default candidates come from the poses, not from appearance: a loop whose drift exceeds `radius` plus the search window is
+not found that way.  candidates="appearance" asks the scans instead (candidates_by_appearance; ParticleEngine.describe_scans and
+match_places): every scan becomes a polar occupancy image, the earlier scan that looks most like the query,
+and the turn at which it does, give the pair and its guess, whatever the drift:
+
+    closed = loops.close_loops(pf.engine, pf.scans, angles, min_gap=200, candidates="appearance")
+
+Everything here is host NumPy and SciPy; the searches run on the GPU.
 """
 from __future__ import annotations
 
@@ -71,6 +77,50 @@ def candidates(poses, min_gap: int, radius: float, half_run: int = 5, stride: in
     return np.array(out, dtype=np.int32).reshape(-1, 3)
 
 
+def candidates_by_appearance(engine, poses, ranges, angles, min_gap: int, half_run: int = 5, stride: int = 1, ref_stride: int = 1,
+                             per_query: int = 1, rings: int = 24, min_similarity: float = 0.0, min_range: Optional[float] = None,
+                             max_range: Optional[float] = None):
+    """Pairs for match_pairs from what the scans look like, wherever their poses are: (pairs {q, r0, r1} int32 [M, 3], guesses
+    [M, 3], similarity [M]).  engine.describe_scans describes every scan (`rings`, `min_range`, `max_range`), engine.match_places
+    compares every `stride`-th scan q with every `ref_stride`-th scan r, r + half_run < q - min_gap as in candidates().  Of its
+    min(16, 4 per_query) best references a query keeps up to `per_query`, in rank order: one is kept if its similarity reaches
+    `min_similarity` and it lies more than half_run scans from every one kept before.  Each gives the run max(r - half_run, 0)
+    .. r + half_run and the guess (x_r, y_r, wrap(theta_r - shift * 2 pi / 64)): the query on the reference, turned as the
+    descriptors say.  min_similarity is a prefilter that saves search work; match()'s acceptance rule is the verifier."""
+    p = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    if min_gap < 0 or half_run < 0 or stride < 1 or ref_stride < 1 or per_query < 1:
+        raise ValueError("min_gap >= 0, half_run >= 0, stride >= 1, ref_stride >= 1 and per_query >= 1 are required")
+    none = np.zeros((0, 3), np.int32), np.zeros((0, 3)), np.zeros(0)
+    n = len(p)
+    qs = np.arange(0, n, int(stride))
+    rs = np.arange(0, n, int(ref_stride))
+    # references r < q - min_gap - half_run: the first of rs that is not, per query
+    limit = np.searchsorted(rs, qs - int(min_gap) - int(half_run), side="left").astype(np.int32)
+    some = limit > 0
+    if not some.any():
+        return none
+    qs, limit = qs[some], limit[some]
+    desc = engine.describe_scans(ranges, angles, rings=rings, min_range=min_range, max_range=max_range).desc
+    found = engine.match_places(desc[qs], desc[rs[:int(limit.max())]], ref_limit=limit, k=min(16, 4 * int(per_query)))
+    sim = found.similarity()
+    pairs, guesses, sims = [], [], []
+    for m, q in enumerate(qs):
+        kept = []
+        for j in range(int(found.count[m])):
+            r = int(rs[found.ref[m, j]])
+            if len(kept) == int(per_query):
+                break
+            if sim[m, j] < min_similarity or any(abs(r - o) <= int(half_run) for o in kept):
+                continue
+            kept.append(r)
+            pairs.append((int(q), max(r - int(half_run), 0), r + int(half_run) + 1))
+            guesses.append((p[r, 0], p[r, 1], float(_wrap(p[r, 2] - int(found.shift[m, j]) * (2.0 * math.pi / 64.0)))))
+            sims.append(float(sim[m, j]))
+    if not pairs:
+        return none
+    return np.array(pairs, dtype=np.int32).reshape(-1, 3), np.array(guesses, dtype=np.float64).reshape(-1, 3), np.array(sims)
+
+
 def pairs_per_call(engine, n_scans: int, n_beams: int, cell_size=None, substeps: int = 1, window: int = 16, rotations: int = 20,
                    max_range=None, limit: Optional[int] = None, **_) -> int:
     """How many pairs one match_pairs call takes within `limit` bytes of scratch (default SCRATCH_BYTES; include/rbpf_hip.h
@@ -85,24 +135,30 @@ def pairs_per_call(engine, n_scans: int, n_beams: int, cell_size=None, substeps:
     return max(1, (int(SCRATCH_BYTES if limit is None else limit) - fixed) // per_pair)
 
 
-def match(engine, poses, ranges, angles, pairs, accept: float = 0.55, gain: float = 0.1, min_used: int = 30, **search) -> LoopEdges:
-    """match_pairs on `pairs` (from candidates) with the scans' current poses as guesses, in as many calls as the scratch limit
-    asks for.  Edge m says where scan q sits in the frame of poses[r], r = (r0 + r1) // 2 the middle of the run.  It is
-    accepted if its fraction score / (2 n_used) reaches `accept` with at least `min_used` beams, and the search either raised
-    the guess's fraction by `gain` or kept the guess: a match that moved the pose for nothing is noise.  `search` goes to
+def match(engine, poses, ranges, angles, pairs, accept: float = 0.55, gain: float = 0.1, min_used: int = 30, guesses=None,
+          **search) -> LoopEdges:
+    """match_pairs on `pairs` (from candidates) with the scans' current poses as guesses, or with `guesses` [M, 3] (from
+    candidates_by_appearance; fraction_guess is then the appearance guess's), in as many calls as the scratch limit asks for.
+    Edge m says where scan q sits in the frame of poses[r], r = (r0 + r1) // 2 the middle of the run.  It is accepted if its
+    fraction score / (2 n_used) reaches `accept` with at least `min_used` beams, and the search either raised the guess's
+    fraction by `gain` or kept the guess: a match that moved the pose for nothing is noise.  `search` goes to
     ParticleEngine.match_pairs (cell_size, substeps, window, rotations, rot_step, min_range, max_range)."""
-    for bad in ("return_scores", "device", "guesses"):
+    for bad in ("return_scores", "device"):
         if bad in search:
-            raise ValueError(f"match() reads every result on the host and guesses from the poses: {bad} is not for it")
+            raise ValueError(f"match() reads every result on the host: {bad} is not for it")
     poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
     ranges = np.ascontiguousarray(ranges, dtype=np.float64).reshape(len(poses), -1)
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 3)
     M = len(pairs)
+    if guesses is not None:
+        guesses = np.ascontiguousarray(guesses, dtype=np.float64).reshape(-1, 3)
+        if len(guesses) != M:
+            raise ValueError(f"{len(guesses)} guesses for {M} pairs")
     q, r = pairs[:, 0].copy(), ((pairs[:, 1] + pairs[:, 2]) // 2).astype(np.int32)
     out, index, score, guess, used = np.empty((M, 3)), np.empty((M, 3), np.int32), np.empty(M, np.int64), np.empty(M, np.int64), np.empty(M, np.int64)
     step = pairs_per_call(engine, len(poses), ranges.shape[1], **search)
     for k in range(0, M, step):
-        res = engine.match_pairs(poses, ranges, angles, pairs[k:k + step], **search)
+        res = engine.match_pairs(poses, ranges, angles, pairs[k:k + step], None if guesses is None else guesses[k:k + step], **search)
         out[k:k + step], index[k:k + step] = res.poses, res.index
         score[k:k + step], guess[k:k + step], used[k:k + step] = res.score, res.score_guess, res.n_used
     some = used > 0
@@ -164,16 +220,23 @@ def relax(poses, edges_ij, z, sigma_t, sigma_th, iterations: int = 20, tol: floa
 
 
 def close_loops(engine, log, angles, particle="best", rounds: int = 1, odo_sigma=(0.02, 0.005), loop_sigma=(0.05, 0.01),
-                cell_size: Optional[float] = None, build_args: Optional[dict] = None, poses=None, **search) -> ClosedTrajectory:
+                cell_size: Optional[float] = None, build_args: Optional[dict] = None, poses=None, candidates: str = "pose",
+                **search) -> ClosedTrajectory:
     """Closes the loops of a logged run.  refine.scan_poses picks the scans and the poses of `particle`'s trajectory (`poses`
     [n, 3] replaces them).  Each round: odometry edges between consecutive scans hold the current poses' own relative poses
     (sigmas `odo_sigma` = (metres, radians) per edge), candidates() proposes pairs, match() turns the accepted ones into loop
     edges (`loop_sigma`), relax() spreads them.  Then rebuild.rebuild_at draws the map at the new poses (`build_args`:
     min_range, max_range, box, device).  `search` holds candidates' min_gap (default 50), radius (2 m), half_run, stride and
     per_query, match's accept, gain and min_used, and match_pairs' search arguments.  With no accepted edge the poses come
-    back as they went in, bit for bit."""
+    back as they went in, bit for bit.  `candidates`: "pose" proposes pairs from the poses as above; "appearance" from what the
+    scans look like (candidates_by_appearance, which also takes ref_stride, rings and min_similarity from `search`, the ranges
+    of the search, and ignores radius), each pair with its own guess; "both" the pose pairs and then the appearance pairs
+    whose (q, middle r) no pose pair has."""
     if rounds < 1:
         raise ValueError("rounds must be at least 1")
+    if candidates not in ("pose", "appearance", "both"):
+        raise ValueError(f"unknown candidates {candidates!r}: pose, appearance or both")
+    propose = globals()["candidates"]                    # the argument hides the function of that name
     records, start, ranges = _refine.scan_poses(engine, log, particle)
     if poses is not None:
         start = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
@@ -182,6 +245,10 @@ def close_loops(engine, log, angles, particle="best", rounds: int = 1, odo_sigma
     search = dict(search)
     cand = {k: search.pop(k) for k in ("half_run", "stride", "per_query") if k in search}
     min_gap, radius = search.pop("min_gap", 50), search.pop("radius", 2.0)
+    look = {}
+    if candidates != "pose":
+        look = {k: search.pop(k) for k in ("ref_stride", "rings", "min_similarity") if k in search}
+        look.update({k: search[k] for k in ("min_range", "max_range") if k in search})
     if cell_size is not None:
         search["cell_size"] = cell_size
     cur = np.array(start, dtype=np.float64)
@@ -190,8 +257,19 @@ def close_loops(engine, log, angles, particle="best", rounds: int = 1, odo_sigma
     out: List[LoopRound] = []
     edges = None
     for _ in range(rounds):
-        pairs = candidates(cur, min_gap, radius, **cand)
-        edges = match(engine, cur, ranges, angles, pairs, **search)
+        pairs, guesses = None, None
+        if candidates != "appearance":
+            pairs = propose(cur, min_gap, radius, **cand)
+        if candidates != "pose":
+            seen, guesses, _ = candidates_by_appearance(engine, cur, ranges, angles, min_gap, **cand, **look)
+            if pairs is None:
+                pairs = seen
+            else:                                        # pose pairs first, at their own poses; then what only appearance found
+                have = {(int(q), (int(a) + int(b)) // 2) for q, a, b in pairs}
+                fresh = np.array([(int(q), (int(a) + int(b)) // 2) not in have for q, a, b in seen], dtype=bool)
+                guesses = np.concatenate([cur[pairs[:, 0]], guesses[fresh]])
+                pairs = np.concatenate([pairs, seen[fresh]])
+        edges = match(engine, cur, ranges, angles, pairs, guesses=guesses, **search)
         ok = edges.accepted
         if not ok.any():
             out.append(LoopRound(len(pairs), 0, 0.0))
