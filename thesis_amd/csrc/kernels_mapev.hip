@@ -638,9 +638,14 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
         // the next particle's record, as one more item of the write-back's queue: the wave that makes it joins the others a batch or so later
         if (S1 == S_hi && wave == EB / 64 - 1 && nxt_p < v.P) ev_prefetch(v, nxt_p, rec, lane);
         // ---- write-back (rbpf_mapupdate.h): the flagged cells get a value from their counts like all others; their real value
-        //      follows after the windows ----
-        strip_write_back<FIELD_COUNT_HI, true, true, false>(v, sg, S0, S1, gx_base, C, fxl, ggf_base, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
-                                                            &s_wbq, &s_written, sparse, lane);
+        //      follows after the windows.  A tile row of whole 32-cell groups under a fan that is not thin (both uniform over the
+        //      workgroup; 0.05 m cells: dim 800) takes the instantiation without the partial group's word tests and the thin fan's branch ----
+        if (v.dim % 32 == 0 && !sparse)
+            strip_write_back<FIELD_COUNT_HI, false, false, false>(v, sg, S0, S1, gx_base, C, fxl, ggf_base, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
+                                                                  &s_wbq, &s_written, false, lane);
+        else
+            strip_write_back<FIELD_COUNT_HI, true, true, false>(v, sg, S0, S1, gx_base, C, fxl, ggf_base, wbk, cnt, gxb, gym, s_ggf, s_tab, s_need,
+                                                                &s_wbq, &s_written, sparse, lane);
         STAMP(4);
     }
     BAR_LDS();                                                                // the window's LDS is free (the write-back's stores are still on their way)
