@@ -822,6 +822,36 @@ int  rbpf_describe_scans(rbpf_handle* h, const double* ranges, int32_t n_scans, 
 int  rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_queries, const uint64_t* ref_desc, int32_t n_refs,
                        int32_t n_rings, const int32_t* ref_limit, int32_t k, int32_t* out_qk4, int32_t* out_q2, uint32_t flags);
 
+/* ---- score surface: how sharp is a match, and is there another one? ------------------------------------------------------------
+ * Reduces n_items score volumes, int32 [n_items][nk][nw][nw] with nk = 2R+1, nw = 2W+1, R = n_rot in 0 .. 100 and W = n_trans in
+ * 0 .. 32, indexed [n][k+R][i+W][j+W] with values in 0 .. 32768: exactly what rbpf_refine_poses and rbpf_match_pairs write into
+ * `scores`.  Everything is exact integer arithmetic.
+ * Parameters: drop_n[n] in 0 .. 32768 per item (NULL: 0 for every item); ex_trans in 0 .. 64; ex_rot in 0 .. 200; K = n_peaks in
+ * 1 .. 8.
+ * Order: candidate c = (i, j, k) with score V(c) comes before another iff its V is larger, then its |k| smaller, then its
+ * i^2 + j^2 smaller, then its (k, i, j) lexicographically smaller: the tie order of rbpf_refine_poses.
+ * Peaks, greedy: free_0 is every candidate.  For p = 0, 1, .. < K while free_p is not empty: peak_p = (i_p, j_p, k_p) is the
+ * first candidate of free_p in that order, s_p its score; box_p = {c : |i - i_p| <= ex_trans, |j - j_p| <= ex_trans, |k - k_p| <=
+ * ex_rot}; free_{p+1} = free_p \ box_p.  out_count[n] is the number of peaks found, at least 1.  Peak 0 is the best candidate
+ * rbpf_refine_poses or rbpf_match_pairs reports for that volume.
+ * Plateau of peak p: T_p = {c in free_p and box_p : V(c) >= s_p - drop}; it always holds the peak.  Weight w(c) = V(c) -
+ * (s_p - drop) + 1 in 1 .. drop + 1; offsets d = (di, dj, dk) = (i - i_p, j - j_p, k - k_p).  All sums are exact int64: the
+ * largest, sum w dk^2 at R = 100, W = 32, drop = 32768 over a constant volume, stays below 1.2e18.
+ * Output record of peak p, out_nk16[n][p], int64 [16]: {i, j, k, s, |T|, sum w, sum w di, sum w dj, sum w dk, sum w di^2,
+ * sum w di dj, sum w di dk, sum w dj^2, sum w dj dk, sum w dk^2, 0}.  The records out_count[n] .. K - 1 are all zero.
+ * It reads no particle's map and changes no engine state; it runs on the handle's stream; host outputs are complete on return.
+ * A NULL scores or out_nk16 (out_count may be NULL), n_items < 1, a parameter out of the ranges above, n_items * nk * nw^2 >=
+ * 2^31, an unknown flag, a host drop_n value out of range or a host volume with a value outside 0 .. 32768 is RBPF_EINVAL; a call
+ * between rbpf_scan_update_begin and _end is RBPF_ESTATE; both are checked before anything is queued, and nothing is written.
+ * More than 4 GiB of scratch is RBPF_ENOMEM: a host volume is staged, 4 bytes per candidate and 4 per host drop, and host outputs
+ * take 128 K + 4 bytes per item.  A device volume (and a device drop_n) is not validated: no score is ever used as an index, so a
+ * value out of range can only give meaningless numbers, never an access outside the buffers.  DESIGN.md 3.20 has the kernel. */
+#define RBPF_SURFACE_DEVICE_IN  1u   /* scores and drop_n are device pointers */
+#define RBPF_SURFACE_DEVICE_OUT 2u   /* out_nk16 / out_count are device pointers, written in stream order, no host wait */
+int  rbpf_score_surface(rbpf_handle* h, const int32_t* scores, int32_t n_items, int32_t n_rot, int32_t n_trans,
+                        const int32_t* drop_n, int32_t ex_trans, int32_t ex_rot, int32_t n_peaks,
+                        int64_t* out_nk16, int32_t* out_count, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

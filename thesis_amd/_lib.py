@@ -29,6 +29,7 @@ RBPF_BUILD_DEVICE_OUT, RBPF_BUILD_ACCUMULATE = 1, 2
 RBPF_REFINE_DEVICE_OUT = 1
 RBPF_PAIRS_DEVICE_OUT = 1
 RBPF_PLACES_DEVICE_OUT, RBPF_PLACES_DEVICE_IN, RBPF_PLACES_MAX_RINGS, RBPF_PLACES_MAX_K = 1, 2, 32, 16
+RBPF_SURFACE_DEVICE_IN, RBPF_SURFACE_DEVICE_OUT = 1, 2
 RBPF_PLACE_DEVICE_IN, RBPF_PLACE_DEVICE_OUT, RBPF_PLACE_DRY = 1, 2, 4
 RBPF_PLACE_REPLACE, RBPF_PLACE_KNOWN, RBPF_PLACE_ADD = 0, 1, 2
 IMU_UNICYCLE, IMU_ABSOLUTE, IMU_VELOCITY = 0, 1, 2
@@ -165,6 +166,8 @@ PROTOTYPES = {
     "rbpf_describe_scans": (C.c_int, [_H, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rbpf_match_places": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _I, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_uint32]),
+    "rbpf_score_surface": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_uint32]),
 }
 
 _lib = None

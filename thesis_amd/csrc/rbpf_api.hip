@@ -2885,4 +2885,60 @@ int rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_quer
     return RBPF_OK;
 }
 
+// ---- peaks and moments of score volumes (kernels_surface.hip) -----------------------------------------------------
+int rbpf_score_surface(rbpf_handle* h, const int32_t* scores, int32_t n_items, int32_t n_rot, int32_t n_trans,
+                       const int32_t* drop_n, int32_t ex_trans, int32_t ex_rot, int32_t n_peaks,
+                       int64_t* out_nk16, int32_t* out_count, uint32_t flags) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!scores || !out_nk16) return fail(h, RBPF_EINVAL, "scores or out_nk16 is NULL");
+    if (flags & ~(RBPF_SURFACE_DEVICE_IN | RBPF_SURFACE_DEVICE_OUT)) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (n_items < 1) return fail(h, RBPF_EINVAL, "n_items >= 1 is required");
+    if (n_trans < 0 || n_trans > 32) return fail(h, RBPF_EINVAL, "0 <= n_trans <= 32 is required");
+    if (n_rot < 0 || n_rot > 100) return fail(h, RBPF_EINVAL, "0 <= n_rot <= 100 is required");
+    if (ex_trans < 0 || ex_trans > 64 || ex_rot < 0 || ex_rot > 200) return fail(h, RBPF_EINVAL, "0 <= ex_trans <= 64 and 0 <= ex_rot <= 200 are required");
+    if (n_peaks < 1 || n_peaks > SURFACE_MAX_PEAKS) return fail(h, RBPF_EINVAL, "1 <= n_peaks <= 8 is required");
+    const size_t N = (size_t)n_items, K = (size_t)n_peaks, per = (size_t)(2 * n_rot + 1) * (2 * n_trans + 1) * (2 * n_trans + 1), vol = N * per;
+    if (vol >= ((size_t)1 << 31)) return fail(h, RBPF_EINVAL, "n_items * (2 n_rot + 1) * (2 n_trans + 1)^2 < 2^31 is required");
+    const bool dev_in = (flags & RBPF_SURFACE_DEVICE_IN) != 0, dev_out = (flags & RBPF_SURFACE_DEVICE_OUT) != 0;
+    if (!dev_in) {
+        for (size_t n = 0; drop_n && n < N; ++n)
+            if (drop_n[n] < 0 || drop_n[n] > 32768) return fail(h, RBPF_EINVAL, "0 <= drop_n[n] <= 32768 is required");
+        for (size_t t = 0; t < vol; ++t)
+            if ((uint32_t)scores[t] > 32768u) return fail(h, RBPF_EINVAL, "a score outside 0 .. 32768");
+    }
+    if (h->scan_begun) return fail(h, RBPF_ESTATE, "score surface between rbpf_scan_update_begin and rbpf_scan_update_end");
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // scratch: [host volume] [host drops] | host outputs
+    const size_t drop_at = dev_in ? 0 : pad(vol * 4), in_b = dev_in ? 0 : drop_at + (drop_n ? N * 4 : 0);
+    const size_t rec_b = dev_out ? 0 : pad(N * K * 128), cnt_b = dev_out ? 0 : pad(N * 4);
+    const size_t total = pad(in_b) + rec_b + cnt_b;
+    if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "the volume and the records need more than 4 GiB: fewer items per call");
+    SurfaceArgs a;
+    a.N = n_items; a.R = n_rot; a.W = n_trans; a.ex_t = ex_trans; a.ex_r = ex_rot; a.K = n_peaks;
+    a.scores = scores; a.drop = drop_n;
+    a.out = reinterpret_cast<long long*>(out_nk16); a.count = out_count;
+    if (total) {
+        HIP_TRY(h, h->reserve(B_SURFACE, total));
+        const Block& d = h->buf[B_SURFACE];
+        if (!dev_in) {
+            Staging& st = h->stage[S_SURFACE];
+            HIP_TRY(h, st.begin(in_b));                                    // the last upload may still read it
+            memcpy(st.p, scores, vol * 4);
+            if (drop_n) memcpy(st.p + drop_at, drop_n, N * 4);
+            HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+            a.scores = d.as<const int32_t>();
+            a.drop = drop_n ? d.as<const int32_t>(drop_at) : nullptr;
+        }
+        if (!dev_out) { a.out = d.as<long long>(pad(in_b)); a.count = d.as<int32_t>(pad(in_b) + rec_b); }
+    }
+    launch_score_surface(a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    HIP_TRY(h, hipMemcpyAsync(out_nk16, a.out, N * K * 128, hipMemcpyDeviceToHost, h->stream));
+    if (out_count) HIP_TRY(h, hipMemcpyAsync(out_count, a.count, N * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 }  // extern "C"

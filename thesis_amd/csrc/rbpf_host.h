@@ -45,8 +45,9 @@ struct Block {
 // trajectory read-out or an estimate; poses, beams, ranges, end cells and host rasters of a map building; guesses, rotations, beams,
 // ranges, field planes, merge words and host outputs of a pose refinement; guesses, rotations, scan poses, beams, ranges, pair lists,
 // the pairs' fields, merge words and host outputs of a pair matching; sectors and ranges, or limits and descriptor tables, the
-// dilated references, their weights, the chunks' lists and host outputs of a scan description or a place search
-enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_SCORE, B_TRACK, B_BUILD, B_REFINE, B_PAIRS, B_PLACES, B_COUNT };
+// dilated references, their weights, the chunks' lists and host outputs of a scan description or a place search; the host volume,
+// the host drops and the host outputs of a score surface
+enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_SCORE, B_TRACK, B_BUILD, B_REFINE, B_PAIRS, B_PLACES, B_SURFACE, B_COUNT };
 
 // A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
 // early error return cannot pull memory from under queued work.
@@ -82,8 +83,8 @@ struct Staging : Block {
 // the table and the host reference uploaded into B_SCORE (pageable); the particle list or the weights uploaded into B_TRACK (pageable);
 // the poses, beams and ranges uploaded into B_BUILD (pageable); the guesses, rotations, beams and ranges uploaded into B_REFINE (pageable);
 // the guesses, rotations, scan poses, beams, ranges and pair lists uploaded into B_PAIRS (pageable); the sectors and ranges, or the
-// limits and host descriptor tables, uploaded into B_PLACES (pageable)
-enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_SCORE, S_TRACK, S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_COUNT };
+// limits and host descriptor tables, uploaded into B_PLACES (pageable); the host volume and drops uploaded into B_SURFACE (pageable)
+enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_SCORE, S_TRACK, S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_SURFACE, S_COUNT };
 
 // Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
 // copy that read it has completed (its event), so uploading never drains the stream.
@@ -137,7 +138,8 @@ struct rbpf_handle {
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;

@@ -241,6 +241,19 @@ struct PlacesArgs {
     int4* partial;                     // [nq][nch][k] {r, s, v, w} best first, {-1, 0, 0, 0} behind the last
     int32_t *out_qk4, *out_q2;         // [nq][k][4], [nq][2]; either may be null
 };
+// peaks and moments of score volumes (kernels_surface.hip): the K best candidates of each of N volumes that lie
+// outside one another's exclusion boxes, each with the size and the weighted sums of its plateau
+static const int SURFACE_BLOCK = 512;      // lanes of a workgroup, one workgroup per item
+static const int SURFACE_MAX_PEAKS = 8;
+static const int SURFACE_SUMS = 11;        // |T|, sum w, three first and six second moments
+struct SurfaceArgs {
+    int N, R, W;                       // items; n_rot and n_trans of the volume, [2 R + 1][2 W + 1][2 W + 1] per item
+    int ex_t, ex_r, K;                 // the exclusion box's half-widths in translation and rotation steps; peaks per item
+    const int32_t* scores;             // [N][2 R + 1][2 W + 1][2 W + 1]
+    const int32_t* drop;               // [N] or null (0): the plateau reaches this far below its peak
+    long long* out;                    // [N][K][16]
+    int32_t* count;                    // [N] peaks found, or null
+};
 // global localization (kernels_locate.hip): one scan against one particle's map over a box of candidate cells
 struct LocateArgs {
     int particle;
@@ -422,6 +435,7 @@ void launch_match_pairs(const PairsArgs& p, const RefineArgs& a, hipStream_t s);
 void launch_describe_scans(const double* d_ranges, const int32_t* d_sector, int n_scans, int n_beams, int n_rings, double min_range,
                            double max_range, double rings_per_m, unsigned long long* d_desc, int32_t* d_info, hipStream_t s);   // either output may be null
 void launch_match_places(const PlacesArgs& a, hipStream_t s);                    // field, search and merge
+void launch_score_surface(const SurfaceArgs& a, hipStream_t s);                  // every record and count is written
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0

@@ -77,6 +77,67 @@ class PairResult(NamedTuple):
     cell_size: float     # metres: a translation step is cell_size / substeps
 
 
+class ScoreSurface(NamedTuple):
+    """ParticleEngine.score_surface: the K best separated peaks of each of N score volumes and the moments of their plateaus
+    (include/rbpf_hip.h, rbpf_score_surface).  numpy arrays, or torch tensors on the GPU; the methods work on
+    the host and bring tensors there first.  thesis_amd/loops.py reads them."""
+    index: Any           # int64 [N, K, 3]: (i, j, k) of peak p, in steps of cell_size / substeps and of rot_step; 0 behind count
+    score: Any           # int64 [N, K]: its score
+    count: Any           # int32 [N]: peaks found, 1 .. K
+    size: Any            # int64 [N, K]: |T|, the cells of the plateau
+    moments: Any         # int64 [N, K, 10]: sum w, sum w d (di, dj, dk), sum w d d^T (ii, ij, ik, jj, jk, kk) over the plateau
+    drop: Any            # int32 [N]: the plateau reaches this far below its peak
+    substeps: Optional[int] = None       # the three below come with a RefineResult or a PairResult, else None
+    rot_step: Optional[float] = None
+    cell_size: Optional[float] = None
+
+    @classmethod
+    def from_records(cls, records, count, drop, substeps=None, rot_step=None, cell_size=None):
+        """From the library's records [N, K, 16] (include/rbpf_hip.h)."""
+        return cls(records[..., 0:3], records[..., 3], count, records[..., 4], records[..., 5:15], drop, substeps, rot_step, cell_size)
+
+    @staticmethod
+    def _host(a):
+        return a.cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+
+    def ambiguity(self) -> np.ndarray:
+        """float64 [N]: score of the second peak / score of the best where there is a second peak and the best score is
+        positive, else 0.  Near 1: another place in the window fits almost as well."""
+        sc, cnt = self._host(self.score).astype(np.float64), self._host(self.count)
+        out = np.zeros(len(cnt))
+        if sc.shape[1] >= 2:
+            ok = (cnt >= 2) & (sc[:, 0] > 0)
+            out[ok] = sc[ok, 1] / sc[ok, 0]
+        return out
+
+    def offset(self, peak: int = 0) -> np.ndarray:
+        """float64 [N, 3]: the weighted mean offset (di, dj, dk) of the plateau from its peak, in steps; 0 behind count."""
+        m = self._host(self.moments)[:, peak].astype(np.float64)
+        return m[:, 1:4] / np.maximum(m[:, 0:1], 1.0)
+
+    def second_moment(self, peak: int = 0) -> np.ndarray:
+        """float64 [N, 3, 3]: the plateau's second moment about the peak, diag(u) (sum w d d^T / sum w) diag(u) with u =
+        (cell_size / substeps, cell_size / substeps, rot_step): metres and radians along the search axes (world x, world y,
+        heading).  Needs the steps, so a surface of a RefineResult or a PairResult; 0 behind count."""
+        if self.cell_size is None or self.substeps is None or self.rot_step is None:
+            raise ValueError("a surface of a bare volume has no step sizes: pass the RefineResult or PairResult")
+        m = self._host(self.moments)[:, peak].astype(np.float64)
+        ii, ij, ik, jj, jk, kk = (m[:, q] for q in range(4, 10))
+        c = np.stack([np.stack([ii, ij, ik], axis=1), np.stack([ij, jj, jk], axis=1), np.stack([ik, jk, kk], axis=1)], axis=1)
+        c /= np.maximum(m[:, 0], 1.0)[:, None, None]
+        u = np.array([self.cell_size / self.substeps, self.cell_size / self.substeps, self.rot_step])
+        return c * u[:, None] * u[None, :]
+
+    def poses(self, guesses) -> np.ndarray:
+        """float64 [N, K, 3]: the peaks as poses round `guesses` [N, 3]: (gx + i step, gy + j step, gtheta + k rot_step)."""
+        if self.cell_size is None or self.substeps is None or self.rot_step is None:
+            raise ValueError("a surface of a bare volume has no step sizes: pass the RefineResult or PairResult")
+        g = _f64(guesses).reshape(-1, 1, 3)
+        idx = self._host(self.index).astype(np.float64)
+        u = np.array([self.cell_size / self.substeps, self.cell_size / self.substeps, self.rot_step])
+        return g + idx * u
+
+
 class ScanDescriptors(NamedTuple):
     """ParticleEngine.describe_scans: per scan [N] (numpy arrays, or torch tensors on the GPU)."""
     desc: Any            # [N, R]: ring g of scan n, bit j = sector j.  numpy uint64; on the GPU int64 with the same bits
@@ -1561,6 +1622,80 @@ class ParticleEngine:
             self.synchronize()
         del qd, rd                                       # kept alive until the call returned
         return PlaceMatches(qk4[..., 0], qk4[..., 1], qk4[..., 2], qk4[..., 3], q2[:, 0], q2[:, 1])
+
+    # -- score surface (include/rbpf_hip.h: rbpf_score_surface; thesis_amd/loops.py) -----------------------------
+    @staticmethod
+    def surface_exclusion(window: int, rotations: int) -> Tuple[int, int]:
+        """score_surface's default exclusion box (translation steps, rotation steps): a quarter of the window's full width
+        on each axis, ceil(window / 2) and ceil(rotations / 2), at least 1.  A convention, not a tuned value."""
+        return max(1, -(-int(window) // 2)), max(1, -(-int(rotations) // 2))
+
+    def score_surface(self, scores, drop=None, drop_fraction: float = 0.05, exclude=None, peaks: int = 2,
+                      device: bool = False) -> ScoreSurface:
+        """What a score volume says beyond its best candidate: the `peaks` (1 .. 8) best candidates that lie outside one
+        another's exclusion boxes, and for each the plateau of candidates within `drop` of it inside its box: size, weight
+        and first and second moments in exact integers.  `scores` is a RefineResult or PairResult that carries its volume
+        (return_scores=True; numpy, or device tensors from device=True), or a bare int32 [N, 2R+1, 2W+1, 2W+1] array or
+        tensor; a volume on the GPU is read where it is.  `drop` [N] (or one number): with a result and None it is
+        floor(drop_fraction * 2 n_used); with a bare volume and None it is 0.  `exclude` = (translation steps, rotation
+        steps) defaults to surface_exclusion(W, R).  device=True: torch tensors on the engine's device, ready for work on
+        torch's current stream."""
+        res = scores if hasattr(scores, "scores") and hasattr(scores, "n_used") else None      # a RefineResult or a PairResult
+        vol = scores.scores if res is not None else scores
+        if vol is None:
+            raise ValueError("the result carries no score volume: ask for return_scores=True")
+        dev_in = hasattr(vol, "data_ptr")
+        torch = dev = cur = None
+        same_stream = False
+        if dev_in or device:
+            torch, dev, cur, same_stream = self._torch_stream()
+        if dev_in:
+            if vol.dtype != torch.int32 or vol.dim() != 4 or vol.device != dev:
+                raise ValueError("a score tensor must be [N, 2R+1, 2W+1, 2W+1] int32 on the engine's device")
+            vol = vol.contiguous()
+        else:
+            vol = np.asarray(vol)
+            if vol.ndim != 4 or vol.dtype != np.int32:
+                raise ValueError("scores must be [N, 2R+1, 2W+1, 2W+1] int32")
+            vol = np.ascontiguousarray(vol)
+        n, nk, nw = int(vol.shape[0]), int(vol.shape[1]), int(vol.shape[2])
+        if nk % 2 != 1 or nw % 2 != 1 or int(vol.shape[3]) != nw:
+            raise ValueError("scores must be [N, 2R+1, 2W+1, 2W+1]")
+        R, W = nk // 2, nw // 2
+        if drop is None:
+            if res is not None:
+                used = ScoreSurface._host(res.n_used).astype(np.int64)
+                drop = np.floor(float(drop_fraction) * (2 * used).astype(np.float64))
+            else:
+                drop = 0
+        dr = np.array(np.broadcast_to(np.asarray(drop), (n,)), dtype=np.int32)       # a copy: contiguous and writeable
+        ex_t, ex_r = self.surface_exclusion(W, R) if exclude is None else (int(exclude[0]), int(exclude[1]))
+        k = int(peaks)
+        kk = min(max(k, 0), 8)                               # a bad count is the library's to refuse
+        flags = 0
+        if dev_in:
+            dr_in = torch.from_numpy(dr).to(dev)
+            ins = [C.c_void_p(vol.data_ptr() or 1), C.c_void_p(dr_in.data_ptr() or 1)]
+            flags |= _lib.RBPF_SURFACE_DEVICE_IN
+        else:
+            ins = [C.c_void_p(vol.ctypes.data or 1), C.c_void_p(dr.ctypes.data or 1)]
+        if device:
+            rec = torch.empty((n, kk, 16), dtype=torch.int64, device=dev)
+            cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+            outs = [C.c_void_p(rec.data_ptr() or 1), C.c_void_p(cnt.data_ptr() or 1)]
+            flags |= _lib.RBPF_SURFACE_DEVICE_OUT
+        else:
+            rec, cnt = np.empty((n, kk, 16), dtype=np.int64), np.empty((n,), dtype=np.int32)
+            outs = [C.c_void_p(rec.ctypes.data or 1), C.c_void_p(cnt.ctypes.data or 1)]
+        if cur is not None and not same_stream:
+            cur.synchronize()                                # the tensors were written or allocated in torch's stream order
+        self._check(self._lib.rbpf_score_surface(self._h, ins[0], n, R, W, ins[1], ex_t, ex_r, k, *outs, flags))
+        if device and not same_stream:
+            self.synchronize()
+        del vol, ins                                         # kept alive until the call returned
+        dr_out = torch.from_numpy(dr).to(dev) if device else dr
+        steps = (int(res.substeps), float(res.rot_step), float(res.cell_size)) if res is not None else (None, None, None)
+        return ScoreSurface.from_records(rec, cnt, dr_out, *steps)
 
     def get_odds_at(self, particle: int, xy) -> Tuple[np.ndarray, np.ndarray]:
         pts = _f64(xy).reshape(-1, 2)
