@@ -118,6 +118,9 @@ typedef struct rbpf_counters {
                                      the same scan, found by the walk's returning adds, summed over particles       */
     uint64_t map_event_overflows; /* ... particles whose list of such passes was full (every flagged cell of theirs
                                      was then replayed by the exact membership test)                               */
+    uint64_t map_updates_skipped; /* particles a map update left out because the resample that followed discarded them
+                                     (rbpf_resample right behind rbpf_scan_update); ray_cells_visited, cells_written and
+                                     the other map-update tallies do not count them                                */
 } rbpf_counters;
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
@@ -170,7 +173,21 @@ int  rbpf_map_update(rbpf_handle* h, const double* poses);
  * match_override : NULL => built-in correlative matcher; else [P*13] = pose(3), cov(9), score(1)
  *                  per particle, as returned by Map.get_scan_match (engine-seam double)
  * guesses        : NULL => on-device Philox proposal; else [P*K*3] explicit samples
- *                  (replaces np.random.multivariate_normal, robot.py:81)                       */
+ *                  (replaces np.random.multivariate_normal, robot.py:81)
+ * The map update waits for the next call in filters of more than four particles per compute unit of the device (below
+ * that, leaving particles out saves no round of the map kernel and the step is as ever).  There, with map updates on,
+ * rbpf_scan_update queues the matcher, the proposal and
+ * the weighting and holds back what rbpf_scan_update_end does (the map update, the NaN-branch weight increments, the
+ * step's trajectory record).  rbpf_resample as the next call launches its plan first, then the held-back update WITHOUT
+ * the particles the plan discards - their maps are overwritten by the copies that follow -, then copies and release; if a
+ * particle is on the NaN-covariance branch its weight still changes, the plan is made behind the update and nobody is left
+ * out.  Every other entry point that touches the device launches the held-back update whole before anything else
+ * (rbpf_set_stream and rbpf_release_stream on the old stream; rbpf_destroy drops it), so results, counters and the order
+ * of work in the stream are those of rbpf_scan_update_begin + _end for every sequence of calls; only
+ * counters.map_updates_skipped and the map update's tallies tell a left-out particle.  What the host alone keeps
+ * (scan_updates, the random streams' position, the trajectory log's record count) changes at the call.
+ * RBPF_SKIP_DISCARDED in the environment of rbpf_create (tests, A/B runs): 1 holds back whatever the filter's size;
+ * 0 does too and leaves nobody out - the same order of launches.                                                  */
 int  rbpf_scan_update(rbpf_handle* h, int32_t adj, const double* last_scan_xy, int32_t n_last,
                       const double* match_override, const double* guesses);
 /* main.py:167-168: last_scan = scan.from_global_reference(particles[0].get_latest_pose()).  Computed on the device
@@ -226,7 +243,10 @@ int  rbpf_native_sincosf(rbpf_handle* h, const float* x, int32_t n, float* s, fl
  * many FREE tiles as it allocates, not the net number: one that releases a tile and allocates another with no free tile
  * fails.  Exhaustion is RBPF_ENOMEM (here with idx_out or did_resample, else at the next call that checks the device's
  * error word, e.g. rbpf_synchronize); the maps are then incomplete and the handle should be destroyed.  The same holds for
- * rbpf_apply_resample_local. */
+ * rbpf_apply_resample_local.
+ * Right behind rbpf_scan_update the call also launches that step's map update, between its plan and its copies (see
+ * there); ms_resample and the "resample" timings stay plan plus copies.  An invalid u launches the update whole, then
+ * fails as ever. */
 int  rbpf_resample(rbpf_handle* h, double u, int32_t* idx_out, int32_t* did_resample);
 
 /* multi-GPU pieces (one handle per rank; the collectives themselves are the caller's, over RCCL).

@@ -59,7 +59,7 @@ class RbpfCounters(C.Structure):
         ("ndt_accepted", C.c_uint64), ("match_shared", C.c_uint64),
         ("fallback_reasons", C.c_uint64), ("ms_ndt", C.c_double), ("stamp7", C.c_uint64), ("map_windows", C.c_uint64),
         ("fallback_geometry", C.c_uint64), ("fallback_bound", C.c_uint64), ("fallback_tables", C.c_uint64),
-        ("map_events", C.c_uint64), ("map_event_overflows", C.c_uint64),
+        ("map_events", C.c_uint64), ("map_event_overflows", C.c_uint64), ("map_updates_skipped", C.c_uint64),
     ]
 
 

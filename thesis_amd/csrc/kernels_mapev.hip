@@ -191,10 +191,18 @@ __device__ __forceinline__ void ev_prefetch(const DevView& v, int p, EvNext* rec
     if (lane == 0) { rec->px = v.upd_pose[p]; rec->py = v.upd_pose[v.P + p]; rec->sn = sn; rec->cs = cs_; rec->slot = slot; rec->p = p; }
 }
 
+// The particle a position of the launch stands for: itself, or - when the coming resample discards some particles (DevView::
+// mu_keep) - the position's entry in the list of the others; v.P behind the last one.
+__device__ __forceinline__ int ev_position(const DevView& v, int pos) {
+    if (!v.mu_keep) return pos;
+    return pos < *v.mu_n_keep ? v.mu_keep[pos] : v.P;
+}
+
 // One particle's update by the whole workgroup.  `draw`: thread 0 takes the workgroup's NEXT particle from the queue (its first
-// one is blockIdx.x, the queue hands out gridDim.x, gridDim.x + 1, ...) before anything else, so that the add's round trip
-// lies under the preamble's loads, and leaves it in *s_next (v.P or more: none) before the particle's first barrier - or
-// before it returns ahead of that barrier.  Every return is uniform over the workgroup; the caller's barrier follows.
+// one is position blockIdx.x, the queue hands out positions gridDim.x, gridDim.x + 1, ...) before anything else, so that the
+// add's round trip - and the look-up of the position behind it - lies under the preamble's loads, and leaves it in *s_next
+// (v.P or more: none) before the particle's first barrier - or before it returns ahead of that barrier.  Every return is
+// uniform over the workgroup; the caller's barrier follows.
 __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const int p, const bool draw, int* s_next, EvNext* rec) {
     extern __shared__ __align__(16) unsigned char smem[];
     int tid_ = threadIdx.x;
@@ -202,7 +210,7 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
     __builtin_assume((unsigned)tid_ < (unsigned)EB);
     const int tid = tid_, lane = tid & 63, wave = tid >> 6;
     int nxt = v.P;
-    if (draw && tid == 0) nxt = (int)gridDim.x + (int)atomicAdd(&v.ev_queue[0], 1u);
+    if (draw && tid == 0) nxt = ev_position(v, (int)gridDim.x + (int)atomicAdd(&v.ev_queue[0], 1u));
     const EvGeom G = ev_geom(v.B, v.reach);
     uint32_t* const cnt = reinterpret_cast<uint32_t*>(smem + G.o_cnt);     // 8-bit fields: bit 0 = flagged, bits 1-7 = passes; [row = global x][col = global y]
     uint8_t*  const cnt8 = smem + G.o_cnt;
@@ -815,6 +823,8 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
 // another one, so nothing depends on how many of them run at the same time.  The queue re-arms itself: a workgroup
 // that leaves has made its last draw, so the one that counts itself last in v.ev_queue[1] puts both words back to
 // zero for the next launch in the stream.  resident == 0: one workgroup per particle, no draw (A/B runs, tests).
+// Both count in positions of the launch (ev_position): a workgroup whose first position lies behind the last particle that
+// stays runs nothing and leaves.
 // THE KERNEL HAS ONE ARGUMENT, this struct: the loop below reads `v` through the kernel-argument segment's own address, where a
 // sole argument lies by construction (and `v` first in it: the static_assert).  Do not add a second argument; add a member.
 struct EvKernArgs { DevView v; int resident; };
@@ -826,7 +836,7 @@ __global__ __launch_bounds__(EB) void map_update_ev_kernel(EvKernArgs ka_) {
     __shared__ EvNext s_rec;
     if (threadIdx.x == 0) s_rec.p = -1;
     __syncthreads();
-    int p = blockIdx.x;
+    int p = ev_position(v, (int)blockIdx.x);
     for (int it = 0; p < v.P; ++it) {
         // The particle's code reads the kernel's arguments through a pointer the compiler cannot see through: whatever it works out
         // from them is worked out per particle, as in a kernel of its own.  (Known to be the same for every particle it was kept in

@@ -110,6 +110,7 @@ __device__ __forceinline__ void fld16_add(int cabs, uint32_t one) {     // 16-bi
 
 __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int32_t* __restrict__ only) {
     if (only && !only[blockIdx.x]) return;                                 // the kernel that ran first did this particle
+    if (v.mu_skip && v.mu_skip[blockIdx.x]) return;                        // the coming resample discards it (DevView::mu_skip)
     extern __shared__ __align__(16) unsigned char smem[];
     const RayGeom G = ray_geom(v.B, v.reach);
     uint32_t* const cnt = reinterpret_cast<uint32_t*>(smem + G.o_cnt);     // 8-bit hit fields, [row = global x][col = global y]

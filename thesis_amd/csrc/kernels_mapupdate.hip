@@ -624,7 +624,9 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
 // workgroup or, earlier, by the whole-fan kernel): one launch less per step.
 __global__ __launch_bounds__(MU_BLOCK, 4) void map_update_kernel(DevView v, const int32_t* __restrict__ only,
                                                                  const uint8_t* __restrict__ bad) {   // 2 workgroups per CU
-    if (!only || only[blockIdx.x]) map_update_particle(v, only != nullptr);
+    // a particle the coming resample discards (DevView::mu_skip) is left out here too: the first kernel did not touch it, so its
+    // entry in `only` is the one of its last update
+    if ((!only || only[blockIdx.x]) && !(v.mu_skip && v.mu_skip[blockIdx.x])) map_update_particle(v, only != nullptr);
     if (bad && bad[blockIdx.x]) {
         __syncthreads();
         nan_branch_weight(v, blockIdx.x, threadIdx.x, MU_BLOCK);

@@ -218,6 +218,56 @@ __device__ void resample_pair_stage(const PairArgs& a) {
     if (tid == 0) { a.n_jobs[0] = total_job; a.n_jobs[1] = 0; }
 }
 
+// ---- the plan in two launches round a map update (rbpf_resample behind rbpf_scan_update) -------------------
+// phase 1, before the update: the plan from the weights as they are, which are final unless a particle is on the NaN-covariance
+// branch (bad[p]: its weight grows on its updated map, robot.py:73-78).  plan[1] = 1: the plan stands, and the particles
+// without offspring are the ones the update leaves out; 0: no plan, nobody is left out.  phase 2, behind the update: returns
+// at once if the plan stands, else makes it.  phase 0: a plan of its own, as ever.
+struct PhaseArgs {
+    int phase;
+    const uint8_t* bad;       // [P]
+    int32_t* plan;            // [2] length of keep, the verdict
+    uint8_t* skip;            // [P] DevView::mu_skip
+    int32_t* keep;            // [P] DevView::mu_keep
+    int leave_out;            // 0: nobody is left out whatever the plan says (RBPF_SKIP_DISCARDED=0)
+    unsigned long long* stats;
+};
+// phase 1 or 2: this launch has nothing to do
+__device__ __forceinline__ bool plan_phase_idle(const PhaseArgs& ph) { return ph.phase != 0 && (ph.plan[1] != 0) != (ph.phase == 1); }
+
+// phase 1, first thing: any particle on the NaN branch?  Writes the verdict, returns it (uniform)
+__device__ bool plan_phase_verdict(int P, const PhaseArgs& ph) {
+    const int tid = threadIdx.x, chunk = (P + PLAN_THREADS - 1) / PLAN_THREADS;
+    const int i0 = min(tid * chunk, P), i1 = min(i0 + chunk, P);
+    int any = 0;
+    for (int i = i0; i < i1; ++i) any |= ph.bad[i];
+    any = __syncthreads_or(any);
+    if (tid == 0) ph.plan[1] = any ? 0 : 1;
+    return any == 0;
+}
+
+// phase 1, last thing: flags and the ascending list of the particles that stay.  leave: those without offspring (T_i == T_{i-1},
+// the pair stage's dead ones) are left out; else nobody
+__device__ void plan_keep_stage(int P, const int32_t* T, bool leave, const PhaseArgs& ph) {
+    __shared__ int s_kbuf[PLAN_THREADS / 64];
+    const int tid = threadIdx.x, chunk = (P + PLAN_THREADS - 1) / PLAN_THREADS;
+    const int i0 = min(tid * chunk, P), i1 = min(i0 + chunk, P);
+    int n = 0;
+    for (int i = i0; i < i1; ++i) {
+        const bool dead = leave && (T[i] - (i > 0 ? T[i - 1] : 0)) == 0;
+        ph.skip[i] = dead ? 1 : 0;
+        n += dead ? 0 : 1;
+    }
+    int total;
+    int base = block_exclusive_scan_1024(n, s_kbuf, tid, total);
+    for (int i = i0; i < i1; ++i)
+        if (!(leave && (T[i] - (i > 0 ? T[i - 1] : 0)) == 0)) ph.keep[base++] = i;
+    if (tid == 0) {
+        ph.plan[0] = total;
+        if (total < P) atomicAdd(&ph.stats[ST_MU_SKIPPED], (unsigned long long)(P - total));
+    }
+}
+
 // ---- kernel 4: permute the small per-particle state, weights <- 1.0 (main.py:77-78) ---------------------
 struct GatherArgs {
     int P;
@@ -514,12 +564,23 @@ __global__ __launch_bounds__(BLOCK) void unpack_kernel(DevView v, const UnpackJo
 }
 
 // ---- kernels: the stages one by one (any P), or the small ones fused into one single-workgroup launch ------------
-__global__ __launch_bounds__(PLAN_THREADS) void resample_plan_kernel(ResampleArgs a) { resample_plan_stage(a); }
-__global__ void resample_expand_kernel(int P, const int32_t* __restrict__ T, int32_t* __restrict__ idx) {
+__global__ __launch_bounds__(PLAN_THREADS) void resample_plan_kernel(ResampleArgs a, PhaseArgs ph) {
+    if (ph.phase == 1 ? !plan_phase_verdict(a.P, ph) : plan_phase_idle(ph)) return;
+    resample_plan_stage(a);
+}
+__global__ void resample_expand_kernel(int P, const int32_t* __restrict__ T, int32_t* __restrict__ idx, PhaseArgs ph) {
+    if (plan_phase_idle(ph)) return;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < P) resample_expand_one(P, T, idx, j);
 }
-__global__ __launch_bounds__(PLAN_THREADS) void resample_pair_kernel(PairArgs a) { resample_pair_stage(a); }
+__global__ __launch_bounds__(PLAN_THREADS) void resample_pair_kernel(PairArgs a, PhaseArgs ph) {
+    if (plan_phase_idle(ph)) {
+        if (ph.phase == 1) plan_keep_stage(a.P, a.T, false, ph);
+        return;
+    }
+    resample_pair_stage(a);
+    if (ph.phase == 1) { __syncthreads(); plan_keep_stage(a.P, a.T, ph.leave_out && *a.did, ph); }
+}
 __global__ __launch_bounds__(PLAN_THREADS) void sources_to_T_kernel(int P, const int32_t* __restrict__ idx, int32_t* __restrict__ T,
                                                                      int32_t* __restrict__ did) { sources_to_T_stage(P, idx, T, did); }
 
@@ -529,7 +590,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void sources_to_T_kernel(int P, const
 enum { RS_PLAN = 1, RS_SRC2T = 2, RS_EXPAND = 4, RS_PAIR = 8, RS_GATHER = 16 };
 static const int RS_FUSE_MAX = 4096;        // beyond this the single workgroup costs more than the launches it saves
 static const int RS_GATHER_FUSE_MAX = 1024; // ... and the state permutation alone beyond this
-struct FusedArgs { int stages; ResampleArgs ra; int32_t* idx; PairArgs pa; GatherArgs ga; };
+struct FusedArgs { int stages; ResampleArgs ra; int32_t* idx; PairArgs pa; GatherArgs ga; PhaseArgs ph; };
 __global__ __launch_bounds__(PLAN_THREADS) void resample_fused_kernel(FusedArgs f) {
     // T and the ancestor indices also live in LDS from the stage that makes them: the later stages search and chase them
     // (a binary search per new particle, neighbour comparisons), which through global memory is a chain of L2 round trips
@@ -543,6 +604,9 @@ __global__ __launch_bounds__(PLAN_THREADS) void resample_fused_kernel(FusedArgs 
 #else
 #define RSTAMP(k) do { } while (0)
 #endif
+    if (f.ph.phase == 1) {
+        if (!plan_phase_verdict(P, f.ph)) { plan_keep_stage(P, f.ra.T, false, f.ph); return; }
+    } else if (plan_phase_idle(f.ph)) return;
     if (f.stages & RS_PLAN) { resample_plan_stage(f.ra); __syncthreads(); }
     RSTAMP(1);
     if (f.stages & RS_SRC2T) { sources_to_T_stage(P, f.idx, f.ra.T, f.ra.did); __syncthreads(); }
@@ -553,6 +617,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void resample_fused_kernel(FusedArgs 
     __syncthreads();
     RSTAMP(2);
     if (f.stages & RS_PAIR) { PairArgs pa = f.pa; pa.T = s_T; pa.idx = s_idx; resample_pair_stage(pa); __syncthreads(); }
+    if (f.ph.phase == 1) plan_keep_stage(P, s_T, f.ph.leave_out && *f.ra.did, f.ph);
     RSTAMP(3);
     if (f.stages & RS_GATHER) { GatherArgs ga = f.ga; ga.T = s_T; ga.idx = s_idx; for (int j = tid; j < ga.P; j += PLAN_THREADS) resample_gather_one(ga, j); }
     RSTAMP(4);
@@ -590,35 +655,55 @@ void launch_resample_indices(int P, const double* d_w, double u, double spread, 
                              int32_t* d_did, int32_t* d_err, hipStream_t s) {
     ResampleArgs ra{P, d_w, u, spread, d_T, d_did, d_err};
     if (P <= RS_FUSE_MAX) {
-        FusedArgs f{RS_PLAN | RS_EXPAND, ra, d_idx, PairArgs{}, GatherArgs{}};
+        FusedArgs f{RS_PLAN | RS_EXPAND, ra, d_idx, PairArgs{}, GatherArgs{}, PhaseArgs{}};
         launch_resample_fused(f, s);
         return;
     }
-    hipLaunchKernelGGL(resample_plan_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, ra);
-    hipLaunchKernelGGL(resample_expand_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, d_T, d_idx);
+    hipLaunchKernelGGL(resample_plan_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, ra, PhaseArgs{});
+    hipLaunchKernelGGL(resample_expand_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, d_T, d_idx, PhaseArgs{});
+}
+
+// the planning launches of the local resample: T and the ancestors, slot pairing, the state permutation where it is fused
+static void launch_resample_planning(const DevView& v, const ResampleBuffers& b, const double* d_w, double u, double spread,
+                                     const PhaseArgs& ph, hipStream_t s) {
+    const PairArgs pa{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err};
+    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
+    if (v.P > RS_FUSE_MAX) {                                   // the stages one launch each
+        if (d_w) {
+            hipLaunchKernelGGL(resample_plan_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, ResampleArgs{v.P, d_w, u, spread, b.T, b.did, v.err}, ph);
+            hipLaunchKernelGGL(resample_expand_kernel, dim3((v.P + 255) / 256), dim3(256), 0, s, v.P, b.T, b.idx, ph);
+        } else hipLaunchKernelGGL(sources_to_T_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, v.P, b.idx, b.T, b.did);
+        hipLaunchKernelGGL(resample_pair_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, pa, ph);
+    } else {
+        FusedArgs f{(d_w ? RS_PLAN | RS_EXPAND : RS_SRC2T) | RS_PAIR | (v.P <= RS_GATHER_FUSE_MAX ? RS_GATHER : 0),
+                    ResampleArgs{v.P, d_w, u, spread, b.T, b.did, v.err}, b.idx, pa, ga, ph};
+        launch_resample_fused(f, s);
+    }
+}
+
+void launch_resample_plan_early(const DevView& v, const ResampleBuffers& b, const uint8_t* d_bad, int leave_out, double u, double spread, hipStream_t s) {
+    launch_resample_planning(v, b, v.weight, u, spread, PhaseArgs{1, d_bad, b.plan, b.skip, b.keep, leave_out, v.stats}, s);
+}
+void launch_resample_plan_late(const DevView& v, const ResampleBuffers& b, double u, double spread, hipStream_t s) {
+    launch_resample_planning(v, b, v.weight, u, spread, PhaseArgs{2, nullptr, b.plan, b.skip, b.keep, 0, v.stats}, s);
+}
+
+// the tile copies (with the state permutation where the plan did not take it) and the release of the tiles they gave up
+void launch_resample_copies(const DevView& v, const ResampleBuffers& b, hipStream_t s) {
+    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
+    // the state permutation moves 200 bytes per particle: through one CU it took as long as the three planning stages together
+    // (25 us of the fused kernel's 54 at 4096 particles), so beyond RS_GATHER_FUSE_MAX particles it rides with the tile copies
+    CopyArgs ca{v, b.jobs, b.n_jobs, b.pending_free, b.n_pending, v.P <= RS_GATHER_FUSE_MAX ? 0 : 1, ga};
+    hipLaunchKernelGGL(resample_copy_kernel, dim3(512), dim3(COPY_BLOCK), 0, s, ca);
+    hipLaunchKernelGGL(resample_release_kernel, dim3(1), dim3(256), 0, s, v, b.pending_free, b.n_pending);
 }
 
 // the whole local resample (main.py:46-79): T and the ancestors, slot pairing, state permutation, tile copies.  The first
 // stage plans from the weights d_w; with d_w == nullptr (the local part of a global resample) it turns the sources already
 // in b.idx (sorted ascending, -1 = arrival, last) into T, and u, spread are unused.
 void launch_resample_local(const DevView& v, const ResampleBuffers& b, const double* d_w, double u, double spread, hipStream_t s) {
-    const PairArgs pa{v.P, b.T, b.idx, b.did, v.slot, b.slot2, b.dead_list, b.jobs, b.n_jobs, v.err};
-    const GatherArgs ga{v.P, b.idx, b.did, v.px, v.py, v.pth, v.cov, v.weight, b.px2, b.py2, b.pth2, b.cov2, b.w2, b.T, v.dup_of};
-    // the state permutation moves 200 bytes per particle: through one CU it took as long as the three planning stages together
-    // (25 us of the fused kernel's 54 at 4096 particles), so beyond RS_GATHER_FUSE_MAX particles it rides with the tile copies
-    const bool fuse_gather = v.P <= RS_GATHER_FUSE_MAX;
-    if (v.P > RS_FUSE_MAX) {                                   // the stages one launch each
-        if (d_w) launch_resample_indices(v.P, d_w, u, spread, b.T, b.idx, b.did, v.err, s);
-        else hipLaunchKernelGGL(sources_to_T_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, v.P, b.idx, b.T, b.did);
-        hipLaunchKernelGGL(resample_pair_kernel, dim3(1), dim3(PLAN_THREADS), 0, s, pa);
-    } else {
-        FusedArgs f{(d_w ? RS_PLAN | RS_EXPAND : RS_SRC2T) | RS_PAIR | (fuse_gather ? RS_GATHER : 0),
-                    ResampleArgs{v.P, d_w, u, spread, b.T, b.did, v.err}, b.idx, pa, ga};
-        launch_resample_fused(f, s);
-    }
-    CopyArgs ca{v, b.jobs, b.n_jobs, b.pending_free, b.n_pending, fuse_gather ? 0 : 1, ga};
-    hipLaunchKernelGGL(resample_copy_kernel, dim3(512), dim3(COPY_BLOCK), 0, s, ca);
-    hipLaunchKernelGGL(resample_release_kernel, dim3(1), dim3(256), 0, s, v, b.pending_free, b.n_pending);
+    launch_resample_planning(v, b, d_w, u, spread, PhaseArgs{}, s);
+    launch_resample_copies(v, b, s);
 }
 
 }  // namespace rbpf

@@ -35,7 +35,11 @@ struct DevGuard {
     ~DevGuard() { if (switched) (void)hipSetDevice(prev); }
     DevGuard(const DevGuard&) = delete; DevGuard& operator=(const DevGuard&) = delete;
 };
-#define ON_DEVICE(h) DevGuard dev_guard_((h)->cfg.device)
+#define ON_DEVICE_HELD(h) DevGuard dev_guard_((h)->cfg.device)
+// ... and, first thing, launches the map update a preceding rbpf_scan_update held back (rbpf_resample alone takes it over
+// instead, rbpf_destroy drops it): whatever the entry point reads or queues finds the stream as if nothing had been held back
+static int flush_map_update(rbpf_handle* h);
+#define ON_DEVICE(h) ON_DEVICE_HELD(h); do { const int flush_rc_ = flush_map_update(h); if (flush_rc_) return flush_rc_; } while (0)
 
 static int fail(rbpf_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_err = msg;
@@ -73,16 +77,28 @@ static bool env_is(const char* name, const char* value) { const char* e = getenv
 // ---- trajectory log (kernels_track.hip): the pieces the step entry points queue while tracking is on ------------
 // one record from the current state, in stream order.  Log full: an implicit record (a step's own) is dropped and counted, an
 // explicit one is RBPF_ENOMEM; the host knows the count, nothing is read back
-static int track_record(rbpf_handle* h, bool implicit) {
+// the two halves apart: the record's place is taken when the step is called (-1: dropped), the record is queued when the step's
+// held-back map update is (the record holds the weights, which the NaN branch of that update changes)
+static int track_take_place(rbpf_handle* h, bool implicit, int& t) {
+    t = -1;
     if (h->track_n >= h->track_cap) {
         if (!implicit) return fail(h, RBPF_ENOMEM, "the trajectory log is full");
         h->track_dropped++;
         return RBPF_OK;
     }
-    launch_track_record(h->v, h->track_log(), h->track_n, h->track_pending(h->track_cur), h->stream);
-    HIP_TRY(h, hipGetLastError());
-    h->track_n++;
+    t = h->track_n++;
     return RBPF_OK;
+}
+static int track_queue(rbpf_handle* h, int t) {
+    if (t < 0) return RBPF_OK;
+    launch_track_record(h->v, h->track_log(), t, h->track_pending(h->track_cur), h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return RBPF_OK;
+}
+static int track_record(rbpf_handle* h, bool implicit) {
+    int t;
+    const int rc = track_take_place(h, implicit, t);
+    return rc ? rc : track_queue(h, t);
 }
 
 extern "C" {
@@ -203,6 +219,11 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
                 for (auto& ev : h->ring[k][e]) HIP_TRY(h, h->events.create(&ev, hipEventDisableSystemFence));
                 h->begin_used[k].assign(rbpf_handle::RING, nullptr);
             }
+        for (int e = 0; e < 2; ++e) {
+            h->rs_mid[e].resize(rbpf_handle::RING);
+            for (auto& ev : h->rs_mid[e]) HIP_TRY(h, h->events.create(&ev, hipEventDisableSystemFence));
+        }
+        h->rs_split.assign(rbpf_handle::RING, 0);
         const size_t P = v.P, LL = (size_t)v.L * v.L, cells = (size_t)dim * dim;
         uint32_t* d_lut; ALLOC(h, d_lut, h->h_lut.size()); v.lut = d_lut;
         HIP_TRY(h, hipMemcpy(d_lut, h->h_lut.data(), h->h_lut.size() * 4, hipMemcpyHostToDevice));
@@ -263,6 +284,12 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
             v.weight_entry_f64 = env_is("RBPF_WEIGHT_ENTRY", "f64") ? 1 : 0;   // rbpf_weight_samples runs the float64 kernel (comparison)
             v.ndt_refine = h->cfg.ndt_refine;
             h->dedup_enabled = !env_is("RBPF_MATCH_DEDUP", "0");   // "0": every particle runs the matcher, duplicates included (tests)
+            {   // rbpf_scan_update holds its map update back for the resample where that pays (rbpf_host.h: hold_back)
+                int cus = 0;
+                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 1; }
+                h->skip_discarded = !env_is("RBPF_SKIP_DISCARDED", "0");   // "0": the held-back map update leaves nobody out (A/B runs, tests)
+                h->hold_back = getenv("RBPF_SKIP_DISCARDED") ? true : (long long)P > 4LL * cus;
+            }
         }
         ALLOC(h, v.dup_of, P); v.dups_valid = 0;
         ALLOC(h, h->d_last_xy, 2 * (size_t)c.max_beams); ALLOC(h, h->d_tmp_sel, 2 * (size_t)c.max_beams);
@@ -280,7 +307,9 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
             ALLOC(h, r.T, P); ALLOC(h, r.idx, P); ALLOC(h, r.did, 1); ALLOC(h, r.slot2, P); ALLOC(h, r.dead_list, P);
             ALLOC(h, r.jobs, 2 * P); ALLOC(h, r.n_jobs, 2); ALLOC(h, r.pending_free, (size_t)v.pool_tiles); ALLOC(h, r.n_pending, 1);
             ALLOC(h, r.px2, P); ALLOC(h, r.py2, P); ALLOC(h, r.pth2, P); ALLOC(h, r.cov2, 9 * P); ALLOC(h, r.w2, P);
+            ALLOC(h, r.skip, P); ALLOC(h, r.keep, P); ALLOC(h, r.plan, 2);
             HIP_TRY(h, hipMemset(r.n_pending, 0, 4)); HIP_TRY(h, hipMemset(r.n_jobs, 0, 8)); HIP_TRY(h, hipMemset(r.did, 0, 4));
+            HIP_TRY(h, hipMemset(r.skip, 0, P)); HIP_TRY(h, hipMemset(r.plan, 0, 8));
         }
         HIP_TRY(h, hipMemset(v.pool, 0, (size_t)v.pool_tiles * cells));
         HIP_TRY(h, hipMemset(v.px, 0, P * 8)); HIP_TRY(h, hipMemset(v.py, 0, P * 8)); HIP_TRY(h, hipMemset(v.pth, 0, P * 8));
@@ -316,7 +345,8 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
 // alone: it belongs to the caller and may already be gone when a late destructor runs.
 int rbpf_destroy(rbpf_handle* h) {
     if (!h) return RBPF_OK;
-    ON_DEVICE(h);
+    ON_DEVICE_HELD(h);
+    h->mu_pending = false;                                                                // a held-back map update is dropped with the maps
     if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError();          // nullptr: a borrowed null stream
     h->each_staging([](Staging& s) { if (s.wait() != hipSuccess) (void)hipGetLastError(); });
     if (h->ev_weights_valid && hipEventSynchronize(h->ev_weights) != hipSuccess) (void)hipGetLastError();
@@ -399,7 +429,7 @@ int rbpf_get_kernel_ms(rbpf_handle* h, int32_t which, double* out_ms, int32_t ca
     for (int i = 0; i < n && m < cap; ++i) {
         int slot = (first + i) % rbpf_handle::RING;
         float ms = 0;
-        if (hipEventElapsedTime(&ms, h->begin_used[which][slot], h->ring[which][1][slot]) != hipSuccess) { (void)hipGetLastError(); continue; }
+        if (h->family_ms(which, slot, &ms) != hipSuccess) { (void)hipGetLastError(); continue; }
         if (out_ms) out_ms[m] = ms;
         ++m;
     }
@@ -433,13 +463,14 @@ int rbpf_get_counters(rbpf_handle* h, rbpf_counters* out) {
         c.map_events = st[ST_MAP_EVENTS]; c.map_event_overflows = st[ST_EV_OVERFLOWS];
     }
     c.map_windows = st[ST_MAP_WINDOWS];
+    c.map_updates_skipped = st[ST_MU_SKIPPED];
     if (h->profiling) {
         double* dst[5] = {&c.ms_raycast, &c.ms_weight, &c.ms_resample, &c.ms_match, &c.ms_ndt};
         for (int k = 0; k < 5; ++k) {
             if (h->ring_n[k] == 0) continue;
             int slot = (h->ring_n[k] - 1) % rbpf_handle::RING;
             float ms = 0;
-            if (hipEventElapsedTime(&ms, h->begin_used[k][slot], h->ring[k][1][slot]) == hipSuccess) *dst[k] = ms;
+            if (h->family_ms(k, slot, &ms) == hipSuccess) *dst[k] = ms;
         }
         (void)hipGetLastError();
     }
@@ -539,8 +570,8 @@ int rbpf_weight_samples(rbpf_handle* h, const double* guesses, const double* prs
 }
 
 // ---- a5 test entry --------------------------------------------------------------------------------------
-static int run_map_update(rbpf_handle* h, const uint8_t* d_bad = nullptr) {
-    DevView& v = h->v;
+// the map-update chain on view v: the handle's own, or that with the list of the particles the coming resample keeps
+static int run_map_update(rbpf_handle* h, const DevView& v, const uint8_t* d_bad = nullptr) {
     // The map update's timing events ride on the first kernel's dispatch (its own start and end: the dominant kernel, without
     // the follow-up launch that usually finds nothing to do) - two event records and their barriers less in the stream per step.
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -551,9 +582,19 @@ static int run_map_update(rbpf_handle* h, const uint8_t* d_bad = nullptr) {
         h->prof_end(0);
     }
     HIP_TRY(h, hipGetLastError());
-    h->scan_updates++;
     return RBPF_OK;
 }
+
+// what rbpf_scan_update held back, with view v: the map update with the NaN-branch increments, then the step's trajectory record
+static int launch_held_map_update(rbpf_handle* h, const DevView& v) {
+    h->mu_pending = false;
+    int rc = run_map_update(h, v, h->d_bad);
+    if (rc) return rc;
+    rc = track_queue(h, h->mu_pending_rec);
+    h->mu_pending_rec = -1;
+    return rc;
+}
+static int flush_map_update(rbpf_handle* h) { return h->mu_pending ? launch_held_map_update(h, h->v) : RBPF_OK; }
 
 int rbpf_map_update(rbpf_handle* h, const double* poses) {
     if (!h) return RBPF_EINVAL;
@@ -572,8 +613,9 @@ int rbpf_map_update(rbpf_handle* h, const double* poses) {
         HIP_TRY(h, hipMemcpyAsync(v.upd_pose + P, v.py, P * 8, hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(v.upd_pose + 2 * P, v.pth, P * 8, hipMemcpyDeviceToDevice, h->stream));
     }
-    int rc = run_map_update(h);
+    int rc = run_map_update(h, h->v);
     if (rc) return rc;
+    h->scan_updates++;
     return check_device_error(h);
 }
 
@@ -609,7 +651,15 @@ static int run_matcher(rbpf_handle* h, int32_t adj, const double* last_scan_xy, 
 int rbpf_scan_update(rbpf_handle* h, int32_t adj, const double* last_scan_xy, int32_t n_last,
                      const double* match_override, const double* guesses) {
     int rc = rbpf_scan_update_begin(h, adj, last_scan_xy, n_last, match_override, guesses);
-    return rc ? rc : rbpf_scan_update_end(h);
+    if (rc || !h->map_updates || !h->hold_back) return rc ? rc : rbpf_scan_update_end(h);
+    // The second half waits for the next call.  The weights are final here (but for the NaN branch), and they decide whom a
+    // resample that follows discards: that call launches the map update behind its plan, without those particles; any other
+    // call launches it whole before it does anything else (ON_DEVICE).  What the host alone keeps of the step changes now.
+    h->scan_begun = false;
+    h->scan_updates++;
+    h->mu_pending = true; h->mu_pending_rec = -1;
+    if (h->track_on && (h->track_flags & RBPF_TRACK_SCAN)) return track_take_place(h, true, h->mu_pending_rec);
+    return RBPF_OK;
 }
 
 // first half: scan matcher, proposal, weighting, moments (robot.py:62-114); the weights are final here unless a
@@ -665,8 +715,9 @@ int rbpf_scan_update_end(rbpf_handle* h) {
     } else {
         // HybridMap.update at the new mean pose (robot.py:115), then - in the same launch - the robot.py:73-78 weight
         // increment of the particles on the NaN-covariance branch, on their updated maps
-        const int rc = run_map_update(h, h->d_bad);
+        const int rc = run_map_update(h, h->v, h->d_bad);
         if (rc) return rc;
+        h->scan_updates++;
     }
     if (h->track_on && (h->track_flags & RBPF_TRACK_SCAN)) return track_record(h, true);
     return RBPF_OK;
@@ -714,6 +765,7 @@ int rbpf_set_map_updates(rbpf_handle* h, int32_t on) {
 
 int rbpf_get_map_update_workgroups(rbpf_handle* h, int32_t* n) {
     if (!h || !n) return RBPF_EINVAL;
+    ON_DEVICE(h);                                   // (the number is known once the update is launched: a held-back one is, here)
     *n = h->ev_workgroups;
     return RBPF_OK;
 }
@@ -852,9 +904,27 @@ static void swap_state_buffers(rbpf_handle* h) {
 // (identity if nothing was resampled; arrivals are their own representatives)
 static int resample_local(rbpf_handle* h, const double* d_w, double u, double spread) {
     DevView& v = h->v;
-    h->prof_begin(2);
-    launch_resample_local(v, h->rs, d_w, u, spread, h->stream);
-    h->prof_end(2);
+    if (h->mu_pending) {
+        // (rbpf_resample behind rbpf_scan_update) the plan, the held-back map update without the particles the plan discards, the
+        // plan once more - it returns at once unless a particle on the NaN branch made the first one wait -, copies and release.
+        // The update runs on the view from before the swap, with the three pointers that name the particles it leaves out.
+        h->prof_begin(2);
+        launch_resample_plan_early(v, h->rs, h->d_bad, h->skip_discarded ? 1 : 0, u, spread, h->stream);
+        h->prof_pause(2);
+        HIP_TRY(h, hipGetLastError());
+        DevView mv = v;
+        mv.mu_skip = h->rs.skip; mv.mu_keep = h->rs.keep; mv.mu_n_keep = h->rs.plan;
+        const int rc = launch_held_map_update(h, mv);
+        if (rc) return rc;
+        h->prof_resume(2);
+        launch_resample_plan_late(v, h->rs, u, spread, h->stream);
+        launch_resample_copies(v, h->rs, h->stream);
+        h->prof_end(2);
+    } else {
+        h->prof_begin(2);
+        launch_resample_local(v, h->rs, d_w, u, spread, h->stream);
+        h->prof_end(2);
+    }
     HIP_TRY(h, hipGetLastError());
     swap_state_buffers(h);
     if (h->track_on) {                              // pending' = pending o ancestors where the device's flag says a resample happened
@@ -869,10 +939,13 @@ static int resample_local(rbpf_handle* h, const double* d_w, double u, double sp
 
 int rbpf_resample(rbpf_handle* h, double u, int32_t* idx_out, int32_t* did_resample) {
     if (!h) return RBPF_EINVAL;
-    ON_DEVICE(h);
+    ON_DEVICE_HELD(h);                                  // a held-back map update goes between this call's own launches (resample_local)
     DevView& v = h->v;
     if (u != u) u = internal_uniform(h);
-    if (!(u >= 0.0 && u < 1.0)) return fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
+    if (!(u >= 0.0 && u < 1.0)) {
+        const int rc = flush_map_update(h);
+        return rc ? rc : fail(h, RBPF_EINVAL, "u must lie in [0, 1)");
+    }
     int rc = resample_local(h, v.weight, u, h->cfg.resample_spread);
     if (rc) return rc;
     if (idx_out) HIP_TRY(h, hipMemcpyAsync(idx_out, h->rs.idx, (size_t)v.P * 4, hipMemcpyDeviceToHost, h->stream));

@@ -163,6 +163,15 @@ struct rbpf_handle {
     unsigned long long resample_draws = 0;
     int ev_workgroups = 0;                                    // workgroups of the event-walk kernel in the last map update (0: it did not run); rbpf_get_map_update_workgroups
     bool map_updates = true;                                  // rbpf_set_map_updates: off = localization, the maps stay as they are
+    // rbpf_scan_update holds its map update back (with the NaN-branch increments and the step's own trajectory record, whose place
+    // in the log, mu_pending_rec, is taken at the call; -1: none) until the next call: rbpf_resample launches it behind its plan,
+    // without the particles the plan discards; every other entry point launches it whole, first thing (ON_DEVICE)
+    bool mu_pending = false; int mu_pending_rec = -1;
+    // Holding back pays where leaving a tenth of the particles out saves rounds of the map kernel over the CUs: measured a loss
+    // at four particles per CU (1024: the map kernel's four rounds stay four, the second plan launch and the list cost 8 us), a gain
+    // at sixteen and forty.  hold_back: more than four particles per CU, or RBPF_SKIP_DISCARDED set (tests, A/B
+    // runs: 1 holds back whatever the size, 0 does too and leaves nobody out - the same order of launches)
+    bool hold_back = false, skip_discarded = true;
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
     std::vector<hipEvent_t> ring[N_KERN][2];
@@ -170,10 +179,23 @@ struct rbpf_handle {
     std::vector<hipEvent_t> begin_used[N_KERN];     // the event that marks a launch's start: its own, or the previous family's end
     hipEvent_t last_end = nullptr;
     bool timed(int k) const { return (prof_mask >> k) & 1u; }
-    void prof_begin(int k) { if (!timed(k)) return; hipEvent_t e = ring[k][0][ring_n[k] % RING]; (void)hipEventRecord(e, stream); begin_used[k][ring_n[k] % RING] = e; }
+    void prof_begin(int k) { if (!timed(k)) return; hipEvent_t e = ring[k][0][ring_n[k] % RING]; (void)hipEventRecord(e, stream); begin_used[k][ring_n[k] % RING] = e; if (k == 2) rs_split[ring_n[k] % RING] = 0; }
     // the previous timed family ended right before this one starts (nothing enqueued in between): one record serves both
     void prof_begin_chained(int k) { if (!timed(k)) return; if (!last_end) { prof_begin(k); return; } begin_used[k][ring_n[k] % RING] = last_end; }
     void prof_end(int k) { if (!timed(k)) return; last_end = ring[k][1][ring_n[k] % RING]; (void)hipEventRecord(last_end, stream); ring_n[k]++; }
+    // a resample whose launches stand on both sides of a map update (mu_pending) is still one entry of family 2: the time from
+    // its begin to the pause plus the time from the resume to its end
+    std::vector<hipEvent_t> rs_mid[2]; std::vector<char> rs_split;
+    void prof_pause(int k) { if (!timed(k)) return; const int slot = ring_n[k] % RING; (void)hipEventRecord(rs_mid[0][slot], stream); rs_split[slot] = 1; }
+    void prof_resume(int k) { if (!timed(k)) return; (void)hipEventRecord(rs_mid[1][ring_n[k] % RING], stream); }
+    hipError_t family_ms(int k, int slot, float* ms) {
+        if (k != 2 || !rs_split[slot]) return hipEventElapsedTime(ms, begin_used[k][slot], ring[k][1][slot]);
+        float a = 0, b = 0;
+        hipError_t e = hipEventElapsedTime(&a, begin_used[k][slot], rs_mid[0][slot]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&b, rs_mid[1][slot], ring[k][1][slot]);
+        *ms = a + b;
+        return e;
+    }
     // a family that is one kernel: its timing events ride on the dispatch and take the kernel's own start and end (no event
     // records in the stream).  False, and both null, if the family is not timed.
     bool prof_take(int k, hipEvent_t& t0, hipEvent_t& t1) {

@@ -82,6 +82,11 @@ struct DevView {
     double*  prop_samp;                // [P][256] its K samples: cos, sin, pose, motion probability, single-precision frame
     int32_t* mu_fallback;              // [P] != 0: the map-update kernel that ran first gave the particle back to the next one
     MapKernelMode mu_mode;             // which map-update kernels run (RBPF_MAP_KERNEL)
+    // the particles a map update leaves out (the update that rbpf_resample launches behind its plan: DESIGN.md 3.4); all three
+    // null: nobody, the list is the identity
+    const uint8_t* mu_skip;            // [P] != 0: the coming resample discards the particle, no kernel of the chain touches it
+    const int32_t* mu_keep;            // [*mu_n_keep] the other particles, ascending: what a position of the event walk's queue stands for
+    const int32_t* mu_n_keep;          // [1]
     uint32_t* ev_queue;                // [2] the event-walk kernel's particle queue: draws of this launch, workgroups that have left; zero between launches (the kernel re-arms it)
     int ev_resident, ev_grid;          // 1: resident workgroups draw particles from ev_queue (0, RBPF_EV_RESIDENT=0: one workgroup per particle); > 0: cap on their number (RBPF_EV_GRID, tests)
     uint32_t* ndt_occ; double* ndt_aux; // NDT stage: the matcher's staged field per particle, its grid optimum (kernels_match.hip)
@@ -101,13 +106,15 @@ struct ResampleBuffers {
     int32_t *n_jobs;                   // [2] job count, queue head
     int32_t *pending_free, *n_pending; // [pool_tiles], [1]
     double *px2, *py2, *pth2, *cov2, *w2;
+    uint8_t* skip; int32_t* keep;      // [P], [P] DevView::mu_skip, mu_keep of the map update between the two plan launches
+    int32_t* plan;                     // [2] that list's length; 1: the first plan launch made the plan, 0: the second one has to
 };
 
 enum { ST_RAY_CELLS = 0, ST_CELLS_WRITTEN = 1, ST_GATHERS = 2, ST_SLOW_CELLS = 3,
        ST_COPIES = 4, ST_COPY_BYTES = 5, ST_WINDOW_FALLBACKS = 6, ST_FALLBACK_REASONS = 7,
        /* 8..15: phase stamps of a -DRBPF_STAMPS build */
        ST_NDT_RUNS = 16, ST_NDT_EVALS = 17, ST_NDT_ACCEPTED = 18, ST_MATCH_SHARED = 19, ST_MAP_WINDOWS = 20,
-       ST_FB_BOUND = 21, ST_FB_TABLES = 22, ST_MAP_EVENTS = 23, ST_EV_OVERFLOWS = 24, ST_COUNT = 28 };   // ST_FALLBACK_REASONS (7) counts reason 1 (geometry / index map)
+       ST_FB_BOUND = 21, ST_FB_TABLES = 22, ST_MAP_EVENTS = 23, ST_EV_OVERFLOWS = 24, ST_MU_SKIPPED = 25, ST_COUNT = 28 };   // ST_FALLBACK_REASONS (7) counts reason 1 (geometry / index map)
 
 // map rendering (kernels_render.hip): one workgroup per job, up to 16 storage rows x 256 storage columns of one lattice tile
 struct RenderJob {
@@ -388,6 +395,13 @@ void launch_imu_update(const DevView& v, int model, double d0, double d1, double
 void launch_resample_indices(int P, const double* d_w, double u, double spread, int32_t* d_T, int32_t* d_idx,
                              int32_t* d_did, int32_t* d_err, hipStream_t s);
 void launch_resample_local(const DevView& v, const ResampleBuffers& b, const double* d_w, double u, double spread, hipStream_t s);
+// the same in three pieces, for a map update that waits between them (rbpf_resample behind rbpf_scan_update): the plan from the
+// weights as they are - unless d_bad marks a particle whose weight the map update still changes - with the particles that update
+// may leave out (leave_out == 0: nobody); behind the update the plan once more, which returns at once if the first one stands;
+// the copies and the release
+void launch_resample_plan_early(const DevView& v, const ResampleBuffers& b, const uint8_t* d_bad, int leave_out, double u, double spread, hipStream_t s);
+void launch_resample_plan_late(const DevView& v, const ResampleBuffers& b, double u, double spread, hipStream_t s);
+void launch_resample_copies(const DevView& v, const ResampleBuffers& b, hipStream_t s);
 void launch_export_weights(const DevView& v, double* d_out, int n_global, const uint8_t* d_bad, hipStream_t s);
 void launch_gather_meta(const DevView& v, const int32_t* d_local, int n, int32_t* d_out, hipStream_t s);
 void launch_pack(const DevView& v, const void* d_jobs, int n_jobs, void* d_buf, hipStream_t s);

@@ -382,6 +382,10 @@ class ParticleEngine:
 
     # -- full step -----------------------------------------------------------------------------------
     def scan_update(self, adj: bool = False, last_scan_xy=None, match_override=None, guesses=None):
+        """Robot.map_update for every particle (rbpf_scan_update).  In filters of more than four particles per CU of the device
+        the library holds the map update back until the next call:
+        resample() / resample_async() right behind it launch it without the particles they discard (counters()
+        ["map_updates_skipped"]); any other call launches it whole first, so every result is what it would be without."""
         ls = None if last_scan_xy is None else _f64(last_scan_xy).reshape(-1, 2)
         mo = None if match_override is None else _f64(match_override).reshape(self.P, 13)
         gs = None if guesses is None else _f64(guesses).reshape(self.P, self.K, 3)

@@ -153,6 +153,10 @@ class ParticleFilter:
         self._record(None)
 
     def map_update(self, ranges, last_scan_xy=None, adj: bool = False):          # main.py:157,159
+        """A large filter's engine holds the step's map update back for the resample that follows, which leaves out the particles it
+        discards (ParticleEngine.scan_update).  With history="device" nothing here touches the device in between
+        (track_info is the host's own count, keep_scans included); history="host" reads the poses back per step, which
+        launches the update whole."""
         self.engine.set_scan(ranges, self.angles)
         self.engine.scan_update(adj=adj, last_scan_xy=last_scan_xy if adj else None)
         self._record(None)
