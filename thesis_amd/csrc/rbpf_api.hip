@@ -7,9 +7,11 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <limits>
 
 #include "rbpf_host.h"
+#include "rbpf_scanbatch.h"
 
 using namespace rbpf;
 
@@ -44,6 +46,20 @@ static int flush_map_update(rbpf_handle* h);
 static int fail(rbpf_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
+}
+
+// the shared argument checks of rbpf_scanbatch.h return their message, or null
+#define ARG_TRY(h, check) do { if (const char* msg_ = (check)) return fail(h, RBPF_EINVAL, msg_); } while (0)
+// an entry point that reads or queues behind what a half-done scan update holds
+#define MID_STEP_TRY(h, what) do { if ((h)->scan_begun) return fail(h, RBPF_ESTATE, mid_step_message(what)); } while (0)
+
+// the host outputs of a call, copied out of its scratch block behind the launch (a null one is skipped), and the wait for them
+struct Fetch { void* host; const void* dev; size_t bytes; };
+static int fetch(rbpf_handle* h, std::initializer_list<Fetch> outs) {
+    for (const Fetch& o : outs)
+        if (o.host) HIP_TRY(h, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
 }
 
 template <typename T>
@@ -1404,7 +1420,7 @@ int rbpf_map_extent(rbpf_handle* h, int32_t particle, int32_t* box4) {
     ON_DEVICE(h);
     if (!box4) return fail(h, RBPF_EINVAL, "box4 is NULL");
     if (particle < -1 || particle >= h->v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map read-out between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map read-out");
     HIP_TRY(h, h->reserve(B_RENDER_OUT, 16));
     int32_t* d_box = h->buf[B_RENDER_OUT].as<int32_t>();
     const int32_t init[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
@@ -1463,7 +1479,7 @@ int rbpf_render_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const
         return fail(h, RBPF_EINVAL, "one particle: cells only (prob, occ_frac and weights must be NULL)");
     if (particle < 0 && (cells || (!prob && !occ_frac)))
         return fail(h, RBPF_EINVAL, "whole filter: prob and / or occ_frac (cells must be NULL)");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map read-out between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map read-out");
     // particles are summed in groups of C (kernels_render.hip); the weight sum is formed in the same order
     const int P = v.P, C = std::max(8, (P + 63) / 64), ngroups = (P + C - 1) / C;
     double S = 0.0;
@@ -1612,7 +1628,7 @@ int rbpf_load_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const i
     if (!box4 || !cells) return fail(h, RBPF_EINVAL, "box4 or cells is NULL");
     if (flags & ~RBPF_LOAD_DEVICE_IN) return fail(h, RBPF_EINVAL, "unknown flags");
     if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map load between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map load");
     if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
     const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
     if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
@@ -1659,7 +1675,7 @@ int rbpf_place_map(rbpf_handle* h, int32_t particle, const int32_t* box4, const 
     if (!std::isfinite(src_pose3[0]) || !std::isfinite(src_pose3[1]) || !std::isfinite(src_pose3[2])) return fail(h, RBPF_EINVAL, "src_pose3 must be finite");
     if (dry && !warped && !covered) return fail(h, RBPF_EINVAL, "a dry run needs warped and / or covered");
     if (!dry && (particle < -1 || particle >= v.P)) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map placement between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map placement");
     if (box4[1] < box4[0] || box4[3] < box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 >= x0 and y1 >= y0");
     const long long ny = (long long)box4[3] - box4[2], ncell = ((long long)box4[1] - box4[0]) * ny;
     if (ncell > (1LL << 31)) return fail(h, RBPF_EINVAL, "box holds more than 2^31 cells");
@@ -1717,44 +1733,33 @@ int rbpf_cast_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, in
     if (!poses_n3 || !angles || !ranges) return fail(h, RBPF_EINVAL, "poses, angles or ranges is NULL");
     if (flags & ~RBPF_CAST_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
     if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (n_poses < 0 || n_beams < 1 || (long long)n_poses * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_poses >= 0, n_beams >= 1 and n_poses * n_beams < 2^31 are required");
+    ARG_TRY(h, check_counts(n_poses, 0, n_beams, 0, "n_poses >= 0, n_beams >= 1 and n_poses * n_beams < 2^31 are required"));
     if (particle < 0 && n_poses != v.P) return fail(h, RBPF_EINVAL, "particle -1 casts pose n in particle n's map: n_poses must equal n_particles");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    for (long long k = 0; k < 3LL * n_poses; ++k)
-        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    ARG_TRY(h, check_max_range(max_range));
+    ARG_TRY(h, check_poses(poses_n3, n_poses));
+    ARG_TRY(h, check_angles(angles, n_beams));
     if (n_poses == 0) return RBPF_OK;
     const bool dev_out = (flags & RBPF_CAST_DEVICE_OUT) != 0;
     const size_t rays = (size_t)n_poses * n_beams;
-    const size_t in_b = (size_t)n_poses * 32 + (size_t)n_beams * 16, out_b = dev_out ? 0 : rays * 8 + (status ? rays : 0);
-    HIP_TRY(h, h->reserve(B_CAST, in_b + out_b));
+    Carve c;                                                               // scratch: [poses] [beams] | host ranges, host status
+    const size_t pose_at = c.pack((size_t)n_poses * 32), beam_at = c.pack((size_t)n_beams * 16), in_b = c.total();
+    const size_t range_at = c.pack(dev_out ? 0 : rays * 8), status_at = c.pack(dev_out || !status ? 0 : rays);
+    HIP_TRY(h, h->reserve(B_CAST, c.total()));
     const Block& d_cast = h->buf[B_CAST];
     HIP_TRY(h, h->stage[S_CAST].begin(in_b));                              // the last upload may still read it
-    double* st = reinterpret_cast<double*>(h->stage[S_CAST].p);
-    for (int n = 0; n < n_poses; ++n) {                                    // host libm, as rbpf_set_scan
-        st[4 * (size_t)n] = poses_n3[3 * (size_t)n]; st[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
-        st[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); st[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
-    }
-    double* sb = st + 4 * (size_t)n_poses;
-    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
+    stage_beam2(stage_pose4(h->stage[S_CAST].as<double>(), poses_n3, n_poses), angles, n_beams);
     HIP_TRY(h, h->stage[S_CAST].upload(d_cast.p, in_b, h->stream));
     CastArgs a;
-    a.pose4 = d_cast.as<const double>();
-    a.beam2 = a.pose4 + 4 * (size_t)n_poses;
+    a.pose4 = d_cast.as<const double>(pose_at);
+    a.beam2 = d_cast.as<const double>(beam_at);
     a.n_poses = n_poses; a.B = n_beams; a.particle = particle;
     a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as lookup_cell_fast forms it
     a.tlim = max_range * a.inv; a.max_range = max_range;
-    a.ranges = dev_out ? ranges : d_cast.as<double>(in_b);
-    a.status = !status ? nullptr : dev_out ? status : d_cast.p + in_b + rays * 8;
+    a.ranges = dev_out ? ranges : d_cast.as<double>(range_at);
+    a.status = !status ? nullptr : dev_out ? status : d_cast.as<uint8_t>(status_at);
     launch_cast_scans(v, a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    HIP_TRY(h, hipMemcpyAsync(ranges, a.ranges, rays * 8, hipMemcpyDeviceToHost, h->stream));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, a.status, rays, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{ranges, a.ranges, rays * 8}, {status, a.status, rays}});
 }
 
 // ---- global localization (kernels_locate.hip) -------------------------------------------------------------------------------
@@ -1776,7 +1781,7 @@ int rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
         return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
     for (int b = 0; b < n_beams; ++b)
         if (!std::isfinite(ranges[b]) || !std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "ranges and angles must be finite");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "scan search between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "scan search");
     if (ncell == 0) return RBPF_OK;
     const rbpf_config& c = h->cfg;
     LocateArgs a;
@@ -1794,10 +1799,9 @@ int rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     const long long runs = std::max(1LL, std::min<long long>(n_rot, (8192 + word_waves - 1) / word_waves));
     a.rpw = (int)((n_rot + runs - 1) / runs);
     const bool dev_out = (flags & RBPF_LOCATE_DEVICE_OUT) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t in_b = ((size_t)n_rot + nb) * 16, offs_b = pad((size_t)n_rot * nb * 4), field_b = pad((size_t)a.rows * a.W * 8);
-    const size_t cand_b = pad((size_t)words * 4), packed_b = pad((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 4 * (rot ? 2 : 1);
-    const size_t total = pad(in_b) + offs_b + field_b + 2 * cand_b + 256 + packed_b + out_b;
+    const size_t in_b = ((size_t)n_rot + nb) * 16, offs_b = pad256((size_t)n_rot * nb * 4), field_b = pad256((size_t)a.rows * a.W * 8);
+    const size_t cand_b = pad256((size_t)words * 4), packed_b = pad256((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 4 * (rot ? 2 : 1);
+    const size_t total = pad256(in_b) + offs_b + field_b + 2 * cand_b + 256 + packed_b + out_b;
     if (total > ((size_t)2 << 30)) return fail(h, RBPF_ENOMEM, "box, beams and rotations need more than 2 GiB of scratch: search a smaller box");
     HIP_TRY(h, h->reserve(B_LOCATE, total));
     const Block& d = h->buf[B_LOCATE];
@@ -1814,7 +1818,7 @@ int rbpf_locate_scan(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
             ++k;
         }
     HIP_TRY(h, h->stage[S_LOCATE].upload(d.p, in_b, h->stream));
-    size_t at = pad(in_b);
+    size_t at = pad256(in_b);
     a.cs = d.as<const double>(); a.bxy = a.cs + 2 * (size_t)n_rot;
     a.offs = d.as<int32_t>(at); at += offs_b;
     a.field = d.as<uint2>(at); at += field_b;
@@ -1865,7 +1869,7 @@ int rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, con
     }
     const double reach = ceil(far * inv) + 1.0;                            // no point lands farther from its cell
     if (!(reach >= 1.0) || reach > 16384.0) return fail(h, RBPF_EINVAL, "the point set reaches more than 16383 cells from its origin");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "alignment between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "alignment");
     if (ncell == 0) return RBPF_OK;
     LocateArgs f;                                                          // the field: locate's, over the box grown by M
     AlignArgs a;
@@ -1878,10 +1882,9 @@ int rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, con
     const long long runs = std::max(1LL, std::min<long long>(r_count, (8192 + word_waves - 1) / word_waves));
     a.rpw = (int)((r_count + runs - 1) / runs);
     const bool dev_out = (flags & RBPF_ALIGN_DEVICE_OUT) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t in_b = ((size_t)r_count + np) * 16, offs_b = pad((size_t)r_count * np * 4), field_b = pad((size_t)f.rows * f.W * 8);
-    const size_t packed_b = pad((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 8;
-    const size_t total = pad(in_b) + offs_b + field_b + packed_b + out_b;
+    const size_t in_b = ((size_t)r_count + np) * 16, offs_b = pad256((size_t)r_count * np * 4), field_b = pad256((size_t)f.rows * f.W * 8);
+    const size_t packed_b = pad256((size_t)ncell * 4), out_b = dev_out ? 0 : (size_t)ncell * 8;
+    const size_t total = pad256(in_b) + offs_b + field_b + packed_b + out_b;
     if (total > ((size_t)2 << 30)) return fail(h, RBPF_ENOMEM, "box, points and rotations need more than 2 GiB of scratch: search a smaller box or window");
     HIP_TRY(h, h->reserve(B_ALIGN, total));
     const Block& d = h->buf[B_ALIGN];
@@ -1895,7 +1898,7 @@ int rbpf_align_points(rbpf_handle* h, int32_t particle, const int32_t* box4, con
     memcpy(sp, occ_xy, (size_t)n_occ * 16);
     if (n_free > 0) memcpy(sp + 2 * (size_t)n_occ, free_xy, (size_t)n_free * 16);
     HIP_TRY(h, h->stage[S_ALIGN].upload(d.p, in_b, h->stream));
-    size_t at = pad(in_b);
+    size_t at = pad256(in_b);
     a.cs = d.as<const double>(); a.pxy = a.cs + 2 * (size_t)r_count;
     a.offs = d.as<int32_t>(at); at += offs_b;
     a.field = f.field = d.as<uint2>(at); at += field_b;
@@ -1923,15 +1926,12 @@ int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int
     if (!poses_n3 || !angles || !value_tab || !gain) return fail(h, RBPF_EINVAL, "poses, angles, value_tab or gain is NULL");
     if (flags & ~RBPF_GAIN_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
     if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (n_poses < 1 || n_beams < 1 || (long long)n_poses * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_poses >= 1, n_beams >= 1 and n_poses * n_beams < 2^31 are required");
+    ARG_TRY(h, check_counts(n_poses, 1, n_beams, 0, "n_poses >= 1, n_beams >= 1 and n_poses * n_beams < 2^31 are required"));
     const long long results = (long long)(particle >= 0 ? 1 : v.P) * n_poses;
     if (results >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_particles * n_poses < 2^31 is required with particle -1");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    for (long long k = 0; k < 3LL * n_poses; ++k)
-        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    ARG_TRY(h, check_max_range(max_range));
+    ARG_TRY(h, check_poses(poses_n3, n_poses));
+    ARG_TRY(h, check_angles(angles, n_beams));
     const int nv = v.cc.vmax - v.cc.vmin + 1;                              // one entry per lattice value
     if (v.cc.vmin > 0 || v.cc.vmax < 0 || nv > 256) return fail(h, RBPF_EINVAL, "the lattice values must include 0");
     for (int k = 0; k < nv; ++k)
@@ -1943,39 +1943,29 @@ int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int
     if (!(2.0 * reach + 1.0 <= 1024.0))
         return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window of more than 1024 cells: the largest admissible "
                                     "max_range is " + std::to_string(509.0 / a.inv) + " m (ceil(max_range * cells per metre) <= 509)");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "view gain between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "view gain");
     a.M = (int)reach; a.W = (2 * a.M + 1 + 31) / 32 + 1;
     const bool dev_out = (flags & RBPF_GAIN_DEVICE_OUT) != 0;
     const size_t nres = (size_t)results;
-    const size_t in_b = (size_t)n_poses * 32 + (size_t)n_beams * 16 + (size_t)nv * 4, out_at = (in_b + 7) & ~(size_t)7;
-    const size_t out_b = dev_out ? 0 : nres * (8 + (seen ? 4 : 0) + (unknown ? 4 : 0));
-    HIP_TRY(h, h->reserve(B_GAIN, out_at + out_b));
+    Carve c;                                                               // scratch: [poses] [beams] [table] | host gain, seen, unknown
+    const size_t pose_at = c.pack((size_t)n_poses * 32), beam_at = c.pack((size_t)n_beams * 16), tab_at = c.pack((size_t)nv * 4), in_b = c.close();
+    const size_t gain_at = c.pack(dev_out ? 0 : nres * 8), seen_at = c.pack(dev_out || !seen ? 0 : nres * 4);
+    const size_t unknown_at = c.pack(dev_out || !unknown ? 0 : nres * 4);
+    HIP_TRY(h, h->reserve(B_GAIN, c.total()));
     const Block& d = h->buf[B_GAIN];
     HIP_TRY(h, h->stage[S_GAIN].begin(in_b));                              // the last upload may still read it
-    double* st = reinterpret_cast<double*>(h->stage[S_GAIN].p);
-    for (int n = 0; n < n_poses; ++n) {                                    // host libm, as rbpf_cast_scans
-        st[4 * (size_t)n] = poses_n3[3 * (size_t)n]; st[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
-        st[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); st[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
-    }
-    double* sb = st + 4 * (size_t)n_poses;
-    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
-    memcpy(sb + 2 * (size_t)n_beams, value_tab, (size_t)nv * 4);
+    memcpy(stage_beam2(stage_pose4(h->stage[S_GAIN].as<double>(), poses_n3, n_poses), angles, n_beams), value_tab, (size_t)nv * 4);
     HIP_TRY(h, h->stage[S_GAIN].upload(d.p, in_b, h->stream));
-    a.pose4 = d.as<const double>();
-    a.beam2 = a.pose4 + 4 * (size_t)n_poses;
-    a.table = reinterpret_cast<const int32_t*>(a.beam2 + 2 * (size_t)n_beams);
+    a.pose4 = d.as<const double>(pose_at);
+    a.beam2 = d.as<const double>(beam_at);
+    a.table = d.as<const int32_t>(tab_at);
     a.n_poses = n_poses; a.B = n_beams; a.nv = nv; a.particle = particle;
-    a.gain = dev_out ? gain : d.as<int64_t>(out_at);
-    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(out_at + nres * 8);
-    a.unknown = !unknown ? nullptr : dev_out ? unknown : d.as<int32_t>(out_at + nres * (8 + (seen ? 4 : 0)));
+    a.gain = dev_out ? gain : d.as<int64_t>(gain_at);
+    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(seen_at);
+    a.unknown = !unknown ? nullptr : dev_out ? unknown : d.as<int32_t>(unknown_at);
     launch_view_gain(v, a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    HIP_TRY(h, hipMemcpyAsync(gain, a.gain, nres * 8, hipMemcpyDeviceToHost, h->stream));
-    if (seen) HIP_TRY(h, hipMemcpyAsync(seen, a.seen, nres * 4, hipMemcpyDeviceToHost, h->stream));
-    if (unknown) HIP_TRY(h, hipMemcpyAsync(unknown, a.unknown, nres * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{gain, a.gain, nres * 8}, {seen, a.seen, nres * 4}, {unknown, a.unknown, nres * 4}});
 }
 
 }  // extern "C"
@@ -2048,7 +2038,7 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
         if (!std::isfinite(start_xy[k])) return fail(h, RBPF_EINVAL, "start coordinates must be finite");
     for (long long k = 0; k < 2LL * ng; ++k)
         if (!std::isfinite(goal_xy[k])) return fail(h, RBPF_EINVAL, "goal coordinates must be finite");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "travel cost between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "travel cost");
 
     TravelArgs a;
     a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
@@ -2059,12 +2049,11 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     const bool dev_out = (flags & RBPF_TRAVEL_DEVICE_OUT) != 0;
     const int np_all = all ? v.P : 1;
     const long long nblk = (long long)a.nbx * a.nby;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     a.cw = a.nby * 64 + 2;
-    const size_t cost_b = pad((size_t)(a.nbx * 64LL + 2) * a.cw * 4), t_b = pad((size_t)nblk * 512), dirty_b = pad((size_t)nblk);
+    const size_t cost_b = pad256((size_t)(a.nbx * 64LL + 2) * a.cw * 4), t_b = pad256((size_t)nblk * 512), dirty_b = pad256((size_t)nblk);
     const size_t per = cost_b + t_b + 2 * dirty_b;
-    const size_t in_b = pad(((size_t)n_start + ng) * 8);
-    const size_t out_b = dev_out ? 0 : pad(cost ? (size_t)ncell * 4 : 0) + pad(clearance ? (size_t)ncell * 2 : 0) + pad((size_t)np_all * ng * 4);
+    const size_t in_b = pad256(((size_t)n_start + ng) * 8);
+    const size_t out_b = dev_out ? 0 : pad256(cost ? (size_t)ncell * 4 : 0) + pad256(clearance ? (size_t)ncell * 2 : 0) + pad256((size_t)np_all * ng * 4);
     const size_t fixed = in_b + 256 + out_b;
     if (fixed + per > RELAX_SCRATCH) return fail(h, RBPF_ENOMEM, "one particle's travel cost over this box needs more than 2 GiB of scratch: use a smaller box");
     const long long batch = relax_batch(np_all, fixed, per, "RBPF_TRAVEL_BATCH");
@@ -2089,9 +2078,9 @@ int rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, cons
     size_t at = in_b + 256;
     int32_t* o_cost = nullptr; uint16_t* o_clear = nullptr; int32_t* o_goal = nullptr;
     if (!dev_out) {
-        if (cost) { o_cost = d.as<int32_t>(at); at += pad((size_t)ncell * 4); }
-        if (clearance) { o_clear = d.as<uint16_t>(at); at += pad((size_t)ncell * 2); }
-        if (ng) { o_goal = d.as<int32_t>(at); at += pad((size_t)np_all * ng * 4); }
+        if (cost) { o_cost = d.as<int32_t>(at); at += pad256((size_t)ncell * 4); }
+        if (clearance) { o_clear = d.as<uint16_t>(at); at += pad256((size_t)ncell * 2); }
+        if (ng) { o_goal = d.as<int32_t>(at); at += pad256((size_t)np_all * ng * 4); }
     } else { o_cost = cost; o_clear = clearance; o_goal = goal_cost; }
     unsigned char* work = d.p + at;
     a.cost_out = o_cost; a.clearance = o_clear;
@@ -2149,7 +2138,7 @@ int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4,
     const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2], ncell = nx * ny;
     if (nx > 32768 || ny > 32768 || ncell > (1LL << 27)) return fail(h, RBPF_EINVAL, "box must be at most 32768 cells on a side and hold at most 2^27 cells");
     if (!box_in_lattice(v, box4)) return fail(h, RBPF_EINVAL, "box leaves the tile lattice");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "frontier regions between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "frontier regions");
 
     FrontierArgs a;
     a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
@@ -2158,12 +2147,11 @@ int rbpf_frontier_regions(rbpf_handle* h, int32_t particle, const int32_t* box4,
     const bool dev_out = (flags & RBPF_FRONTIER_DEVICE_OUT) != 0, table = regions || counts;
     const int np_all = all ? v.P : 1;
     const long long nblk = (long long)a.nbx * a.nby;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     a.cw = a.nby * 64 + 2;
-    const size_t lab_b = pad((size_t)(a.nbx * 64LL + 2) * a.cw * 4), dirty_b = pad((size_t)nblk);
+    const size_t lab_b = pad256((size_t)(a.nbx * 64LL + 2) * a.cw * 4), dirty_b = pad256((size_t)nblk);
     const size_t per = lab_b * (table ? 2 : 1) + 2 * dirty_b;
-    const size_t counts_b = pad((size_t)np_all * 12), table_b = table ? pad((size_t)np_all * max_regions * 80) : 0;
-    const size_t label_b = label && !dev_out ? pad((size_t)ncell * 4) : 0;
+    const size_t counts_b = pad256((size_t)np_all * 12), table_b = table ? pad256((size_t)np_all * max_regions * 80) : 0;
+    const size_t label_b = label && !dev_out ? pad256((size_t)ncell * 4) : 0;
     const size_t fixed = 256 + counts_b + table_b + label_b;
     if (fixed + per > RELAX_SCRATCH) return fail(h, RBPF_ENOMEM, "one particle's frontier regions over this box need more than 2 GiB of scratch: use a smaller box");
     const long long batch = relax_batch(np_all, fixed, per, "RBPF_FRONTIER_BATCH");
@@ -2236,7 +2224,7 @@ int rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     if (!dev_in)
         for (long long i = 0; i < ncell; ++i)
             if (ref[i] < v.cc.vmin || ref[i] > v.cc.vmax) return fail(h, RBPF_EINVAL, "reference value outside [min_odds_emp, max_odds_occ]");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map scores between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map scores");
 
     ScoreArgs a;
     a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
@@ -2244,11 +2232,10 @@ int rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const
     a.tol = tol; a.validate = dev_in;
     const int np_all = particle < 0 ? v.P : 1;
     const size_t nblk = (size_t)a.nbx * a.nby;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // scratch: [flag] [table] [host reference] | [near rows] [block sums] [host scores]; the first three are one upload
-    const size_t tab_b = pad((size_t)nv * 4), ref_b = dev_in ? 0 : pad((size_t)ncell), in_b = 256 + tab_b + ref_b;
-    const size_t near_b = pad(nblk * BR_EDGE * 8), sums_b = pad(nblk * 16), out_n = (size_t)np_all * SCORE_FIELDS * 8;
-    HIP_TRY(h, h->reserve(B_SCORE, in_b + near_b + sums_b + (dev_out ? 0 : pad(out_n))));
+    const size_t tab_b = pad256((size_t)nv * 4), ref_b = dev_in ? 0 : pad256((size_t)ncell), in_b = 256 + tab_b + ref_b;
+    const size_t near_b = pad256(nblk * BR_EDGE * 8), sums_b = pad256(nblk * 16), out_n = (size_t)np_all * SCORE_FIELDS * 8;
+    HIP_TRY(h, h->reserve(B_SCORE, in_b + near_b + sums_b + (dev_out ? 0 : pad256(out_n))));
     const Block& d = h->buf[B_SCORE];
     Staging& st = h->stage[S_SCORE];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
@@ -2286,8 +2273,6 @@ int rbpf_score_maps(rbpf_handle* h, int32_t particle, const int32_t* box4, const
 }  // extern "C"
 
 // ---- pose estimate and trajectory log (kernels_track.hip) -------------------------------------------------------
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int check_weights_mode(rbpf_handle* h, int32_t mode, const double* weights) {
     if (mode != RBPF_W_UNIFORM && mode != RBPF_W_RESAMPLE && mode != RBPF_W_GIVEN) return fail(h, RBPF_EINVAL, "unknown weights_mode");
     if ((mode == RBPF_W_GIVEN) != (weights != nullptr)) return fail(h, RBPF_EINVAL, "weights go with RBPF_W_GIVEN, and only with it");
@@ -2527,20 +2512,16 @@ int rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, cons
     if (!poses_n3 || !ranges || !angles || !box4) return fail(h, RBPF_EINVAL, "poses, ranges, angles or box4 is NULL");
     if (!hits && !seen) return fail(h, RBPF_EINVAL, "hits and seen are both NULL");
     if (flags & ~(RBPF_BUILD_DEVICE_OUT | RBPF_BUILD_ACCUMULATE)) return fail(h, RBPF_EINVAL, "unknown flags");
-    if (n_scans < 1 || n_beams < 1 || (long long)n_scans * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_scans >= 1, n_beams >= 1 and n_scans * n_beams < 2^31 are required");
+    ARG_TRY(h, check_counts(n_scans, 1, n_beams, 0, "n_scans >= 1, n_beams >= 1 and n_scans * n_beams < 2^31 are required"));
     if (box4[1] <= box4[0] || box4[3] <= box4[2]) return fail(h, RBPF_EINVAL, "box must have x1 > x0 and y1 > y0");
     const long long nx = (long long)box4[1] - box4[0], ny = (long long)box4[3] - box4[2];
     if (nx > INT32_MAX || ny > INT32_MAX || nx > (1LL << 31) / ny)
         return fail(h, RBPF_EINVAL, "box must hold at most 2^31 cells, in fewer than 2^31 rows and columns");
     const long long ncell = nx * ny;
     if (!std::isfinite(cells_per_m) || !(cells_per_m > 0.0)) return fail(h, RBPF_EINVAL, "cells_per_m must be finite and > 0");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
-    for (long long k = 0; k < 3LL * n_scans; ++k)
-        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    ARG_TRY(h, check_ranges(max_range, min_range));
+    ARG_TRY(h, check_poses(poses_n3, n_scans));
+    ARG_TRY(h, check_angles(angles, n_beams));
     BuildArgs a;
     a.inv = cells_per_m;
     a.tlim = max_range * a.inv;
@@ -2548,37 +2529,29 @@ int rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, cons
     if (!(2.0 * reach + 1.0 <= 1024.0))
         return fail(h, RBPF_EINVAL, "max_range " + std::to_string(max_range) + " m needs a window of more than 1024 cells: the largest admissible "
                                     "max_range is " + std::to_string(509.0 / a.inv) + " m (ceil(max_range * cells per metre) <= 509)");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "map building between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "map building");
     a.M = (int)reach; a.W = (2 * a.M + 1 + 31) / 32 + 1;
     a.x0 = box4[0]; a.y0 = box4[2]; a.nx = (int)nx; a.ny = (int)ny;
     a.min_range = min_range; a.max_range = max_range;
     a.n_scans = n_scans; a.B = n_beams;
     const bool dev_out = (flags & RBPF_BUILD_DEVICE_OUT) != 0, accumulate = (flags & RBPF_BUILD_ACCUMULATE) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // scratch: [poses] [beams] [ranges] | [end cells] [host hits] [host seen]; the first three are one upload
-    const size_t nray = (size_t)n_scans * n_beams, pose_b = (size_t)n_scans * 32, beam_b = (size_t)n_beams * 16;
-    const size_t in_b = pose_b + beam_b + nray * 8, ends_b = pad(nray * 4), out_b = dev_out ? 0 : pad((size_t)ncell * 4);
-    const size_t total = pad(in_b) + ends_b + out_b * ((hits ? 1 : 0) + (seen ? 1 : 0));
-    if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "scans and box need more than 4 GiB of scratch: build fewer scans per call (RBPF_BUILD_ACCUMULATE) or a smaller box");
-    HIP_TRY(h, h->reserve(B_BUILD, total));
+    const size_t nray = (size_t)n_scans * n_beams, out_b = (size_t)ncell * 4;
+    Carve c;                                                               // scratch: [poses] [beams] [ranges] | [end cells] [host hits] [host seen]
+    const size_t pose_at = c.pack((size_t)n_scans * 32), beam_at = c.pack((size_t)n_beams * 16), range_at = c.pack(nray * 8), in_b = c.close();
+    const size_t ends_at = c.take(nray * 4), hits_at = c.take(dev_out || !hits ? 0 : out_b), seen_at = c.take(dev_out || !seen ? 0 : out_b);
+    if (c.total() > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "scans and box need more than 4 GiB of scratch: build fewer scans per call (RBPF_BUILD_ACCUMULATE) or a smaller box");
+    HIP_TRY(h, h->reserve(B_BUILD, c.total()));
     const Block& d = h->buf[B_BUILD];
     Staging& st = h->stage[S_BUILD];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
-    double* sp = reinterpret_cast<double*>(st.p);
-    for (int n = 0; n < n_scans; ++n) {                                    // host libm, as rbpf_cast_scans
-        sp[4 * (size_t)n] = poses_n3[3 * (size_t)n]; sp[4 * (size_t)n + 1] = poses_n3[3 * (size_t)n + 1];
-        sp[4 * (size_t)n + 2] = cos(poses_n3[3 * (size_t)n + 2]); sp[4 * (size_t)n + 3] = sin(poses_n3[3 * (size_t)n + 2]);
-    }
-    double* sb = sp + 4 * (size_t)n_scans;
-    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
-    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    memcpy(stage_beam2(stage_pose4(st.as<double>(), poses_n3, n_scans), angles, n_beams), ranges, nray * 8);
     HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-    a.pose4 = d.as<const double>();
-    a.beam2 = a.pose4 + 4 * (size_t)n_scans;
-    a.ranges = a.beam2 + 2 * (size_t)n_beams;
-    a.ends = d.as<uint32_t>(pad(in_b));
-    a.hits = !hits ? nullptr : dev_out ? hits : d.as<int32_t>(pad(in_b) + ends_b);
-    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(pad(in_b) + ends_b + (hits ? out_b : 0));
+    a.pose4 = d.as<const double>(pose_at);
+    a.beam2 = d.as<const double>(beam_at);
+    a.ranges = d.as<const double>(range_at);
+    a.ends = d.as<uint32_t>(ends_at);
+    a.hits = !hits ? nullptr : dev_out ? hits : d.as<int32_t>(hits_at);
+    a.seen = !seen ? nullptr : dev_out ? seen : d.as<int32_t>(seen_at);
     int32_t* const host_out[2] = {hits, seen};
     int32_t* const dev[2] = {a.hits, a.seen};
     for (int k = 0; k < 2; ++k) {
@@ -2588,20 +2561,16 @@ int rbpf_build_map(rbpf_handle* h, const double* poses_n3, int32_t n_scans, cons
     }
     launch_build_map(a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    for (int k = 0; k < 2; ++k)
-        if (dev[k]) HIP_TRY(h, hipMemcpyAsync(host_out[k], dev[k], (size_t)ncell * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{hits, a.hits, out_b}, {seen, a.seen, out_b}});
 }
 
 // ---- scan-to-map refinement (kernels_refine.hip) -------------------------------------------------------------------
 static const size_t REFINE_LDS_LIMIT = 160 * 1024 - 64;                    // dynamic LDS of the search kernel: 160 KiB less its statics
-static int refine_row_words(long long Mw) { return (int)((((2 * Mw + 1 + 31) >> 5) + 2) | 1); }
-static bool refine_substeps_ok(int32_t S) { return S == 1 || S == 2 || S == 4 || S == 8 || S == 16; }
+// rotations whose tasks fit one workgroup: its lanes over the tasks of one rotation (search_kpw)
+static int refine_fit(int substeps, int n_trans) { const int nw = 2 * n_trans + 1; return REFINE_BLOCK / (nw * refine_runs(nw, search_shift(substeps))); }
 
 int32_t rbpf_refine_max_reach(int32_t substeps, int32_t n_trans) {
-    if (!refine_substeps_ok(substeps) || n_trans < 0 || n_trans > 32) return -1;
+    if (!search_substeps_ok(substeps) || n_trans < 0 || n_trans > 32) return -1;
     const int extra = (n_trans + substeps - 1) / substeps + 2;
     int reach = -1;                                                        // the LDS need grows with Mw: the first failure ends the search
     for (int c = 0; refine_lds_bytes(c + extra, refine_row_words(c + extra)) <= REFINE_LDS_LIMIT; ++c) reach = c;
@@ -2627,40 +2596,24 @@ int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, 
     if (!poses_n3 || !ranges || !angles) return fail(h, RBPF_EINVAL, "poses, ranges or angles is NULL");
     if (!out_pose_n3 && !out_n6) return fail(h, RBPF_EINVAL, "out_pose_n3 and out_n6 are both NULL");
     if (flags & ~RBPF_REFINE_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
-    if (n_scans < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
+    ARG_TRY(h, check_counts(n_scans, 1, n_beams, 16384, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required"));
     if (particle < 0 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
-    if (!refine_substeps_ok(substeps)) return fail(h, RBPF_EINVAL, "substeps must be 1, 2, 4, 8 or 16");
-    if (n_trans < 0 || n_trans > 32) return fail(h, RBPF_EINVAL, "0 <= n_trans <= 32 is required");
-    if (n_rot < 0 || n_rot > 100) return fail(h, RBPF_EINVAL, "0 <= n_rot <= 100 is required");
-    if (!std::isfinite(rot_step) || rot_step < 0.0) return fail(h, RBPF_EINVAL, "rot_step must be finite and >= 0");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
-    for (long long k = 0; k < 3LL * n_scans; ++k)
-        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    ARG_TRY(h, check_search(substeps, n_trans, n_rot));
+    ARG_TRY(h, check_rot_step(rot_step));
+    ARG_TRY(h, check_ranges(max_range, min_range));
+    ARG_TRY(h, check_poses(poses_n3, n_scans));
+    ARG_TRY(h, check_angles(angles, n_beams));
     const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as lookup_cell_fast forms it
     const double invS = inv * (double)substeps;                            // exact: a power of two
     for (int n = 0; n < n_scans; ++n)
         for (int c = 0; c < 2; ++c)
             if (!((fabs(poses_n3[3 * (size_t)n + c]) + max_range) * invS + (double)n_trans < 1073741824.0))
                 return fail(h, RBPF_EINVAL, "(|pose| + max_range) * cells per metre * substeps + n_trans < 2^30 is required");
-    const int extra = (n_trans + substeps - 1) / substeps + 2;
-    const double reach = ceil(max_range * inv);
-    const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
-    if (!(reach <= (double)max_reach)) return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "pose refinement between rbpf_scan_update_begin and rbpf_scan_update_end");
     RefineArgs a;
-    a.N = n_scans; a.B = n_beams; a.Wt = n_trans; a.R = n_rot; a.nk = 2 * n_rot + 1;
-    a.s = substeps == 1 ? 0 : substeps == 2 ? 1 : substeps == 4 ? 2 : substeps == 8 ? 3 : 4;
-    a.Mw = (int)reach + extra; a.WW = refine_row_words(a.Mw);
-    a.invS = invS; a.min_range = min_range; a.max_range = max_range;
-    // rotations per workgroup: as many tasks as a workgroup has lanes, fewer while the grid would not fill the GPU
-    const int nw = 2 * n_trans + 1, t1 = nw * refine_runs(nw, a.s);
-    a.kpw = std::max(1, std::min(std::min(16, a.nk), REFINE_BLOCK / t1));
-    while (a.kpw > 1 && (long long)n_scans * ((a.nk + a.kpw - 1) / a.kpw) < 1024) --a.kpw;
-    if (const char* e = getenv("RBPF_REFINE_KPW")) a.kpw = std::max(1, std::min(std::min(16, a.nk), atoi(e)));   // for tests
+    const int max_reach = rbpf_refine_max_reach(substeps, n_trans), nw = 2 * n_trans + 1;
+    if (!search_setup(a, n_scans, n_beams, substeps, n_trans, n_rot, inv, min_range, max_range, max_reach, refine_fit(substeps, n_trans), "RBPF_REFINE_KPW"))
+        return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
+    MID_STEP_TRY(h, "pose refinement");
     // the field: the union of the windows, cut to the lattice grown by 2 (F = 0 farther out)
     const long long dim = v.dim, off = (long long)v.R * dim + dim / 2, edge = (long long)v.L * dim;   // mosaic X + off = a * dim + i
     long long lo[2] = {INT64_MAX, INT64_MAX}, hi[2] = {INT64_MIN, INT64_MIN};
@@ -2679,55 +2632,41 @@ int rbpf_refine_poses(rbpf_handle* h, int32_t particle, const double* poses_n3, 
     f.particle = particle; f.M = 0; f.x0 = a.fx0 = any_field ? (int)lo[0] : 0; f.y0 = a.fy0 = any_field ? (int)lo[1] : 0;
     f.rows = a.frows = any_field ? (int)ext[0] : 0; f.W = a.fW = any_field ? (int)((ext[1] + 31) / 32) : 0;
     const bool dev_out = (flags & RBPF_REFINE_DEVICE_OUT) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // scratch: [guesses] [rotations] [beams] [ranges] [centre cells] | [field] [merge words] [guess scores] [n_used] | host outputs
     const size_t N = (size_t)n_scans, nray = N * n_beams, vol = N * a.nk * nw * nw;
-    const size_t guess_b = N * 16, rot_b = N * a.nk * 32, beam_b = (size_t)n_beams * 16, cell_at = guess_b + rot_b + beam_b + nray * 8;
-    const size_t in_b = cell_at + N * 8, field_b = pad((size_t)a.frows * a.fW * 8), merge_b = pad(N * 8) + 2 * pad(N * 4);
-    const size_t pose_b = !dev_out && out_pose_n3 ? pad(N * 24) : 0, n6_b = !dev_out && out_n6 ? pad(N * 24) : 0;
-    const size_t total = pad(in_b) + field_b + merge_b + pose_b + n6_b + (scores && !dev_out ? pad(vol * 4) : 0);
-    if (total + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
+    Carve c;
+    const size_t guess_at = c.pack(N * 16), rot_at = c.pack(N * a.nk * 32), beam_at = c.pack((size_t)n_beams * 16), range_at = c.pack(nray * 8);
+    const size_t cell_at = c.pack(N * 8), in_b = c.close(), field_at = c.take((size_t)a.frows * a.fW * 8);
+    const size_t packed_at = c.take(N * 8), gscore_at = c.take(N * 4), used_at = c.take(N * 4), merge_b = c.total() - packed_at;
+    const size_t pose_at = c.take(dev_out || !out_pose_n3 ? 0 : N * 24), n6_at = c.take(dev_out || !out_n6 ? 0 : N * 24);
+    const size_t score_at = c.take(dev_out || !scores ? 0 : vol * 4);
+    if (c.total() + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
         return fail(h, RBPF_ENOMEM, "scans, field and score volume need more than 4 GiB: refine fewer scans per call");
-    HIP_TRY(h, h->reserve(B_REFINE, total));
+    HIP_TRY(h, h->reserve(B_REFINE, c.total()));
     const Block& d = h->buf[B_REFINE];
     Staging& st = h->stage[S_REFINE];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
-    double* sg = reinterpret_cast<double*>(st.p);
-    double* sr = sg + 2 * N;
-    int32_t* sc = reinterpret_cast<int32_t*>(st.p + cell_at);
+    double* sg = st.as<double>(guess_at);
+    int32_t* sc = st.as<int32_t>(cell_at);
     for (size_t n = 0; n < N; ++n) {
-        const double gx = poses_n3[3 * n], gy = poses_n3[3 * n + 1], gth = poses_n3[3 * n + 2];
-        sg[2 * n] = gx; sg[2 * n + 1] = gy;
-        sc[2 * n] = (int32_t)floor(gx * inv); sc[2 * n + 1] = (int32_t)floor(gy * inv);
-        for (int q = 0; q < a.nk; ++q) {                                   // host libm: the device never sees an angle
-            const double th = gth + (double)(q - n_rot) * rot_step;
-            double* o = sr + (n * a.nk + q) * 4;
-            o[0] = cos(th); o[1] = sin(th); o[2] = th; o[3] = 0.0;
-        }
+        const double* g = poses_n3 + 3 * n;
+        sg[2 * n] = g[0]; sg[2 * n + 1] = g[1];
+        sc[2 * n] = (int32_t)floor(g[0] * inv); sc[2 * n + 1] = (int32_t)floor(g[1] * inv);
+        stage_rotations(st.as<double>(rot_at) + n * a.nk * 4, g[2], n_rot, rot_step);
     }
-    double* sb = sr + 4 * N * a.nk;
-    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
-    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    memcpy(stage_beam2(st.as<double>(beam_at), angles, n_beams), ranges, nray * 8);
     HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-    a.guess = d.as<const double>(); a.rot = a.guess + 2 * N; a.beam2 = a.rot + 4 * N * a.nk; a.ranges = a.beam2 + 2 * (size_t)n_beams;
-    a.cell0 = d.as<const int32_t>(cell_at);
-    size_t at = pad(in_b);
-    a.field = f.field = d.as<uint2>(at); at += field_b;
-    a.packed = d.as<unsigned long long>(at);
-    a.guess_score = d.as<int32_t>(at + pad(N * 8)); a.n_used = d.as<int32_t>(at + pad(N * 8) + pad(N * 4));
+    a.guess = d.as<const double>(guess_at); a.rot = d.as<const double>(rot_at); a.beam2 = d.as<const double>(beam_at);
+    a.ranges = d.as<const double>(range_at); a.cell0 = d.as<const int32_t>(cell_at);
+    a.field = f.field = d.as<uint2>(field_at);
+    a.packed = d.as<unsigned long long>(packed_at); a.guess_score = d.as<int32_t>(gscore_at); a.n_used = d.as<int32_t>(used_at);
     HIP_TRY(h, hipMemsetAsync(a.packed, 0, merge_b, h->stream));
-    at += merge_b;
-    a.out_pose = !out_pose_n3 ? nullptr : dev_out ? out_pose_n3 : d.as<double>(at); at += pose_b;
-    a.out_n6 = !out_n6 ? nullptr : dev_out ? out_n6 : d.as<int32_t>(at); at += n6_b;
-    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(at);
+    a.out_pose = !out_pose_n3 ? nullptr : dev_out ? out_pose_n3 : d.as<double>(pose_at);
+    a.out_n6 = !out_n6 ? nullptr : dev_out ? out_n6 : d.as<int32_t>(n6_at);
+    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(score_at);
     launch_refine_poses(v, f, a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    if (out_pose_n3) HIP_TRY(h, hipMemcpyAsync(out_pose_n3, a.out_pose, N * 24, hipMemcpyDeviceToHost, h->stream));
-    if (out_n6) HIP_TRY(h, hipMemcpyAsync(out_n6, a.out_n6, N * 24, hipMemcpyDeviceToHost, h->stream));
-    if (scores) HIP_TRY(h, hipMemcpyAsync(scores, a.scores, vol * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{out_pose_n3, a.out_pose, N * 24}, {out_n6, a.out_n6, N * 24}, {scores, a.scores, vol * 4}});
 }
 
 // ---- scan-to-submap matching (kernels_pairs.hip) -------------------------------------------------------------------
@@ -2740,23 +2679,17 @@ int rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, co
     if (!poses_n3 || !ranges || !angles || !pairs_m3) return fail(h, RBPF_EINVAL, "poses, ranges, angles or pairs is NULL");
     if (!out_pose_m3 && !out_m8) return fail(h, RBPF_EINVAL, "out_pose_m3 and out_m8 are both NULL");
     if (flags & ~RBPF_PAIRS_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
-    if (n_scans < 1 || n_pairs < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_scans >= 1, n_pairs >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
-    if (!refine_substeps_ok(substeps)) return fail(h, RBPF_EINVAL, "substeps must be 1, 2, 4, 8 or 16");
-    if (n_trans < 0 || n_trans > 32) return fail(h, RBPF_EINVAL, "0 <= n_trans <= 32 is required");
-    if (n_rot < 0 || n_rot > 100) return fail(h, RBPF_EINVAL, "0 <= n_rot <= 100 is required");
+    const char* const counts = "n_scans >= 1, n_pairs >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required";
+    ARG_TRY(h, n_pairs < 1 ? counts : check_counts(n_scans, 1, n_beams, 16384, counts));
+    ARG_TRY(h, check_search(substeps, n_trans, n_rot));
     const int nk = 2 * n_rot + 1, nw = 2 * n_trans + 1;
     if ((long long)n_pairs * nk >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_pairs * (2 n_rot + 1) < 2^31 is required");
-    if (!std::isfinite(rot_step) || rot_step < 0.0) return fail(h, RBPF_EINVAL, "rot_step must be finite and >= 0");
+    ARG_TRY(h, check_rot_step(rot_step));
     if (!std::isfinite(cells_per_m) || !(cells_per_m > 0.0)) return fail(h, RBPF_EINVAL, "cells_per_m must be finite and > 0");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
-    for (long long k = 0; k < 3LL * n_scans; ++k)
-        if (!std::isfinite(poses_n3[k])) return fail(h, RBPF_EINVAL, "poses must be finite");
-    for (long long k = 0; guess_m3 && k < 3LL * n_pairs; ++k)
-        if (!std::isfinite(guess_m3[k])) return fail(h, RBPF_EINVAL, "guesses must be finite");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
+    ARG_TRY(h, check_ranges(max_range, min_range));
+    ARG_TRY(h, check_poses(poses_n3, n_scans));
+    if (guess_m3) ARG_TRY(h, check_finite(guess_m3, 3LL * n_pairs, "guesses must be finite"));
+    ARG_TRY(h, check_angles(angles, n_beams));
     for (int m = 0; m < n_pairs; ++m) {
         const int32_t* p = pairs_m3 + 3 * (size_t)m;
         if (p[0] < 0 || p[0] >= n_scans || p[1] < 0 || p[1] >= p[2] || p[2] > n_scans)
@@ -2771,88 +2704,59 @@ int rbpf_match_pairs(rbpf_handle* h, const double* poses_n3, int32_t n_scans, co
         for (int n = p[1]; ok && n < p[2]; ++n) ok = in_reach(poses_n3[3 * (size_t)n]) && in_reach(poses_n3[3 * (size_t)n + 1]);
         if (!ok) return fail(h, RBPF_EINVAL, "(|coordinate| + max_range) * cells per metre * substeps + n_trans < 2^30 is required of every guess and reference pose");
     }
-    const int extra = (n_trans + substeps - 1) / substeps + 2;
-    const double reach = ceil(max_range * inv);
-    const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
-    if (!(reach <= (double)max_reach)) return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "pair matching between rbpf_scan_update_begin and rbpf_scan_update_end");
     RefineArgs a;
-    a.N = n_pairs; a.B = n_beams; a.Wt = n_trans; a.R = n_rot; a.nk = nk;
-    a.s = substeps == 1 ? 0 : substeps == 2 ? 1 : substeps == 4 ? 2 : substeps == 8 ? 3 : 4;
-    a.Mw = (int)reach + extra; a.WW = refine_row_words(a.Mw);
-    a.invS = invS; a.min_range = min_range; a.max_range = max_range;
+    const int max_reach = rbpf_refine_max_reach(substeps, n_trans);
+    if (!search_setup(a, n_pairs, n_beams, substeps, n_trans, n_rot, inv, min_range, max_range, max_reach, refine_fit(substeps, n_trans), "RBPF_PAIRS_KPW"))
+        return fail(h, RBPF_EINVAL, refine_window_message(max_range, inv, max_reach));
+    MID_STEP_TRY(h, "pair matching");
     a.fx0 = a.fy0 = a.frows = a.fW = 0; a.field = nullptr;                 // every pair stages its own field
-    const int t1 = nw * refine_runs(nw, a.s);                              // rotations per workgroup: refinement's rule
-    a.kpw = std::max(1, std::min(std::min(16, a.nk), REFINE_BLOCK / t1));
-    while (a.kpw > 1 && (long long)n_pairs * ((a.nk + a.kpw - 1) / a.kpw) < 1024) --a.kpw;
-    if (const char* e = getenv("RBPF_PAIRS_KPW")) a.kpw = std::max(1, std::min(std::min(16, a.nk), atoi(e)));   // for tests
     const bool dev_out = (flags & RBPF_PAIRS_DEVICE_OUT) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // scratch: [guesses] [rotations] [scan poses] [beams] [ranges] [centre cells] [runs] [queries] | [fields] [merge words] [guess
     // scores] [n_used] [n_ref] | host outputs
     const size_t M = (size_t)n_pairs, N = (size_t)n_scans, nray = N * n_beams, vol = M * nk * nw * nw;
-    const size_t guess_b = M * 16, rot_b = M * nk * 32, pose_at = guess_b + rot_b, beam_at = pose_at + N * 32;
-    const size_t cell_at = beam_at + (size_t)n_beams * 16 + nray * 8, run_at = cell_at + M * 8, query_at = run_at + M * 8, in_b = query_at + M * 4;
-    const size_t field_b = pad(M * (2 * (size_t)a.Mw + 1) * a.WW * 8), merge_b = pad(M * 8) + 3 * pad(M * 4);
-    const size_t pose_b = !dev_out && out_pose_m3 ? pad(M * 24) : 0, m8_b = !dev_out && out_m8 ? pad(M * 32) : 0;
-    const size_t total = pad(in_b) + field_b + merge_b + pose_b + m8_b + (scores && !dev_out ? pad(vol * 4) : 0);
-    if (total + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
+    Carve c;
+    const size_t guess_at = c.pack(M * 16), rot_at = c.pack(M * nk * 32), pose_at = c.pack(N * 32), beam_at = c.pack((size_t)n_beams * 16);
+    const size_t range_at = c.pack(nray * 8), cell_at = c.pack(M * 8), run_at = c.pack(M * 8), query_at = c.pack(M * 4), in_b = c.close();
+    const size_t field_at = c.take(M * (2 * (size_t)a.Mw + 1) * a.WW * 8);
+    const size_t packed_at = c.take(M * 8), gscore_at = c.take(M * 4), used_at = c.take(M * 4), ref_at = c.take(M * 4), merge_b = c.total() - packed_at;
+    const size_t out_pose_at = c.take(dev_out || !out_pose_m3 ? 0 : M * 24), m8_at = c.take(dev_out || !out_m8 ? 0 : M * 32);
+    const size_t score_at = c.take(dev_out || !scores ? 0 : vol * 4);
+    if (c.total() + (scores && dev_out ? vol * 4 : 0) > ((size_t)4 << 30))
         return fail(h, RBPF_ENOMEM, "pairs, fields and score volume need more than 4 GiB: match fewer pairs per call");
-    HIP_TRY(h, h->reserve(B_PAIRS, total));
+    HIP_TRY(h, h->reserve(B_PAIRS, c.total()));
     const Block& d = h->buf[B_PAIRS];
     Staging& st = h->stage[S_PAIRS];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
-    double* sg = reinterpret_cast<double*>(st.p);
-    double* sr = sg + 2 * M;
-    double* sp = reinterpret_cast<double*>(st.p + pose_at);
-    double* sb = reinterpret_cast<double*>(st.p + beam_at);
-    int32_t* sc = reinterpret_cast<int32_t*>(st.p + cell_at);
-    int32_t* sn = reinterpret_cast<int32_t*>(st.p + run_at);
-    int32_t* sq = reinterpret_cast<int32_t*>(st.p + query_at);
+    double* sg = st.as<double>(guess_at);
+    int32_t *sc = st.as<int32_t>(cell_at), *sn = st.as<int32_t>(run_at), *sq = st.as<int32_t>(query_at);
     for (size_t m = 0; m < M; ++m) {
         const int32_t* p = pairs_m3 + 3 * m;
         const double* g = guess_m3 ? guess_m3 + 3 * m : poses_n3 + 3 * (size_t)p[0];
         sg[2 * m] = g[0]; sg[2 * m + 1] = g[1];
         sc[2 * m] = (int32_t)floor(g[0] * inv); sc[2 * m + 1] = (int32_t)floor(g[1] * inv);
         sn[2 * m] = p[1]; sn[2 * m + 1] = p[2]; sq[m] = p[0];
-        for (int q = 0; q < nk; ++q) {                                     // host libm: the device never sees an angle
-            const double th = g[2] + (double)(q - n_rot) * rot_step;
-            double* o = sr + (m * nk + q) * 4;
-            o[0] = cos(th); o[1] = sin(th); o[2] = th; o[3] = 0.0;
-        }
+        stage_rotations(st.as<double>(rot_at) + m * nk * 4, g[2], n_rot, rot_step);
     }
-    for (size_t n = 0; n < N; ++n) {
-        sp[4 * n] = poses_n3[3 * n]; sp[4 * n + 1] = poses_n3[3 * n + 1];
-        sp[4 * n + 2] = cos(poses_n3[3 * n + 2]); sp[4 * n + 3] = sin(poses_n3[3 * n + 2]);
-    }
-    for (int b = 0; b < n_beams; ++b) { sb[2 * b] = cos(angles[b]); sb[2 * b + 1] = sin(angles[b]); }
-    memcpy(sb + 2 * (size_t)n_beams, ranges, nray * 8);
+    stage_pose4(st.as<double>(pose_at), poses_n3, N);
+    memcpy(stage_beam2(st.as<double>(beam_at), angles, n_beams), ranges, nray * 8);
     HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-    a.guess = d.as<const double>(); a.rot = a.guess + 2 * M; a.beam2 = d.as<const double>(beam_at); a.ranges = a.beam2 + 2 * (size_t)n_beams;
-    a.cell0 = d.as<const int32_t>(cell_at);
+    a.guess = d.as<const double>(guess_at); a.rot = d.as<const double>(rot_at); a.beam2 = d.as<const double>(beam_at);
+    a.ranges = d.as<const double>(range_at); a.cell0 = d.as<const int32_t>(cell_at);
     PairsArgs f;
     f.M = n_pairs; f.B = n_beams; f.Mw = a.Mw; f.WW = a.WW; f.inv = inv; f.min_range = min_range; f.max_range = max_range;
     f.pose4 = d.as<const double>(pose_at); f.beam2 = a.beam2; f.ranges = a.ranges; f.cell0 = a.cell0;
     f.runs = d.as<const int32_t>(run_at); f.query = d.as<const int32_t>(query_at);
-    size_t at = pad(in_b);
-    f.fields = d.as<uint2>(at); at += field_b;
-    a.packed = d.as<unsigned long long>(at);
-    a.guess_score = d.as<int32_t>(at + pad(M * 8)); a.n_used = d.as<int32_t>(at + pad(M * 8) + pad(M * 4));
-    f.n_ref = d.as<int32_t>(at + pad(M * 8) + 2 * pad(M * 4));
+    f.fields = d.as<uint2>(field_at);
+    a.packed = d.as<unsigned long long>(packed_at); a.guess_score = d.as<int32_t>(gscore_at); a.n_used = d.as<int32_t>(used_at);
+    f.n_ref = d.as<int32_t>(ref_at);
     HIP_TRY(h, hipMemsetAsync(a.packed, 0, merge_b, h->stream));
-    at += merge_b;
     a.out_pose = nullptr; a.out_n6 = nullptr;                              // pairs_final_kernel writes the pair outputs
-    f.out_pose = !out_pose_m3 ? nullptr : dev_out ? out_pose_m3 : d.as<double>(at); at += pose_b;
-    f.out_m8 = !out_m8 ? nullptr : dev_out ? out_m8 : d.as<int32_t>(at); at += m8_b;
-    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(at);
+    f.out_pose = !out_pose_m3 ? nullptr : dev_out ? out_pose_m3 : d.as<double>(out_pose_at);
+    f.out_m8 = !out_m8 ? nullptr : dev_out ? out_m8 : d.as<int32_t>(m8_at);
+    a.scores = !scores ? nullptr : dev_out ? scores : d.as<int32_t>(score_at);
     launch_match_pairs(f, a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    if (out_pose_m3) HIP_TRY(h, hipMemcpyAsync(out_pose_m3, f.out_pose, M * 24, hipMemcpyDeviceToHost, h->stream));
-    if (out_m8) HIP_TRY(h, hipMemcpyAsync(out_m8, f.out_m8, M * 32, hipMemcpyDeviceToHost, h->stream));
-    if (scores) HIP_TRY(h, hipMemcpyAsync(scores, a.scores, vol * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{out_pose_m3, f.out_pose, M * 24}, {out_m8, f.out_m8, M * 32}, {scores, a.scores, vol * 4}});
 }
 
 // ---- places by appearance (kernels_places.hip) -------------------------------------------------------------------
@@ -2863,44 +2767,33 @@ int rbpf_describe_scans(rbpf_handle* h, const double* ranges, int32_t n_scans, c
     if (!ranges || !angles) return fail(h, RBPF_EINVAL, "ranges or angles is NULL");
     if (!desc && !info_n2) return fail(h, RBPF_EINVAL, "desc and info_n2 are both NULL");
     if (flags & ~RBPF_PLACES_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
-    if (n_scans < 1 || n_beams < 1 || n_beams > 16384 || (long long)n_scans * n_beams >= (1LL << 31))
-        return fail(h, RBPF_EINVAL, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required");
+    ARG_TRY(h, check_counts(n_scans, 1, n_beams, 16384, "n_scans >= 1, 1 <= n_beams <= 16384 and n_scans * n_beams < 2^31 are required"));
     if (n_rings < 1 || n_rings > RBPF_PLACES_MAX_RINGS) return fail(h, RBPF_EINVAL, "1 <= n_rings <= 32 is required");
-    if (!std::isfinite(max_range) || !(max_range > 0.0)) return fail(h, RBPF_EINVAL, "max_range must be finite and > 0");
-    if (!std::isfinite(min_range) || min_range < 0.0) return fail(h, RBPF_EINVAL, "min_range must be finite and >= 0");
-    for (int b = 0; b < n_beams; ++b)
-        if (!std::isfinite(angles[b])) return fail(h, RBPF_EINVAL, "angles must be finite");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "scan description between rbpf_scan_update_begin and rbpf_scan_update_end");
+    ARG_TRY(h, check_ranges(max_range, min_range));
+    ARG_TRY(h, check_angles(angles, n_beams));
+    MID_STEP_TRY(h, "scan description");
     const bool dev_out = (flags & RBPF_PLACES_DEVICE_OUT) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // scratch: [sectors] [ranges] | host outputs
     const size_t N = (size_t)n_scans, R = (size_t)n_rings, nray = N * n_beams;
-    const size_t range_at = pad((size_t)n_beams * 4), in_b = range_at + nray * 8;
-    const size_t desc_b = !dev_out && desc ? pad(N * R * 8) : 0, info_b = !dev_out && info_n2 ? pad(N * 8) : 0;
-    const size_t total = pad(in_b) + desc_b + info_b;
-    if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "the scans need more than 4 GiB: describe fewer scans per call");
-    HIP_TRY(h, h->reserve(B_PLACES, total));
+    Carve c;                                                               // scratch: [sectors] [ranges] | host outputs
+    const size_t sector_at = c.take((size_t)n_beams * 4), range_at = c.pack(nray * 8), in_b = c.close();
+    const size_t desc_at = c.take(dev_out || !desc ? 0 : N * R * 8), info_at = c.take(dev_out || !info_n2 ? 0 : N * 8);
+    if (c.total() > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "the scans need more than 4 GiB: describe fewer scans per call");
+    HIP_TRY(h, h->reserve(B_PLACES, c.total()));
     const Block& d = h->buf[B_PLACES];
     Staging& st = h->stage[S_PLACES];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
-    int32_t* ss = reinterpret_cast<int32_t*>(st.p);
+    int32_t* ss = st.as<int32_t>(sector_at);
     const double per_rad = 32.0 / M_PI;
     for (int b = 0; b < n_beams; ++b)                                      // host floating point: the device never sees an angle.  fmod is exact:
         ss[b] = (int32_t)((long long)fmod(floor(angles[b] * per_rad), 64.0) & 63);   // ((int64)floor) & 63, also where the floor exceeds an int64
     memcpy(st.p + range_at, ranges, nray * 8);
     HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-    size_t at = pad(in_b);
-    unsigned long long* o_desc = !desc ? nullptr : dev_out ? reinterpret_cast<unsigned long long*>(desc) : d.as<unsigned long long>(at);
-    at += desc_b;
-    int32_t* o_info = !info_n2 ? nullptr : dev_out ? info_n2 : d.as<int32_t>(at);
-    launch_describe_scans(d.as<const double>(range_at), d.as<const int32_t>(), n_scans, n_beams, n_rings, min_range, max_range,
+    unsigned long long* o_desc = !desc ? nullptr : dev_out ? reinterpret_cast<unsigned long long*>(desc) : d.as<unsigned long long>(desc_at);
+    int32_t* o_info = !info_n2 ? nullptr : dev_out ? info_n2 : d.as<int32_t>(info_at);
+    launch_describe_scans(d.as<const double>(range_at), d.as<const int32_t>(sector_at), n_scans, n_beams, n_rings, min_range, max_range,
                           (double)n_rings / max_range, o_desc, o_info, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    if (desc) HIP_TRY(h, hipMemcpyAsync(desc, o_desc, N * R * 8, hipMemcpyDeviceToHost, h->stream));
-    if (info_n2) HIP_TRY(h, hipMemcpyAsync(info_n2, o_info, N * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{desc, o_desc, N * R * 8}, {info_n2, o_info, N * 8}});
 }
 
 int rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_queries, const uint64_t* ref_desc, int32_t n_refs,
@@ -2916,46 +2809,38 @@ int rbpf_match_places(rbpf_handle* h, const uint64_t* query_desc, int32_t n_quer
     if ((long long)n_queries * k >= (1LL << 31)) return fail(h, RBPF_EINVAL, "n_queries * k < 2^31 is required");
     for (int q = 0; ref_limit && q < n_queries; ++q)
         if (ref_limit[q] < 0 || ref_limit[q] > n_refs) return fail(h, RBPF_EINVAL, "0 <= ref_limit[q] <= n_refs is required");
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "place search between rbpf_scan_update_begin and rbpf_scan_update_end");
+    MID_STEP_TRY(h, "place search");
     PlacesArgs a;
     a.nq = n_queries; a.nr = n_refs; a.R = n_rings; a.k = k;
     a.chunk = std::min(256, n_refs);
     if (const char* e = getenv("RBPF_PLACES_CHUNK")) a.chunk = std::max(1, std::min(n_refs, atoi(e)));   // for tests
     a.nch = (n_refs + a.chunk - 1) / a.chunk;
     const bool dev_out = (flags & RBPF_PLACES_DEVICE_OUT) != 0, dev_in = (flags & RBPF_PLACES_DEVICE_IN) != 0;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // scratch: [limits] [host query table] [host reference table] | [dilated references] [weights] [chunk lists] | host outputs
     const size_t Q = (size_t)n_queries, N = (size_t)n_refs, R = (size_t)n_rings;
-    const size_t qd_at = pad(Q * 4), rd_at = qd_at + (dev_in ? 0 : pad(Q * R * 8)), in_b = rd_at + (dev_in ? 0 : pad(N * R * 8));
-    const size_t dil_b = pad(N * R * 8), w_b = pad(N * 4), part_b = pad(Q * a.nch * k * 16);
-    const size_t qk4_b = !dev_out && out_qk4 ? pad(Q * k * 16) : 0, q2_b = !dev_out && out_q2 ? pad(Q * 8) : 0;
-    const size_t total = in_b + dil_b + w_b + part_b + qk4_b + q2_b;
-    if (total > ((size_t)4 << 30) || (Q + 3) / 4 * a.nch >= ((size_t)1 << 31))
+    Carve c;
+    const size_t limit_at = c.take(Q * 4), qd_at = c.take(dev_in ? 0 : Q * R * 8), rd_at = c.take(dev_in ? 0 : N * R * 8), in_b = c.total();
+    const size_t dil_at = c.take(N * R * 8), w_at = c.take(N * 4), part_at = c.take(Q * a.nch * k * 16);
+    const size_t qk4_at = c.take(dev_out || !out_qk4 ? 0 : Q * k * 16), q2_at = c.take(dev_out || !out_q2 ? 0 : Q * 8);
+    if (c.total() > ((size_t)4 << 30) || (Q + 3) / 4 * a.nch >= ((size_t)1 << 31))
         return fail(h, RBPF_ENOMEM, "tables and chunk lists need more than 4 GiB: match fewer queries per call");
-    HIP_TRY(h, h->reserve(B_PLACES, total));
+    HIP_TRY(h, h->reserve(B_PLACES, c.total()));
     const Block& d = h->buf[B_PLACES];
     Staging& st = h->stage[S_PLACES];
     HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
-    int32_t* sl = reinterpret_cast<int32_t*>(st.p);
+    int32_t* sl = st.as<int32_t>(limit_at);
     for (size_t q = 0; q < Q; ++q) sl[q] = ref_limit ? ref_limit[q] : n_refs;
     if (!dev_in) { memcpy(st.p + qd_at, query_desc, Q * R * 8); memcpy(st.p + rd_at, ref_desc, N * R * 8); }
     HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-    a.limit = d.as<const int32_t>();
+    a.limit = d.as<const int32_t>(limit_at);
     a.qd = dev_in ? reinterpret_cast<const unsigned long long*>(query_desc) : d.as<const unsigned long long>(qd_at);
     a.rd = dev_in ? reinterpret_cast<const unsigned long long*>(ref_desc) : d.as<const unsigned long long>(rd_at);
-    size_t at = in_b;
-    a.dil = d.as<unsigned long long>(at); at += dil_b;
-    a.w = d.as<int32_t>(at); at += w_b;
-    a.partial = d.as<int4>(at); at += part_b;
-    a.out_qk4 = !out_qk4 ? nullptr : dev_out ? out_qk4 : d.as<int32_t>(at); at += qk4_b;
-    a.out_q2 = !out_q2 ? nullptr : dev_out ? out_q2 : d.as<int32_t>(at);
+    a.dil = d.as<unsigned long long>(dil_at); a.w = d.as<int32_t>(w_at); a.partial = d.as<int4>(part_at);
+    a.out_qk4 = !out_qk4 ? nullptr : dev_out ? out_qk4 : d.as<int32_t>(qk4_at);
+    a.out_q2 = !out_q2 ? nullptr : dev_out ? out_q2 : d.as<int32_t>(q2_at);
     launch_match_places(a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    if (out_qk4) HIP_TRY(h, hipMemcpyAsync(out_qk4, a.out_qk4, Q * k * 16, hipMemcpyDeviceToHost, h->stream));
-    if (out_q2) HIP_TRY(h, hipMemcpyAsync(out_q2, a.out_q2, Q * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{out_qk4, a.out_qk4, Q * k * 16}, {out_q2, a.out_q2, Q * 8}});
 }
 
 // ---- peaks and moments of score volumes (kernels_surface.hip) -----------------------------------------------------
@@ -2980,12 +2865,10 @@ int rbpf_score_surface(rbpf_handle* h, const int32_t* scores, int32_t n_items, i
         for (size_t t = 0; t < vol; ++t)
             if ((uint32_t)scores[t] > 32768u) return fail(h, RBPF_EINVAL, "a score outside 0 .. 32768");
     }
-    if (h->scan_begun) return fail(h, RBPF_ESTATE, "score surface between rbpf_scan_update_begin and rbpf_scan_update_end");
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // scratch: [host volume] [host drops] | host outputs
-    const size_t drop_at = dev_in ? 0 : pad(vol * 4), in_b = dev_in ? 0 : drop_at + (drop_n ? N * 4 : 0);
-    const size_t rec_b = dev_out ? 0 : pad(N * K * 128), cnt_b = dev_out ? 0 : pad(N * 4);
-    const size_t total = pad(in_b) + rec_b + cnt_b;
+    MID_STEP_TRY(h, "score surface");
+    Carve c;                                                               // scratch: [host volume] [host drops] | host outputs
+    const size_t vol_at = c.take(dev_in ? 0 : vol * 4), drop_at = c.pack(dev_in || !drop_n ? 0 : N * 4), in_b = c.close();
+    const size_t rec_at = c.take(dev_out ? 0 : N * K * 128), cnt_at = c.take(dev_out ? 0 : N * 4), total = c.total();
     if (total > ((size_t)4 << 30)) return fail(h, RBPF_ENOMEM, "the volume and the records need more than 4 GiB: fewer items per call");
     SurfaceArgs a;
     a.N = n_items; a.R = n_rot; a.W = n_trans; a.ex_t = ex_trans; a.ex_r = ex_rot; a.K = n_peaks;
@@ -2997,21 +2880,17 @@ int rbpf_score_surface(rbpf_handle* h, const int32_t* scores, int32_t n_items, i
         if (!dev_in) {
             Staging& st = h->stage[S_SURFACE];
             HIP_TRY(h, st.begin(in_b));                                    // the last upload may still read it
-            memcpy(st.p, scores, vol * 4);
+            memcpy(st.p + vol_at, scores, vol * 4);
             if (drop_n) memcpy(st.p + drop_at, drop_n, N * 4);
             HIP_TRY(h, st.upload(d.p, in_b, h->stream));
-            a.scores = d.as<const int32_t>();
+            a.scores = d.as<const int32_t>(vol_at);
             a.drop = drop_n ? d.as<const int32_t>(drop_at) : nullptr;
         }
-        if (!dev_out) { a.out = d.as<long long>(pad(in_b)); a.count = d.as<int32_t>(pad(in_b) + rec_b); }
+        if (!dev_out) { a.out = d.as<long long>(rec_at); a.count = d.as<int32_t>(cnt_at); }
     }
     launch_score_surface(a, h->stream);
     HIP_TRY(h, hipGetLastError());
-    if (dev_out) return RBPF_OK;
-    HIP_TRY(h, hipMemcpyAsync(out_nk16, a.out, N * K * 128, hipMemcpyDeviceToHost, h->stream));
-    if (out_count) HIP_TRY(h, hipMemcpyAsync(out_count, a.count, N * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return RBPF_OK;
+    return dev_out ? RBPF_OK : fetch(h, {{out_nk16, a.out, N * K * 128}, {out_count, a.count, N * 4}});
 }
 
 }  // extern "C"

@@ -33,21 +33,31 @@ struct Block {
     }
     template <typename T> T* as(size_t byte_offset = 0) const { return reinterpret_cast<T*>(p + byte_offset); }
 };
-// the handle's device scratch: samples of rbpf_weight_samples; table and ancestors of the global resample; departing particles
-// and job list of a migration; LUT, weights and jobs of the last render, the group sums of a split render, the outputs of a
-// render to host memory; flag, touched tiles, jobs and host raster of a map load; poses, beams and host outputs of a cast;
-// rotations, beams, offset table, field planes, candidate words, merge raster and host outputs of a locate; flag, touched tiles,
-// jobs, host source and host outputs of a map placement; rotations, points, offset table, field planes, merge raster and host
-// outputs of an alignment; poses, beams, table and host outputs of a view gain; start and goal cells, round counters, cost fields,
-// traversable bits, dirty flags and host outputs of a travel cost; round counters, region counts, tables, label and size rasters,
-// dirty flags and the host label output of a frontier labelling; reference raster, table, flag, near rows, block sums and the
-// host score output of a map scoring; particle list or weights, chunk maps, chunk starts, lineage table and host outputs of a
-// trajectory read-out or an estimate; poses, beams, ranges, end cells and host rasters of a map building; guesses, rotations, beams,
-// ranges, field planes, merge words and host outputs of a pose refinement; guesses, rotations, scan poses, beams, ranges, pair lists,
-// the pairs' fields, merge words and host outputs of a pair matching; sectors and ranges, or limits and descriptor tables, the
-// dilated references, their weights, the chunks' lists and host outputs of a scan description or a place search; the host volume,
-// the host drops and the host outputs of a score surface
-enum { B_SAMPLES, B_GT, B_GIDX, B_I32, B_JOBS, B_DRAIN_FIRST, B_RENDER = B_DRAIN_FIRST, B_RENDER_PART, B_RENDER_OUT, B_LOAD, B_CAST, B_LOCATE, B_PLACE, B_ALIGN, B_GAIN, B_TRAVEL, B_FRONTIER, B_SCORE, B_TRACK, B_BUILD, B_REFINE, B_PAIRS, B_PLACES, B_SURFACE, B_COUNT };
+// the handle's device scratch: what each block holds ("host outputs": the staging of outputs the caller wants in host memory)
+enum {
+    B_SAMPLES,                      // the samples of rbpf_weight_samples
+    B_GT, B_GIDX,                   // table and ancestors of the global resample
+    B_I32, B_JOBS,                  // departing particles and job list of a migration
+    B_DRAIN_FIRST,                  // from here on queued work may still read a block: h->reserve drains the stream before it grows
+    B_RENDER = B_DRAIN_FIRST,       // LUT, weights and jobs of the last render
+    B_RENDER_PART, B_RENDER_OUT,    // the group sums of a split render; the outputs of a render to host memory
+    B_LOAD,                         // flag, touched tiles, jobs and host raster of a map load
+    B_CAST,                         // poses, beams, host outputs
+    B_LOCATE,                       // rotations, beams, offset table, field planes, candidate words, merge raster, host outputs
+    B_PLACE,                        // flag, touched tiles, jobs, host source, host outputs
+    B_ALIGN,                        // rotations, points, offset table, field planes, merge raster, host outputs
+    B_GAIN,                         // poses, beams, table, host outputs
+    B_TRAVEL,                       // start and goal cells, round counters, cost fields, traversable bits, dirty flags, host outputs
+    B_FRONTIER,                     // round counters, region counts, tables, label and size rasters, dirty flags, host labels
+    B_SCORE,                        // flag, table, reference raster, near rows, block sums, host scores
+    B_TRACK,                        // particle list or weights, chunk maps, chunk starts, lineage table, host outputs
+    B_BUILD,                        // poses, beams, ranges, end cells, host rasters
+    B_REFINE,                       // guesses, rotations, beams, ranges, centre cells, field planes, merge words, host outputs
+    B_PAIRS,                        // guesses, rotations, scan poses, beams, ranges, pair lists, the pairs' fields, merge words, host outputs
+    B_PLACES,                       // sectors and ranges, or limits and descriptor tables, dilated references, weights, chunk lists, host outputs
+    B_SURFACE,                      // host volume, host drops, host outputs
+    B_COUNT
+};
 
 // A device temporary of one call (diagnostic entry points), freed on every return path.  hipFree waits for the device, so an
 // early error return cannot pull memory from under queued work.
@@ -77,14 +87,18 @@ struct Staging : Block {
     }
     void destroy_event() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; }
 };
-// job lists of the pack / unpack kernels and the landing zone of the early resample read-back (pinned); the blocks uploaded
-// into B_RENDER, B_CAST, B_LOAD, B_LOCATE, B_PLACE, B_ALIGN and B_GAIN (pageable); the round counters a travel cost reads back
-// and, behind them, the block it uploads into B_TRAVEL (pinned); the round counters a frontier labelling reads back (pinned);
-// the table and the host reference uploaded into B_SCORE (pageable); the particle list or the weights uploaded into B_TRACK (pageable);
-// the poses, beams and ranges uploaded into B_BUILD (pageable); the guesses, rotations, beams and ranges uploaded into B_REFINE (pageable);
-// the guesses, rotations, scan poses, beams, ranges and pair lists uploaded into B_PAIRS (pageable); the sectors and ranges, or the
-// limits and host descriptor tables, uploaded into B_PLACES (pageable); the host volume and drops uploaded into B_SURFACE (pageable)
-enum { S_JOBS, S_EARLY, S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN, S_TRAVEL, S_FRONTIER, S_SCORE, S_TRACK, S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_SURFACE, S_COUNT };
+// host staging, pageable unless noted: what is uploaded into the block of the same name
+enum {
+    S_JOBS,                         // job lists of the pack / unpack kernels (pinned)
+    S_EARLY,                        // the landing zone of the early resample read-back (pinned)
+    S_RENDER, S_CAST, S_LOAD, S_LOCATE, S_PLACE, S_ALIGN, S_GAIN,   // the upload of B_RENDER .. B_GAIN
+    S_TRAVEL,                       // the round counters a travel cost reads back and, behind them, its upload (pinned)
+    S_FRONTIER,                     // the round counters a frontier labelling reads back (pinned)
+    S_SCORE,                        // the table and the host reference
+    S_TRACK,                        // the particle list or the weights
+    S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_SURFACE,   // the upload of B_BUILD .. B_SURFACE: everything in front of the first '|' of its layout
+    S_COUNT
+};
 
 // Pinned staging ring for the per-step uploads (scan block, previous scan, index vectors): a slot is reused only after the
 // copy that read it has completed (its event), so uploading never drains the stream.
