@@ -678,6 +678,50 @@ int64_t rbpf_track_record_bytes(rbpf_handle* h);
 int  rbpf_track_export(rbpf_handle* h, int32_t t0, int32_t t1, void* records);
 int  rbpf_track_import(rbpf_handle* h, int32_t n, const void* records);
 
+/* ---- pose modes: which hypotheses are alive, how heavy is each, and where? ---------------------------------------------------
+ * A set is P poses (x_j, y_j, th_j) with the effective weights w_j of weights_mode / weights (as rbpf_estimate; the RBPF_W_RESAMPLE
+ * shift is taken over all P).  Parameters: bin_xy (metres, finite, > 0), n_th (heading bins, 1 .. 4096), max_modes K
+ * (1 .. RBPF_MODES_MAX).  The host computes inv = 1.0 / bin_xy and kth = (double)n_th / 6.283185307179586 once, in float64.
+ *   bin of a particle     ix = floor(x * inv), iy = floor(y * inv), it = floor(th * kth) mod n_th taken non-negative: one IEEE
+ *                         multiplication and a floor each; any finite th is accepted, nothing is wrapped beforehand
+ *   contributing          finite w > 0 and a finite pose (the rule of the estimate row), and |x * inv| < 2^23, |y * inv| < 2^23,
+ *                         |th * kth| < 2^40.  Everyone else contributes nothing and has label -1
+ *   adjacency             two occupied bins with |dix| <= 1, |diy| <= 1 and cyclic distance of `it` modulo n_th <= 1: the
+ *                         26-neighbourhood; n_th <= 3 makes all heading bins adjacent, n_th = 1 ignores the heading
+ *   mode                  a connected component of occupied bins; its root = the smallest index of its contributing particles,
+ *                         its members = the contributing particles in its bins
+ *   order                 wmax = the largest effective weight of a contributing particle;
+ *                         q_j = (uint64) floor((w_j / wmax) * 4294967296.0), 0 .. 2^32; Q_c = sum of q_j over the members (< 2^49);
+ *                         Q_total = sum of Q_c.  Modes are ordered by Q_c descending, ties by root ascending: integers only.
+ *                         The first min(n_modes, K) get rows
+ *   info  int64 [4]       {n_modes, n_bins, n_used, Q_total}; n_modes counts all modes, also those beyond K, n_bins all occupied bins
+ *   rows_f64 [K][16]      the estimate row over the mode's members with the effective weights: the bits of the estimate row of the
+ *                         set with everyone else's weight 0 (same sums, same order).  Slot 12 = (double)Q_c, slot 13 =
+ *                         (double)Q_c / (double)Q_total (the mode's share), slots 14, 15 = 0
+ *   rows_i32 [K][4]       {best, n_used, n_bins, root} of the mode; best = the first argmax of the RAW weights among the members
+ *   rows past min(n_modes, K): NaN in slots 0 .. 11, 0 in slots 12 .. 15, {-1, 0, 0, -1}
+ *   label int32 [P]       the root of particle j's mode, or -1
+ * With no contributing particle info is all zeros and every row is the unused row.  Two calls on the same state return identical
+ * bits.  DESIGN.md 3.21 has the kernel.
+ * rbpf_pose_modes: the set of the filter's current poses.  Needs no tracking, changes no engine state, runs on the handle's stream,
+ * and stands towards a held-back map update and a half-done scan update as rbpf_estimate does.  info4 is required; rows_f64 and
+ * rows_i32 are both given or both NULL; label may be NULL.  Without RBPF_MODES_DEVICE_OUT the outputs are host arrays, complete on
+ * return.
+ * rbpf_track_modes: the smoothed form, the companion of rbpf_track_summary.  For every record t of [t0, t1) the set holds the poses
+ * at t of the current particles' ancestors, with the FINAL weights; member indices (root, best) are the current particles'.  info
+ * [T][4], rows_f64 [T][K][16], rows_i32 [T][K][4] are host arrays, complete on return; any may be NULL, not all.  The records are
+ * worked through in slabs whose tables stay within 256 MiB (RBPF_MODES_SLAB_BYTES in the environment lowers that: tests).
+ * RBPF_ESTATE while tracking is off.
+ * Both: P <= 65536.  RBPF_EINVAL, checked before anything is queued and with no output touched: a NULL pattern, a bad mode, a
+ * negative or non-finite given weight, a bin_xy that is not finite or not > 0, n_th or max_modes out of range, an unknown flag, a
+ * bad record range. */
+#define RBPF_MODES_DEVICE_OUT 1u   /* the four outputs are device pointers, written in stream order, no host wait */
+#define RBPF_MODES_MAX 64
+int  rbpf_pose_modes(rbpf_handle* h, int32_t weights_mode, const double* weights, double bin_xy, int32_t n_th, int32_t max_modes,
+                     uint32_t flags, int64_t* info4, double* rows_f64, int32_t* rows_i32, int32_t* label);
+int  rbpf_track_modes(rbpf_handle* h, int32_t t0, int32_t t1, int32_t weights_mode, const double* weights, double bin_xy, int32_t n_th,
+                      int32_t max_modes, int64_t* info /* [T][4] */, double* rows_f64 /* [T][K][16] */, int32_t* rows_i32 /* [T][K][4] */);
+
 /* ---- map building: what map do these scans draw from these poses? ----------------------------------------------------------
  * Hit and visit counts of n_scans scans (ranges [n_scans][n_beams], metres; angles [n_beams], sensor frame, as rbpf_set_scan) taken
  * at the sensor poses poses_n3 [n_scans][3], rasterised at ANY cell size: inv = cells_per_m (finite, > 0), cell (X, Y) is the world

@@ -25,6 +25,7 @@ RBPF_SCORE_DEVICE_IN, RBPF_SCORE_DEVICE_OUT, RBPF_SCORE_FIELDS = 1, 2, 13
 RBPF_W_UNIFORM, RBPF_W_RESAMPLE, RBPF_W_GIVEN = 0, 1, 2
 RBPF_EST_F64, RBPF_EST_I32 = 16, 4
 RBPF_TRACK_IMU, RBPF_TRACK_SCAN, RBPF_TRACK_CHUNK, RBPF_TRACK_DEVICE_OUT = 1, 2, 64, 1
+RBPF_MODES_DEVICE_OUT, RBPF_MODES_MAX = 1, 64
 RBPF_BUILD_DEVICE_OUT, RBPF_BUILD_ACCUMULATE = 1, 2
 RBPF_REFINE_DEVICE_OUT = 1
 RBPF_PAIRS_DEVICE_OUT = 1
@@ -156,6 +157,8 @@ PROTOTYPES = {
     "rbpf_track_record_bytes": (C.c_int64, [_H]),
     "rbpf_track_export": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
     "rbpf_track_import": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "rbpf_pose_modes": (C.c_int, [_H, C.c_int32, _D, C.c_double, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbpf_track_modes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _D, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_build_map": (C.c_int, [_H, _D, C.c_int32, _D, _D, C.c_int32, C.c_double, _I, C.c_double, C.c_double, C.c_uint32,
                                  C.c_void_p, C.c_void_p]),
     "rbpf_refine_max_reach": (C.c_int32, [C.c_int32, C.c_int32]),

@@ -2449,6 +2449,114 @@ int rbpf_track_summary(rbpf_handle* h, int32_t t0, int32_t t1, int32_t mode, con
     return RBPF_OK;
 }
 
+}  // extern "C"
+
+// ---- pose modes (kernels_modes.hip) ------------------------------------------------------------------------------
+static const size_t MODES_SLAB_BYTES = (size_t)256 << 20;    // lineage rows and tables of the records rbpf_track_modes has in flight
+
+// the checks the two entry points share, in the order of the header; fills what the kernel needs but the pointers
+static int modes_args(rbpf_handle* h, int32_t mode, const double* weights, double bin_xy, int32_t n_th, int32_t max_modes, ModesArgs& a) {
+    if (h->v.P > MODES_MAX_P) return fail(h, RBPF_EINVAL, "pose modes need P <= 65536");
+    const int rc = check_weights_mode(h, mode, weights);
+    if (rc) return rc;
+    if (weights)
+        for (int j = 0; j < h->v.P; ++j)
+            if (!std::isfinite(weights[j])) return fail(h, RBPF_EINVAL, "a given weight is not finite");
+    if (!std::isfinite(bin_xy) || !(bin_xy > 0)) return fail(h, RBPF_EINVAL, "bin_xy must be finite and > 0");
+    if (n_th < 1 || n_th > 4096) return fail(h, RBPF_EINVAL, "1 <= n_th <= 4096 is required");
+    if (max_modes < 1 || max_modes > RBPF_MODES_MAX) return fail(h, RBPF_EINVAL, "1 <= max_modes <= RBPF_MODES_MAX is required");
+    a.P = h->v.P; a.S = modes_slots(a.P);
+    a.n_th = n_th; a.K = max_modes; a.mode = mode;
+    a.inv = 1.0 / bin_xy; a.kth = (double)n_th / 6.283185307179586;
+    a.w_raw = h->v.weight; a.w_given = nullptr; a.label = nullptr;
+    return RBPF_OK;
+}
+
+static int modes_upload_weights(rbpf_handle* h, const double* weights) {
+    Staging& st = h->stage[S_TRACK];
+    HIP_TRY(h, st.begin((size_t)h->v.P * 8));
+    memcpy(st.p, weights, (size_t)h->v.P * 8);
+    HIP_TRY(h, st.upload(h->buf[B_TRACK].p, (size_t)h->v.P * 8, h->stream));
+    return RBPF_OK;
+}
+
+extern "C" {
+
+int rbpf_pose_modes(rbpf_handle* h, int32_t mode, const double* weights, double bin_xy, int32_t n_th, int32_t max_modes, uint32_t flags,
+                    int64_t* info4, double* rows_f64, int32_t* rows_i32, int32_t* label) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    if (!info4) return fail(h, RBPF_EINVAL, "info4 is NULL");
+    if (!rows_f64 != !rows_i32) return fail(h, RBPF_EINVAL, "rows_f64 and rows_i32 are both given or both NULL");
+    if (flags & ~RBPF_MODES_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    ModesArgs a;
+    int rc = modes_args(h, mode, weights, bin_xy, n_th, max_modes, a);
+    if (rc) return rc;
+    const bool dev_out = (flags & RBPF_MODES_DEVICE_OUT) != 0;
+    const size_t P = (size_t)a.P, K = (size_t)a.K;
+    const size_t w_b = weights ? pad256(P * 8) : 0, tab_b = modes_set_bytes(a.P, a.S);
+    const size_t f_n = K * RBPF_EST_F64 * 8, i_n = K * RBPF_EST_I32 * 4;
+    const size_t out_b = dev_out ? 0 : 256 + pad256(f_n) + pad256(i_n);
+    HIP_TRY(h, h->reserve(B_TRACK, w_b + tab_b + out_b));
+    const Block& d = h->buf[B_TRACK];
+    if (weights && (rc = modes_upload_weights(h, weights))) return rc;
+    a.w_given = weights ? d.as<const double>() : nullptr;
+    a.tables = d.p + w_b;
+    const size_t at = w_b + tab_b;
+    a.info = dev_out ? reinterpret_cast<long long*>(info4) : d.as<long long>(at);
+    a.rows_f = !rows_f64 ? nullptr : dev_out ? rows_f64 : d.as<double>(at + 256);
+    a.rows_i = !rows_i32 ? nullptr : dev_out ? rows_i32 : d.as<int32_t>(at + 256 + pad256(f_n));
+    a.label = dev_out ? label : nullptr;
+    launch_pose_modes(h->v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (dev_out) return RBPF_OK;
+    return fetch(h, {{info4, a.info, 32}, {rows_f64, a.rows_f, f_n}, {rows_i32, a.rows_i, i_n},
+                     {label, a.tables + modes_label_offset(a.P, a.S), P * 4}});
+}
+
+int rbpf_track_modes(rbpf_handle* h, int32_t t0, int32_t t1, int32_t mode, const double* weights, double bin_xy, int32_t n_th,
+                     int32_t max_modes, int64_t* info, double* rows_f64, int32_t* rows_i32) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    int rc = track_state_and_range(h, t0, t1);
+    if (rc) return rc;
+    if (!info && !rows_f64 && !rows_i32) return fail(h, RBPF_EINVAL, "info, rows_f64 and rows_i32 are all NULL");
+    ModesArgs a;
+    if ((rc = modes_args(h, mode, weights, bin_xy, n_th, max_modes, a))) return rc;
+    const size_t P = (size_t)a.P, K = (size_t)a.K, T = (size_t)(t1 - t0);
+    const size_t tab_b = modes_set_bytes(a.P, a.S), lin_row = P * 4;
+    size_t budget = MODES_SLAB_BYTES;
+    if (const char* env = getenv("RBPF_MODES_SLAB_BYTES")) {                                     // tests: several slabs on a short log
+        const long long v = atoll(env);
+        if (v > 0) budget = std::min(budget, (size_t)v);
+    }
+    const size_t slab = std::max<size_t>(1, std::min(T, budget / (tab_b + lin_row)));            // records in flight
+    const size_t w_b = weights ? pad256(P * 8) : 0, walk_b = track_walk_bytes(h, t0, a.P), lin_b = pad256(slab * lin_row);
+    const size_t info_b = pad256(slab * 32), f_b = pad256(slab * K * RBPF_EST_F64 * 8), i_b = pad256(slab * K * RBPF_EST_I32 * 4);
+    HIP_TRY(h, h->reserve(B_TRACK, w_b + walk_b + lin_b + slab * tab_b + info_b + f_b + i_b));
+    const Block& d = h->buf[B_TRACK];
+    if (weights && (rc = modes_upload_weights(h, weights))) return rc;
+    a.w_given = weights ? d.as<const double>() : nullptr;
+    int32_t* d_lin = d.as<int32_t>(w_b + walk_b);
+    size_t at = w_b + walk_b + lin_b;
+    a.tables = d.p + at; at += slab * tab_b;
+    a.info = d.as<long long>(at); at += info_b;
+    a.rows_f = d.as<double>(at); at += f_b;
+    a.rows_i = d.as<int32_t>(at);
+    for (size_t r0 = 0; r0 < T; r0 += slab) {              // a slab's outputs leave in stream order before the next slab overwrites them
+        const size_t n = std::min(slab, T - r0);
+        const int a0 = t0 + (int)r0;
+        if ((rc = track_walk(h, a0, a0 + (int)n, nullptr, a.P, w_b, d_lin, nullptr))) return rc;
+        launch_track_modes(h->track_log(), a0, (int)n, d_lin, a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        if (info) HIP_TRY(h, hipMemcpyAsync(info + r0 * 4, a.info, n * 32, hipMemcpyDeviceToHost, h->stream));
+        if (rows_f64) HIP_TRY(h, hipMemcpyAsync(rows_f64 + r0 * K * RBPF_EST_F64, a.rows_f, n * K * RBPF_EST_F64 * 8, hipMemcpyDeviceToHost, h->stream));
+        if (rows_i32) HIP_TRY(h, hipMemcpyAsync(rows_i32 + r0 * K * RBPF_EST_I32, a.rows_i, n * K * RBPF_EST_I32 * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return RBPF_OK;
+}
+
 int rbpf_track_filtered(rbpf_handle* h, int32_t t0, int32_t t1, double* out_f64, int32_t* out_i32) {
     if (!h) return RBPF_EINVAL;
     ON_DEVICE(h);

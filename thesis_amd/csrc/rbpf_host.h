@@ -50,7 +50,7 @@ enum {
     B_TRAVEL,                       // start and goal cells, round counters, cost fields, traversable bits, dirty flags, host outputs
     B_FRONTIER,                     // round counters, region counts, tables, label and size rasters, dirty flags, host labels
     B_SCORE,                        // flag, table, reference raster, near rows, block sums, host scores
-    B_TRACK,                        // particle list or weights, chunk maps, chunk starts, lineage table, host outputs
+    B_TRACK,                        // particle list or weights, chunk maps, chunk starts, lineage table, mode tables, host outputs
     B_BUILD,                        // poses, beams, ranges, end cells, host rasters
     B_REFINE,                       // guesses, rotations, beams, ranges, centre cells, field planes, merge words, host outputs
     B_PAIRS,                        // guesses, rotations, scan poses, beams, ranges, pair lists, the pairs' fields, merge words, host outputs

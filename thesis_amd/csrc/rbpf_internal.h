@@ -368,7 +368,26 @@ struct TrackWalk {
     int32_t* out_idx; double* out_pose;   // [t1 - t0][n], [t1 - t0][n][3]; either may be null
 };
 
+// pose modes (kernels_modes.hip): one workgroup clusters one set of P poses.  The tables of a set, in global scratch:
+// keys u64 [S] | Q u64 [P] | bin root i32 [S] | up i32 [P] | slot i32 [P] | members i32 [P] | bins i32 [P] | label i32 [P]
+static const int MODES_MAX_P = TRACK_SUMMARY_MAX_P;
+inline int modes_slots(int P) { int s = 2; while (s < 2 * P) s *= 2; return s; }   // 2 * next_pow2(P): load factor <= 0.5
+__host__ __device__ inline size_t modes_label_offset(int P, int S) { return (size_t)S * 12 + (size_t)P * 24; }
+__host__ __device__ inline size_t modes_set_bytes(int P, int S) { return (modes_label_offset(P, S) + (size_t)P * 4 + 255) & ~(size_t)255; }
+struct ModesArgs {
+    int P, S;                          // particles of a set; slots of its bin table
+    int n_th, K, mode;                 // heading bins, rows, weights_mode
+    double inv, kth;                   // 1 / bin_xy, n_th / (2 pi): computed once on the host
+    const double* w_raw; const double* w_given;
+    unsigned char* tables;             // [sets][modes_set_bytes]
+    long long* info;                   // [sets][4]
+    double* rows_f; int32_t* rows_i;   // [sets][K][16], [sets][K][4]; both null: no rows
+    int32_t* label;                    // [P] or null: the labels stay in the tables (one set only)
+};
+
 // kernel launchers (one translation unit per kernel family)
+void launch_pose_modes(const DevView& v, const ModesArgs& a, hipStream_t s);
+void launch_track_modes(const TrackLog& g, int t0, int n_sets, const int32_t* d_lineage, const ModesArgs& a, hipStream_t s);   // d_lineage [n_sets][P]
 void launch_track_compose(int P, const int32_t* d_did, const int32_t* d_idx, const int32_t* d_pend, int32_t* d_pend2, hipStream_t s);
 void launch_track_record(const DevView& v, const TrackLog& g, int t, int32_t* d_pend, hipStream_t s);   // record t from the current state; d_pend becomes the identity
 void launch_estimate(const DevView& v, const double* d_given, int mode, double* d_out16, int32_t* d_out4, hipStream_t s);

@@ -203,6 +203,41 @@ class TrajectorySummary(NamedTuple):
     weight_sum: np.ndarray  # [T]
 
 
+class Modes(NamedTuple):
+    """ParticleEngine.pose_modes: the modes of the particle cloud (include/rbpf_hip.h, rbpf_pose_modes), heaviest
+    first, k = min(count, max_modes) of them.  numpy arrays; with device=True torch tensors on the GPU, count / bins / used
+    0-d tensors, and all max_modes rows (NaN / -1 / 0 behind `count`): slicing to k would need a host read."""
+    count: Any             # modes in the cloud, also those beyond max_modes
+    bins: Any              # occupied bins
+    used: Any              # contributing particles
+    poses: Any             # [k, 3] weighted mean x, y and circular mean heading of each mode
+    covs: Any              # [k, 3, 3]
+    share: Any             # [k] the mode's share of the weight, Q_c / Q_total
+    size: Any              # [k] int32 members
+    mode_bins: Any         # [k] int32 bins
+    root: Any              # [k] int32 the smallest member index: the mode's label
+    best: Any              # [k] int32 the first argmax of the raw weights among the members
+    resultant: Any         # [k]
+    n_eff: Any             # [k]
+    weight_sum: Any        # [k]
+    labels: Any = None     # int32 [P]: the root of each particle's mode, -1 for a particle that contributes nothing; None unless asked
+
+    def estimate(self, i: int) -> "Estimate":
+        """Mode i as an Estimate: what estimate() returns over the mode's members alone."""
+        h = (lambda x: x.cpu().numpy()) if hasattr(self.poses, "cpu") else np.asarray
+        return Estimate(pose=h(self.poses[i]).copy(), cov=h(self.covs[i]).copy(), resultant=float(self.resultant[i]), n_eff=float(self.n_eff[i]),
+                        best=int(self.best[i]), n_used=int(self.size[i]), weight_sum=float(self.weight_sum[i]))
+
+
+class TrajectoryModes(NamedTuple):
+    """ParticleEngine.trajectory_modes: the modes of the current particles' ancestors at every record, K = max_modes columns
+    (NaN / 0 behind `count`)."""
+    count: np.ndarray      # [T] int64
+    share: np.ndarray      # [T, K]
+    poses: np.ndarray      # [T, K, 3]
+    size: np.ndarray       # [T, K] int32
+
+
 def _cov_from_rows(f: np.ndarray) -> np.ndarray:
     """[..., 16] estimate rows -> [..., 3, 3] symmetric covariances."""
     return f[..., [3, 4, 5, 4, 6, 7, 5, 7, 8]].reshape(f.shape[:-1] + (3, 3))
@@ -1225,6 +1260,58 @@ class ParticleEngine:
         self._check(self._lib.rbpf_estimate(self._h, mode, None if w is None else _dp(w), _dp(f), _ip(i)))
         return Estimate(pose=f[0:3].copy(), cov=_cov_from_rows(f), resultant=float(f[9]), n_eff=float(f[11]), best=int(i[0]),
                         n_used=int(i[1]), weight_sum=float(f[10]))
+
+    def pose_modes(self, bin_xy: float = 0.5, heading_bins: int = 36, max_modes: int = 8, weights="resample", labels: bool = False,
+                   device: bool = False) -> Modes:
+        """The modes of the particle cloud, clustered on the device: connected components of the occupied bins of a lattice of
+        bin_xy metres and 2 pi / heading_bins (26-neighbourhood, cyclic heading), heaviest first, one estimate per mode
+        (Modes; `weights` as estimate()).  While the filter is multimodal - after relocalize(), in a symmetric building -
+        estimate() averages hypotheses; this tells them apart, and locate.converged(modes) says when one is left.  Needs no
+        tracking, changes nothing.  device=True: torch tensors, written in stream order without a host wait."""
+        mode, w = self._weights_arg(weights)
+        bxy, n_th, K = float(bin_xy), int(heading_bins), int(max_modes)
+        Kc = min(max(K, 0), _lib.RBPF_MODES_MAX)          # bad parameters are the library's to refuse
+        cur, same_stream = None, False
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            cur = torch.cuda.current_stream(dev)
+            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
+            info = torch.empty(4, dtype=torch.int64, device=dev)
+            f = torch.empty((Kc, _lib.RBPF_EST_F64), dtype=torch.float64, device=dev)
+            i = torch.empty((Kc, _lib.RBPF_EST_I32), dtype=torch.int32, device=dev)
+            lab = torch.empty(self.P, dtype=torch.int32, device=dev) if labels else None
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() or 1)
+            if not same_stream:
+                cur.synchronize()                        # the tensors were allocated in torch's stream order
+        else:
+            info, f, i = np.empty(4, dtype=np.int64), np.empty((Kc, _lib.RBPF_EST_F64)), np.empty((Kc, _lib.RBPF_EST_I32), dtype=np.int32)
+            lab = np.empty(self.P, dtype=np.int32) if labels else None
+            ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 1)
+        self._check(self._lib.rbpf_pose_modes(self._h, mode, None if w is None else _dp(w), bxy, n_th, K,
+                                              _lib.RBPF_MODES_DEVICE_OUT if device else 0, ptr(info), ptr(f), ptr(i), ptr(lab)))
+        if device and not same_stream:
+            self.synchronize()
+        k = Kc if device else min(int(info[0]), Kc)
+        f, i = f[:k], i[:k]
+        return Modes(count=info[0] if device else int(info[0]), bins=info[1] if device else int(info[1]),
+                     used=info[2] if device else int(info[2]), poses=f[:, 0:3], covs=_cov_from_rows(f), share=f[:, 13], size=i[:, 1],
+                     mode_bins=i[:, 2], root=i[:, 3], best=i[:, 0], resultant=f[:, 9], n_eff=f[:, 11], weight_sum=f[:, 10], labels=lab)
+
+    def trajectory_modes(self, bin_xy: float = 0.5, heading_bins: int = 36, max_modes: int = 4, weights="resample", t0: int = 0,
+                         t1: Optional[int] = None) -> TrajectoryModes:
+        """The smoothed form of pose_modes, the companion of trajectory_summary: per record the modes of the poses the current
+        particles' ancestors had there, with the FINAL weights.  Where n_alive of the summary says how many lineages survive,
+        count says where along the path they still disagree by more than a bin.  P <= 65536."""
+        if t1 is None:
+            t1 = self.track_info()["n_records"]
+        mode, w = self._weights_arg(weights)
+        bxy, n_th, K = float(bin_xy), int(heading_bins), int(max_modes)
+        T, Kc = max(int(t1) - int(t0), 0), min(max(K, 0), _lib.RBPF_MODES_MAX)
+        info, f, i = np.empty((T, 4), dtype=np.int64), np.empty((T, Kc, _lib.RBPF_EST_F64)), np.empty((T, Kc, _lib.RBPF_EST_I32), dtype=np.int32)
+        vp = lambda a: C.c_void_p(a.ctypes.data or 1)
+        self._check(self._lib.rbpf_track_modes(self._h, int(t0), int(t1), mode, None if w is None else _dp(w), bxy, n_th, K, vp(info), vp(f), vp(i)))
+        return TrajectoryModes(count=info[:, 0].copy(), share=f[:, :, 13].copy(), poses=f[:, :, 0:3].copy(), size=i[:, :, 1].copy())
 
     def track(self, capacity: int, imu: bool = False, scan: bool = True):
         """Starts the trajectory log on the device: room for `capacity` records of every particle's pose and parent (28 bytes per

@@ -71,3 +71,21 @@ def seed_particles(hyp: Hypotheses, n_particles: int, cell_size: float, n_rot: i
     rng = np.random.Generator(np.random.PCG64(seed))
     j = rng.uniform(-0.5, 0.5, size=poses.shape)
     return poses + j * np.array([cell_size, cell_size, TWO_PI / n_rot])
+
+
+def converged(modes, share: float = 0.95) -> bool:
+    """True iff the cloud has a mode and the heaviest one (ParticleEngine.pose_modes orders them) holds at least `share` of
+    the weight."""
+    return int(modes.count) > 0 and float(modes.share[0]) >= share
+
+
+def kld_size(n_bins: int, epsilon: float = 0.05, z: float = 2.326) -> int:
+    """Fox's KLD-sampling bound: the particles that keep the KL divergence of the sampled from the true posterior below `epsilon`
+    with the confidence of the upper normal quantile `z` (2.326: 99 %), when the posterior occupies `n_bins` bins (Modes.bins):
+    ceil((k - 1) / (2 epsilon) * (1 - 2 / (9 (k - 1)) + sqrt(2 / (9 (k - 1))) z)^3), and 1 for n_bins <= 1.  It only reports:
+    the engine's particle count is fixed."""
+    k = int(n_bins)
+    if k <= 1:
+        return 1
+    a = 2.0 / (9.0 * (k - 1))
+    return int(np.ceil((k - 1) / (2.0 * epsilon) * (1.0 - a + np.sqrt(a) * z) ** 3))

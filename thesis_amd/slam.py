@@ -216,6 +216,10 @@ class ParticleFilter:
         out.reverse()
         return out
 
+    def pose_modes(self, **kw):
+        """The modes of the particle cloud, one estimate a mode (ParticleEngine.pose_modes)."""
+        return self.engine.pose_modes(**kw)
+
     def close(self):
         self.engine.close()
 
