@@ -121,6 +121,13 @@ typedef struct rbpf_counters {
     uint64_t map_updates_skipped; /* particles a map update left out because the resample that followed discarded them
                                      (rbpf_resample right behind rbpf_scan_update); ray_cells_visited, cells_written and
                                      the other map-update tallies do not count them                                */
+    uint64_t map_pool_cells;      /* flagged cells folded by a wave from a fixed-capacity list: global-index kernel, cells
+                                     whose list outgrew the 16-event per-pair list and moved to a pool list of 64 (a list
+                                     moves when two more events would not fit, so cells that end with 15 or 16 events
+                                     can count); 128x128-window kernel, buckets of 17 .. cap events.  Longer lists
+                                     count in slow_cells                                                             */
+    uint64_t map_near_cells;      /* global-index kernel: flagged cells within 16 steps of the sensor folded from the
+                                     second walk of the block round the start cell (not those handed to slow_cells)  */
 } rbpf_counters;
 
 /* ---- lifecycle ------------------------------------------------------------------------- */

@@ -12,11 +12,10 @@ GPU only:  python -m pytest tests -m gpu"""
 import numpy as np
 import pytest
 
-from oracle import rbpf_oracle as orc
+from tests.helpers import run_map_case
 
 pytestmark = pytest.mark.gpu
 
-Q = 0.1
 FOLD_BEAMS = 32          # consecutive beams per cell that the register fold holds (FOLD_SPAN / 2 in kernels_mapev.hip)
 
 
@@ -29,52 +28,8 @@ def ev_engine(monkeypatch):
 
 
 def run_case(engine, poses, scans, angles, cell_size=0.05, pool_tiles=32):
-    """Two (or more) scans into an engine and into one oracle map per DISTINCT pose; every tile byte and the read-out at
-    the flagged cells compared.  scans: list of range arrays, angles: one array or one per scan.  Returns the counters."""
-    poses = np.asarray(poses, dtype=np.float64)
-    P = len(poses)
-    angs = angles if isinstance(angles, list) else [angles] * len(scans)
-    B = max(len(r) for r in scans)
-    e = engine.ParticleEngine(P, max_beams=B, cell_size=cell_size, pool_tiles=pool_tiles)
-    maps = {}
-    for p in range(P):
-        maps.setdefault(tuple(float(v) for v in poses[p]), orc.OracleHybridMap(cell_size))
-    for r, a in zip(scans, angs):
-        e.set_scan(r, a)
-        e.map_update(poses)
-        sx, sy = orc.scan_xy(r, a)
-        for pose, hm in maps.items():
-            hm.update(pose, sx, sy)
-    c = e.counters()
-    print({k: c[k] for k in ("map_events", "map_event_overflows", "map_windows", "window_fallbacks", "slow_cells", "fallback_reasons")})
-    dim = e.dim
-    for p in range(P):
-        pose = tuple(float(v) for v in poses[p])
-        hm = maps[pose]
-        got = {cxy: cells for cxy, cells in e.tiles(p)}
-        assert set(got.keys()) == {(float(t.cx), float(t.cy)) for t in hm.tiles}
-        for t in hm.tiles:
-            q = np.rint(t.map / Q)
-            assert np.max(np.abs(t.map - q * Q)) < 1e-9
-            have = got[(float(t.cx), float(t.cy))]
-            assert have.shape == (dim, dim)
-            if not np.array_equal(have, q.astype(np.int8)):
-                bad = np.argwhere(have != q.astype(np.int8))
-                raise AssertionError(f"particle {p} tile ({t.cx}, {t.cy}): {len(bad)} cells differ, first {bad[:5].tolist()} "
-                                     f"got {have[tuple(bad[0])]} want {q[tuple(bad[0])]}")
-        # read-out at the flagged cells: the last scan's end points and the points one cell short of them
-        sx, sy = orc.scan_xy(scans[-1], angs[-1])
-        rr = np.hypot(sx, sy)
-        keep = rr > 1e-9
-        short = np.where(keep, np.maximum(rr - cell_size, 0.0) / np.where(keep, rr, 1.0), 0.0)
-        gx, gy = orc.transform(np.concatenate([sx, sx * short]), np.concatenate([sy, sy * short]), pose)
-        pts = np.stack([gx, gy], axis=1)
-        vals, none = e.get_odds_at(p, pts)
-        want = [hm.get_odds_at(float(x), float(y)) for x, y in pts]
-        assert np.array_equal(none, np.array([w is None for w in want]))
-        np.testing.assert_allclose(vals[~none], np.array([w for w in want if w is not None], dtype=np.float64), rtol=0, atol=1e-9)
-    e.close()
-    return c
+    """tests.helpers.run_map_case with the Python oracle at every size.  Returns the counters."""
+    return run_map_case(engine, poses, scans, angles, cell_size=cell_size, pool_tiles=pool_tiles, c_oracle_above=10 ** 9)
 
 
 def bundle(n, centre, width=2e-4):

@@ -61,6 +61,7 @@ class RbpfCounters(C.Structure):
         ("fallback_reasons", C.c_uint64), ("ms_ndt", C.c_double), ("stamp7", C.c_uint64), ("map_windows", C.c_uint64),
         ("fallback_geometry", C.c_uint64), ("fallback_bound", C.c_uint64), ("fallback_tables", C.c_uint64),
         ("map_events", C.c_uint64), ("map_event_overflows", C.c_uint64), ("map_updates_skipped", C.c_uint64),
+        ("map_pool_cells", C.c_uint64), ("map_near_cells", C.c_uint64),
     ]
 
 

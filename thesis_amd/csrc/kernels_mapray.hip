@@ -143,6 +143,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
     __shared__ int s_fan[4];
     __shared__ int s_wsum[RB / 64];
     __shared__ int s_nslow, s_written, s_nspec, s_nact, s_exact, s_nnear, s_npool, s_wbq;
+    __shared__ int s_npoolf, s_nnearf;                // cells folded from a pool list / from the block's second walk (tallies only)
     __shared__ int s_lcnt[MAXLEV + 1], s_lfill[MAXLEV + 1], s_nk[MAXLEV + 2], s_lp[MAXLEV + 3], s_nlev;
     __shared__ unsigned long long s_cells;
     __shared__ double s_sincos[2];
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
     const int fxl = x0 - v.reach - 2, fyl = y0 - v.reach - 2, nfx = 2 * v.reach + 5;
     if (tid == 0) {
         s_fan[0] = x0; s_fan[1] = x0; s_fan[2] = y0; s_fan[3] = y0;
-        s_cells = 0; s_fb = 0; s_written = 0; s_nslow = 0; s_nspec = 0; s_nact = 0; s_exact = 0; s_nnear = 0; s_npool = 0;
+        s_cells = 0; s_fb = 0; s_written = 0; s_nslow = 0; s_nspec = 0; s_nact = 0; s_exact = 0; s_nnear = 0; s_npool = 0; s_npoolf = 0; s_nnearf = 0;
     }
     for (int i = tid; i < LL; i += RB) { s_need[i] = 0; s_tab[i] = tab[i]; }
     bins32[tid] = 0;
@@ -650,7 +651,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
                 g.a = __shfl_down(fc.a, off, 64); g.lo = __shfl_down(fc.lo, off, 64); g.hi = __shfl_down(fc.hi, off, 64);
                 if ((lane & (2 * off - 1)) == 0) fc = caf_then(fc, g);
             }
-            if (lane == 0) oval[key] = (uint8_t)(caf_apply(fc, (int)(int8_t)oldv8[key]) - v.cc.vmin);
+            if (lane == 0) { oval[key] = (uint8_t)(caf_apply(fc, (int)(int8_t)oldv8[key]) - v.cc.vmin); atomicAdd(&s_npoolf, 1); }
         }
     }
     // ---- pass 2b: cells other classes reach too; one lane per (cell, other class) ----
@@ -827,7 +828,7 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
                         g.a = __shfl_down(fc.a, off, 64); g.lo = __shfl_down(fc.lo, off, 64); g.hi = __shfl_down(fc.hi, off, 64);
                         if ((lane & (2 * off - 1)) == 0) fc = caf_then(fc, g);
                     }
-                    if (lane == 0) oval[key] = (uint8_t)(caf_apply(fc, val0) - v.cc.vmin);
+                    if (lane == 0) { oval[key] = (uint8_t)(caf_apply(fc, val0) - v.cc.vmin); atomicAdd(&s_nnearf, 1); }
                 }
             }
             BAR_LDS();
@@ -885,6 +886,8 @@ __global__ __launch_bounds__(RB) void map_update_ray_kernel(DevView v, const int
             BAR_LDS();
         }
         if (tid == 0 && nslow) atomicAdd(&v.stats[ST_SLOW_CELLS], (unsigned long long)nslow);
+        if (tid == 0 && s_npoolf) atomicAdd(&v.stats[ST_POOL_CELLS], (unsigned long long)s_npoolf);
+        if (tid == 0 && s_nnearf) atomicAdd(&v.stats[ST_NEAR_CELLS], (unsigned long long)s_nnearf);
     }
     STAMP(3);
 

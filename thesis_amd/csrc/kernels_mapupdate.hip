@@ -115,7 +115,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
     __shared__ int s_x0, s_y0, s_skip;
     __shared__ int s_need[49], s_tab[49];
     __shared__ int s_fan[4];                       // ray fan bounding box: gx min, gx max, gy min, gy max
-    __shared__ int s_nflag, s_bb[4], s_written, s_nslow, s_nbig, s_nchunk, s_irreg, s_wsum[MU_BLOCK / 64], s_tot_written, s_tot_slow;
+    __shared__ int s_nflag, s_bb[4], s_written, s_nslow, s_nbig, s_nchunk, s_irreg, s_wsum[MU_BLOCK / 64], s_tot_written, s_tot_slow, s_tot_big;
     static_assert(WIN * WIN / 32 == MU_BLOCK, "one flag word per thread");
     __shared__ unsigned long long s_cells;
 
@@ -138,7 +138,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
         if (ok && !lut_covers(v, x0, y0, v.reach)) { atomicCAS(v.err, 0, RBPF_ERANGE); ok = false; }
         s_skip = ok ? 0 : 1;
         s_fan[0] = x0; s_fan[1] = x0; s_fan[2] = y0; s_fan[3] = y0;
-        s_cells = 0; s_tot_written = 0; s_tot_slow = 0;
+        s_cells = 0; s_tot_written = 0; s_tot_slow = 0; s_tot_big = 0;
     }
     for (int i = tid; i < LL; i += MU_BLOCK) { s_need[i] = 0; s_tab[i] = tab[i]; }
     __syncthreads();
@@ -533,6 +533,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
                     if (lane == 0) cnt16_set(s.cnt, c, 0x8000u | ((uint32_t)val & 0xFFu));
                 }
                 if (tid == 0 && nslow) s_tot_slow += nslow;
+                if (tid == 0 && nbig) s_tot_big += nbig;
             }
             BAR_LDS();
             STAMP(4);
@@ -615,6 +616,7 @@ __device__ __forceinline__ void map_update_particle(const DevView& v, bool only)
         if (s_cells) atomicAdd(&v.stats[ST_RAY_CELLS], s_cells);
         if (s_tot_written) atomicAdd(&v.stats[ST_CELLS_WRITTEN], (unsigned long long)s_tot_written);
         if (s_tot_slow) atomicAdd(&v.stats[ST_SLOW_CELLS], (unsigned long long)s_tot_slow);
+        if (s_tot_big) atomicAdd(&v.stats[ST_POOL_CELLS], (unsigned long long)s_tot_big);
         STAMP_FLUSH();
     }
 }

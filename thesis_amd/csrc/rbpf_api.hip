@@ -480,6 +480,7 @@ int rbpf_get_counters(rbpf_handle* h, rbpf_counters* out) {
     }
     c.map_windows = st[ST_MAP_WINDOWS];
     c.map_updates_skipped = st[ST_MU_SKIPPED];
+    c.map_pool_cells = st[ST_POOL_CELLS]; c.map_near_cells = st[ST_NEAR_CELLS];
     if (h->profiling) {
         double* dst[5] = {&c.ms_raycast, &c.ms_weight, &c.ms_resample, &c.ms_match, &c.ms_ndt};
         for (int k = 0; k < 5; ++k) {

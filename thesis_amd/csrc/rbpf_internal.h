@@ -114,7 +114,8 @@ enum { ST_RAY_CELLS = 0, ST_CELLS_WRITTEN = 1, ST_GATHERS = 2, ST_SLOW_CELLS = 3
        ST_COPIES = 4, ST_COPY_BYTES = 5, ST_WINDOW_FALLBACKS = 6, ST_FALLBACK_REASONS = 7,
        /* 8..15: phase stamps of a -DRBPF_STAMPS build */
        ST_NDT_RUNS = 16, ST_NDT_EVALS = 17, ST_NDT_ACCEPTED = 18, ST_MATCH_SHARED = 19, ST_MAP_WINDOWS = 20,
-       ST_FB_BOUND = 21, ST_FB_TABLES = 22, ST_MAP_EVENTS = 23, ST_EV_OVERFLOWS = 24, ST_MU_SKIPPED = 25, ST_COUNT = 28 };   // ST_FALLBACK_REASONS (7) counts reason 1 (geometry / index map)
+       ST_FB_BOUND = 21, ST_FB_TABLES = 22, ST_MAP_EVENTS = 23, ST_EV_OVERFLOWS = 24, ST_MU_SKIPPED = 25,
+       ST_POOL_CELLS = 26, ST_NEAR_CELLS = 27, ST_COUNT = 28 };   // ST_FALLBACK_REASONS (7) counts reason 1 (geometry / index map)
 
 // map rendering (kernels_render.hip): one workgroup per job, up to 16 storage rows x 256 storage columns of one lattice tile
 struct RenderJob {

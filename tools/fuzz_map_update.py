@@ -89,7 +89,7 @@ def run(N=120, SEED=1, kernels=None, verbose=True):
       c = e.counters()
       e.close()
       if verbose and case % 20 == 0:
-          print("case", case, "ok so far, bad", bad, "cs", cs, "B", B, kernel, "fallbacks", c["window_fallbacks"], "reasons %x" % c["fallback_reasons"], "windows", c["map_windows"], "events", c["map_events"], "ev overflows", c["map_event_overflows"], flush=True)
+          print("case", case, "ok so far, bad", bad, "cs", cs, "B", B, kernel, "fallbacks", c["window_fallbacks"], "reasons %x" % c["fallback_reasons"], "windows", c["map_windows"], "events", c["map_events"], "ev overflows", c["map_event_overflows"], "pool cells", c["map_pool_cells"], "near cells", c["map_near_cells"], flush=True)
   if saved_env is None: os.environ.pop("RBPF_MAP_KERNEL", None)
   else: os.environ["RBPF_MAP_KERNEL"] = saved_env
   if verbose: print("done", N, "cases, mismatching:", bad)
