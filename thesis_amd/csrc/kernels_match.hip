@@ -61,6 +61,7 @@ struct MatchArgs {
     int n_coarse_rot;           // rotations on each side at the coarse level
     int cap_sel;                // LDS capacity for selected beams
     int sc_cap;                 // entries of the score table in LDS (the coarse level runs in groups of rotations that fit)
+    int p0;                     // first particle of the launch: workgroup b works on particle p0 + b (0 in the stateless twin)
     double cell_off;            // 0.5 in the stateless twin: its points are snapped to cell corners (hybridmap.py:226-227)
     int ndt;                    // 0 off; 1 matchScanCustom.m:38-44 acceptance; 2 take every valid NDT pose (diagnostic)
     int ndt_nc;                 // NDT cell edge in matcher cells (0.1 m, matchScanCustom.m:37); < 2: no cell can hold 3 points
@@ -165,7 +166,7 @@ __device__ inline void match_frame(const DevView& v, const MatchArgs& a, int p, 
 
 __global__ __launch_bounds__(MBLOCK) void match_kernel(DevView v, MatchArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int N = a.N, W = N >> 5, tid = threadIdx.x, p = blockIdx.x;
+    const int N = a.N, W = N >> 5, tid = threadIdx.x, p = a.p0 + blockIdx.x;
     // An exact duplicate (a copy made by the last resample: same pose, covariance and map) would repeat its
     // representative's search bit for bit; the proposal kernel reads the representative's row instead.
     // (the loads the set-up needs are issued together with the duplicate test's: one round trip to memory instead of three)
@@ -889,7 +890,7 @@ size_t ndt_lds_bytes(int N, int B) { (void)B; return (size_t)(N + 2) * (N / 32 +
 // (beam, grid) pairs and a fixed-order reduction, so results do not depend on wave timing.
 __global__ __launch_bounds__(NBLOCK, 4) void ndt_kernel(DevView v, MatchArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int N = a.N, W = N >> 5, tid = threadIdx.x, p = blockIdx.x;
+    const int N = a.N, W = N >> 5, tid = threadIdx.x, p = a.p0 + blockIdx.x;
     uint32_t* occ = reinterpret_cast<uint32_t*>(smem);
     const float* __restrict__ bx = a.sel_x;     // beams stay in global memory (the same 8.6 KB for every workgroup: L1/L2 hits)
     const float* __restrict__ by = a.sel_y;
@@ -1108,13 +1109,14 @@ void launch_native_sincosf(const float* d_x, int n, float* d_s, float* d_c, hipS
     if (n > 0) hipLaunchKernelGGL(native_sincosf_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_x, n, d_s, d_c);
 }
 
-// t0 / t1 (or nullptr): timing events that take the kernel's own start and end (carried by its dispatch: hipExtLaunchKernelGGL)
+// t0 / t1 (or nullptr): timing events that take the kernel's own start and end (carried by its dispatch: hipExtLaunchKernelGGL);
+// t1 alone: an event another stream waits on for this kernel's end
 static void launch_match(const DevView& v, const MatchArgs& a_in, int grid, size_t lds, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
     MatchArgs a = a_in;
     a.sc_cap = match_sc_capacity(a.N, a.cap_sel, lds);
     static size_t lds_set[MAX_DEVICES] = {};
     ensure_dynamic_lds(reinterpret_cast<const void*>(match_kernel), lds, lds_set);
-    if (t0 && t1) hipExtLaunchKernelGGL(match_kernel, dim3(grid), dim3(MBLOCK), lds, s, t0, t1, 0, v, a);
+    if (t0 || t1) hipExtLaunchKernelGGL(match_kernel, dim3(grid), dim3(MBLOCK), lds, s, t0, t1, 0, v, a);
     else hipLaunchKernelGGL(match_kernel, dim3(grid), dim3(MBLOCK), lds, s, v, a);
 }
 
@@ -1125,27 +1127,29 @@ static void launch_ndt(const DevView& v, const MatchArgs& a, int grid, hipStream
     size_t lds = ndt_lds_bytes(a.N, a.cap_sel);
     static size_t lds_set[MAX_DEVICES] = {};
     ensure_dynamic_lds(reinterpret_cast<const void*>(ndt_kernel), lds, lds_set);
-    if (t0 && t1) hipExtLaunchKernelGGL(ndt_kernel, dim3(grid), dim3(NBLOCK), lds, s, t0, t1, 0, v, a);
+    if (t0 || t1) hipExtLaunchKernelGGL(ndt_kernel, dim3(grid), dim3(NBLOCK), lds, s, t0, t1, 0, v, a);
     else hipLaunchKernelGGL(ndt_kernel, dim3(grid), dim3(NBLOCK), lds, s, v, a);
 }
 
 // stage 1: the grid search (match_kernel); stage 2: the NDT refinement (ndt_kernel) -- two calls so that the host can
-// time them apart.  Returns whether the NDT stage is active for this configuration.
+// time them apart; stage 0: no launch.  Particles [p0, p0 + n) of the SoA state (stride v.P); n = 0 launches nothing.
+// Returns whether the NDT stage is active for this configuration.
 bool launch_match_particles(const DevView& v, int mode, const double* d_ref, int n_ref, double* d_out, int N, int ds,
-                            double mcs, double d0, int ncr, double max_range, int cap_sel, size_t lds, int stage, hipStream_t s,
-                            hipEvent_t t0, hipEvent_t t1) {
+                            double mcs, double d0, int ncr, double max_range, int cap_sel, size_t lds, int stage, int p0, int n,
+                            hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     MatchArgs a;
     memset(&a, 0, sizeof(a));
     a.mode = mode; a.single = 0; a.ref_xy = d_ref; a.n_ref = n_ref; a.out = d_out;
     a.N = N; a.ds = ds; a.mcs = mcs; a.d0 = d0; a.rot_range = 3.141592653589793 / 6; a.max_range = max_range;
     a.sel_x = mode ? v.asel_x : v.msel_x; a.sel_y = mode ? v.asel_y : v.msel_y; a.n_sel = mode ? v.n_asel : v.n_msel;
-    a.n_coarse_rot = ncr; a.cap_sel = cap_sel;
+    a.n_coarse_rot = ncr; a.cap_sel = cap_sel; a.p0 = p0;
     a.ndt = v.ndt_refine; a.ndt_nc = ndt_cells(mcs); a.ndt_max_iter = 500;
     a.dup_of = v.dups_valid ? v.dup_of : nullptr;
     const bool ndt = a.ndt && a.ndt_nc >= 2 && v.ndt_occ;
     if (ndt) { a.ndt_occ = v.ndt_occ; a.ndt_aux = v.ndt_aux; }
-    if (stage == 1) launch_match(v, a, v.P, lds, s, t0, t1);
-    if (stage == 2 && ndt) launch_ndt(v, a, v.P, s, t0, t1);
+    if (n <= 0) return ndt;
+    if (stage == 1) launch_match(v, a, n, lds, s, t0, t1);
+    if (stage == 2 && ndt) launch_ndt(v, a, n, s, t0, t1);
     return ndt;
 }
 

@@ -11,6 +11,8 @@
 // A particle whose matcher covariance holds a NaN, or has an eigenvalue below -eps, takes the reference's fallback (robot.py:73-78):
 // its pose is kept, its map is updated at that pose and its weight is incremented AFTER the map
 // update by bad_weight_kernel.
+#include <hip/hip_ext.h>
+
 #include "rbpf_internal.h"
 #include "rbpf_device.h"
 
@@ -89,6 +91,7 @@ struct ProposeArgs {
     uint8_t* bad;               // [P] 1 = NaN covariance (robot.py:73)
     uint64_t seed; uint32_t stream;
     double* dbg_w;              // optional [P][K] raw sample weights (tests), or nullptr
+    int p0, n;                  // the launch covers particles [p0, p0 + n) of the SoA state (stride DevView::P)
 };
 
 
@@ -98,8 +101,8 @@ struct ProposeArgs {
 // first wave used to run alone (a third of that kernel's instructions).
 static const int PREP_W = 24;       // doubles per particle: U[9], A[9], mean[3], log c, bad, -
 __global__ __launch_bounds__(64) void propose_prep_kernel(DevView v, ProposeArgs a) {
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= v.P) return;
+    const int i = blockIdx.x * 64 + threadIdx.x, p = a.p0 + i;
+    if (i >= a.n) return;
     const double* m = a.match + (size_t)(a.match_of ? a.match_of[p] : p) * 13;
     double* o = v.prop_prep + (size_t)p * PREP_W;
     bool bad = false;
@@ -130,8 +133,8 @@ __global__ __launch_bounds__(64) void propose_prep_kernel(DevView v, ProposeArgs
 //      coordinates.  (In the weighting kernel these few hundred float64 instructions were a serial prologue of 30 lanes.)
 static const int SAMP_W = 256;      // doubles per particle: cos[32], sin[32], x[32], y[32], theta[32], motion pdf[32], float4 frame[32]
 __global__ __launch_bounds__(256) void propose_samples_kernel(DevView v, ProposeArgs a) {
-    const int gid = blockIdx.x * 256 + threadIdx.x, p = gid >> 5, k = gid & 31, K = v.K;
-    if (p >= v.P || k >= K) return;
+    const int gid = blockIdx.x * 256 + threadIdx.x, p = a.p0 + (gid >> 5), k = gid & 31, K = v.K;
+    if ((gid >> 5) >= a.n || k >= K) return;
     const double* pr = v.prop_prep + (size_t)p * PREP_W;
     if (pr[22] != 0.0) return;                                       // robot.py:73-78: no proposal for this particle
     const double mean[3] = {pr[18], pr[19], pr[20]};
@@ -305,7 +308,7 @@ __global__ __launch_bounds__(BLOCK) void propose_weight_kernel(DevView v, Propos
     __shared__ int s_bad, s_nredo[2];
     __shared__ uint32_t s_redo[REDO_CAP];
     __shared__ __align__(16) float s_bx[WB_CAP], s_by[WB_CAP];
-    const int p = blockIdx.x, tid = threadIdx.x, K = v.K;
+    const int p = a.p0 + blockIdx.x, tid = threadIdx.x, K = v.K;
     long long st_prev = clock64();
     if (tid == 0) { s_nredo[0] = 0; s_nredo[1] = 0; }
     const int LL = v.L * v.L;
@@ -438,12 +441,17 @@ __global__ __launch_bounds__(BLOCK) void bad_weight_kernel(DevView v, const uint
     nan_branch_weight(v, blockIdx.x, threadIdx.x, BLOCK);
 }
 
+// frame, samples and weighting of particles [p0, p0 + n) (the random streams are keyed by the global particle id, whatever the
+// range); n = 0 launches nothing.  done (or nullptr): an event another stream waits on for the weighting kernel's end, carried
+// by that kernel's dispatch
 void launch_propose_weight(const DevView& v, const double* d_match, const int32_t* d_match_of, const double* d_guesses, uint8_t* d_bad,
-                           uint64_t seed, uint32_t stream, double* d_dbg_w, hipStream_t s) {
-    ProposeArgs a{d_match, d_match_of, d_guesses, d_bad, seed, stream, d_dbg_w};
-    hipLaunchKernelGGL(propose_prep_kernel, dim3((v.P + 63) / 64), dim3(64), 0, s, v, a);
-    hipLaunchKernelGGL(propose_samples_kernel, dim3((v.P * 32 + 255) / 256), dim3(256), 0, s, v, a);
-    hipLaunchKernelGGL(propose_weight_kernel, dim3(v.P), dim3(BLOCK), 0, s, v, a);
+                           uint64_t seed, uint32_t stream, double* d_dbg_w, int p0, int n, hipStream_t s, hipEvent_t done) {
+    if (n <= 0) return;
+    ProposeArgs a{d_match, d_match_of, d_guesses, d_bad, seed, stream, d_dbg_w, p0, n};
+    hipLaunchKernelGGL(propose_prep_kernel, dim3((n + 63) / 64), dim3(64), 0, s, v, a);
+    hipLaunchKernelGGL(propose_samples_kernel, dim3((n * 32 + 255) / 256), dim3(256), 0, s, v, a);
+    if (done) hipExtLaunchKernelGGL(propose_weight_kernel, dim3(n), dim3(BLOCK), 0, s, nullptr, done, 0, v, a);
+    else hipLaunchKernelGGL(propose_weight_kernel, dim3(n), dim3(BLOCK), 0, s, v, a);
 }
 void launch_bad_weight(const DevView& v, const uint8_t* d_bad, hipStream_t s) {
     hipLaunchKernelGGL(bad_weight_kernel, dim3(v.P), dim3(BLOCK), 0, s, v, d_bad);

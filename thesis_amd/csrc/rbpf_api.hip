@@ -89,6 +89,11 @@ static int check_device_error(rbpf_handle* h) {
 }
 
 static bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && strcmp(e, value) == 0; }
+// The scan step's front half runs as two parts on two streams from SCAN_HALVES_MIN_PER_CU particles per CU up to, not including,
+// SCAN_HALVES_END_PER_CU.  Measured on 256 CUs: a gain of 1 to 2.5 % of the step at 3072, 3584, 4096 and 4608
+// particles, nothing at 5120, a loss at 1024, 2048 and from 6144 on - the gain hangs on how the parts' rounds of workgroups
+// fall over the CUs
+static const long long SCAN_HALVES_MIN_PER_CU = 12, SCAN_HALVES_END_PER_CU = 20;
 
 // ---- trajectory log (kernels_track.hip): the pieces the step entry points queue while tracking is on ------------
 // one record from the current state, in stream order.  Log full: an implicit record (a step's own) is dropped and counted, an
@@ -305,6 +310,21 @@ int rbpf_create(const rbpf_config* cfg, rbpf_handle** out) {
                 if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 1; }
                 h->skip_discarded = !env_is("RBPF_SKIP_DISCARDED", "0");   // "0": the held-back map update leaves nobody out (A/B runs, tests)
                 h->hold_back = getenv("RBPF_SKIP_DISCARDED") ? true : (long long)P > 4LL * cus;
+                // the front half of the step as two staggered half-batches (rbpf_host.h: halves_first).  RBPF_SCAN_HALVES=1: always
+                // (tests, A/B runs), =0: never; unset: the size rule measured in DESIGN.md 6
+                const bool halves = env_is("RBPF_SCAN_HALVES", "0") ? false : getenv("RBPF_SCAN_HALVES") ? true : ((long long)P >= SCAN_HALVES_MIN_PER_CU * cus && (long long)P < SCAN_HALVES_END_PER_CU * cus);
+                if (halves) {
+                    int least = 0, greatest = 0;
+                    HIP_TRY(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
+                    HIP_TRY(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, greatest));
+                    // device-side ordering only; two of them ride on a kernel's dispatch, as the timing events do
+                    HIP_TRY(h, h->events.create(&h->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence));
+                    HIP_TRY(h, h->events.create(&h->ev_half_match, hipEventDisableSystemFence));
+                    HIP_TRY(h, h->events.create(&h->ev_half_weight, hipEventDisableSystemFence));
+                    // the first part is the larger one: five eighths measured best at the flagship size; a filter of
+                    // one particle has no second part
+                    h->halves_first = (int)(P - std::max<size_t>(P > 1 ? 1 : 0, 3 * P / 8));
+                }
             }
         }
         ALLOC(h, v.dup_of, P); v.dups_valid = 0;
@@ -364,6 +384,7 @@ int rbpf_destroy(rbpf_handle* h) {
     ON_DEVICE_HELD(h);
     h->mu_pending = false;                                                                // a held-back map update is dropped with the maps
     if (hipStreamSynchronize(h->stream) != hipSuccess) (void)hipGetLastError();          // nullptr: a borrowed null stream
+    if (h->side && hipStreamSynchronize(h->side) != hipSuccess) (void)hipGetLastError();  // (joined into the stream by every step: idle unless a step failed half-way)
     h->each_staging([](Staging& s) { if (s.wait() != hipSuccess) (void)hipGetLastError(); });
     if (h->ev_weights_valid && hipEventSynchronize(h->ev_weights) != hipSuccess) (void)hipGetLastError();
     for (Block& b : h->allocs) b.release();
@@ -373,6 +394,7 @@ int rbpf_destroy(rbpf_handle* h) {
     h->each_staging([](Staging& s) { s.destroy_event(); });
     h->events.destroy();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->side) (void)hipStreamDestroy(h->side);
     (void)hipGetLastError();
     delete h;
     return RBPF_OK;
@@ -636,8 +658,8 @@ int rbpf_map_update(rbpf_handle* h, const double* poses) {
     return check_device_error(h);
 }
 
-static int run_matcher(rbpf_handle* h, int32_t adj, const double* last_scan_xy, int32_t n_last) {
-    DevView& v = h->v;
+// the previous scan of an adj = 1 step: the device-resident one (n_last: its size), or the caller's, uploaded on the stream
+static int stage_last_scan(rbpf_handle* h, int32_t adj, const double* last_scan_xy, int32_t& n_last) {
     if (adj && !last_scan_xy) {                 // the device-resident previous scan (rbpf_refresh_last_scan / rbpf_import_last_scan)
         if (h->n_last_dev < 0) return fail(h, RBPF_ESTATE, "adj = 1 without last_scan_xy needs rbpf_refresh_last_scan first");
         n_last = h->n_last_dev;
@@ -649,17 +671,50 @@ static int run_matcher(rbpf_handle* h, int32_t adj, const double* last_scan_xy, 
         HIP_TRY(h, hipMemcpyAsync(h->d_last_xy, slot, (size_t)n_last * 16, hipMemcpyHostToDevice, h->stream));
         h->rings[R_LAST].submitted(h->stream);
     }
+    return RBPF_OK;
+}
+
+// one matcher stage (1: grid search, 2: NDT) for particles [p0, p0 + n) on stream s; stage 0: whether the NDT stage is active
+static bool match_stage(rbpf_handle* h, int32_t adj, int32_t n_last, int stage, int p0, int n, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+    return launch_match_particles(h->v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
+                                  h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, stage, p0, n, s, t0, t1);
+}
+
+static int run_matcher(rbpf_handle* h, int32_t adj, int32_t n_last) {
     // both stages are one kernel each: their timing events ride on the dispatch and take the kernel's own start and end
     hipEvent_t t0 = nullptr, t1 = nullptr;
     h->prof_take(3, t0, t1);
-    h->match_rows = v.dups_valid ? 2 : 1;
-    const bool ndt = launch_match_particles(v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
-                                            h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, 1, h->stream, t0, t1);
-    if (ndt) {
+    if (match_stage(h, adj, n_last, 1, 0, h->v.P, h->stream, t0, t1)) {
         h->prof_take(4, t0, t1);
-        launch_match_particles(v, adj ? 1 : 0, h->d_last_xy, adj ? n_last : 0, h->d_match, h->mN, h->mds, h->mmcs, h->md0,
-                               h->mncr, h->cfg.match_max_range, h->cfg.max_beams, h->mlds, 2, h->stream, t0, t1);
+        match_stage(h, adj, n_last, 2, 0, h->v.P, h->stream, t0, t1);
     }
+    HIP_TRY(h, hipGetLastError());
+    return RBPF_OK;
+}
+
+// The front half of the step as two staggered half-batches (rbpf_host.h: halves_first): particles [0, n0) on
+// the side stream behind everything the step has queued so far, [n0, P) on the handle's stream.  Nothing couples one
+// particle to another here but an exact duplicate's read of its representative's match row; the representative is the first
+// copy, the lower index, so only the second half can read across the split: its frame kernel waits for the first half's
+// last matcher kernel.  The stream continues behind both halves' weighting.
+static int run_front_halves(rbpf_handle* h, int32_t adj, int32_t n_last, const int32_t* match_of, const double* d_g) {
+    const DevView& v = h->v;
+    const int n0 = std::min(h->halves_first, v.P), n1 = v.P - n0;
+    const bool ndt = match_stage(h, adj, n_last, 0, 0, 0, h->stream);
+    double* dbg = h->prop_capture ? h->d_prop_w : nullptr;
+    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
+    match_stage(h, adj, n_last, 1, 0, n0, h->side, nullptr, ndt || !n1 ? nullptr : h->ev_half_match);
+    if (ndt) match_stage(h, adj, n_last, 2, 0, n0, h->side, nullptr, n1 ? h->ev_half_match : nullptr);
+    launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, dbg, 0, n0, h->side, h->ev_half_weight);
+    HIP_TRY(h, hipGetLastError());
+    if (n1) {
+        match_stage(h, adj, n_last, 1, n0, n1, h->stream);
+        if (ndt) match_stage(h, adj, n_last, 2, n0, n1, h->stream);
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_half_match, 0));
+        launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, dbg, n0, n1, h->stream);
+    }
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_half_weight, 0));
     HIP_TRY(h, hipGetLastError());
     return RBPF_OK;
 }
@@ -692,23 +747,30 @@ int rbpf_scan_update_begin(rbpf_handle* h, int32_t adj, const double* last_scan_
         h->match_rows = 0;
         HIP_TRY(h, hipMemcpyAsync(h->d_match, match_override, 13 * P * 8, hipMemcpyHostToDevice, h->stream));
     } else {
-        int rc = run_matcher(h, adj, last_scan_xy, n_last);
+        const int rc = stage_last_scan(h, adj, last_scan_xy, n_last);
         if (rc) return rc;
+        h->match_rows = v.dups_valid ? 2 : 1;
     }
     const double* d_g = nullptr;
     if (guesses) {
         HIP_TRY(h, hipMemcpyAsync(h->d_guess_full, guesses, P * (size_t)v.K * 3 * 8, hipMemcpyHostToDevice, h->stream));
         d_g = h->d_guess_full;
     }
-    if (!match_override && !guesses) h->prof_begin_chained(1); else h->prof_begin(1);     // right after the matcher's last kernel
     // the matcher ran once per group of exact duplicates (copies made by the last resample, untouched since): every
     // member reads its representative's row; the proposal below is what makes the copies differ, so the groups end here
     const int32_t* match_of = (!match_override && v.dups_valid) ? v.dup_of : nullptr;
     if (h->prop_capture && !h->d_prop_w) ALLOC(h, h->d_prop_w, P * (size_t)v.K);
-    launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, h->prop_capture ? h->d_prop_w : nullptr, h->stream);
+    if (!match_override && h->halves_now()) {
+        const int rc = run_front_halves(h, adj, n_last, match_of, d_g);
+        if (rc) return rc;
+    } else {
+        if (!match_override) { const int rc = run_matcher(h, adj, n_last); if (rc) return rc; }
+        if (!match_override && !guesses) h->prof_begin_chained(1); else h->prof_begin(1);     // right after the matcher's last kernel
+        launch_propose_weight(v, h->d_match, match_of, d_g, h->d_bad, h->cfg.seed, (uint32_t)h->scan_updates, h->prop_capture ? h->d_prop_w : nullptr, 0, v.P, h->stream);
+        h->prof_end(1);
+    }
     h->prop_valid = true; h->prop_captured = h->prop_capture;
     v.dups_valid = 0;
-    h->prof_end(1);
     HIP_TRY(h, hipGetLastError());
     // the event orders an early weight export on ANOTHER stream behind the weighting; recorded only once such a caller exists
     h->ev_weights_valid = false;

@@ -186,6 +186,15 @@ struct rbpf_handle {
     // at sixteen and forty.  hold_back: more than four particles per CU, or RBPF_SKIP_DISCARDED set (tests, A/B
     // runs: 1 holds back whatever the size, 0 does too and leaves nobody out - the same order of launches)
     bool hold_back = false, skip_discarded = true;
+    // The front half of a scan step (matcher, NDT, proposal frame, samples, weighting) as two staggered half-batches: particles
+    // [0, halves_first) on `side`, a stream of the handle's own with the device's highest priority, the rest on `stream`, so that
+    // one half's kernels fill the CUs the other half's kernel leaves idle while its last workgroups drain.
+    // Streams and the three events below are all the synchronisation there is.  halves_first = 0: one stream, as before
+    // (RBPF_SCAN_HALVES=0, or unset below the size rule of rbpf_create); never while the match, ndt or weight family is timed
+    hipStream_t side = nullptr;
+    int halves_first = 0;
+    hipEvent_t ev_fork = nullptr, ev_half_match = nullptr, ev_half_weight = nullptr;   // uploads queued; first half's match rows final; its weighting done
+    bool halves_now() const { return halves_first > 0 && side && !(prof_mask & 0x1Au); }
     // profiling: a ring of HIP-event pairs per kernel family, recorded on the handle's stream
     static const int N_KERN = 5, RING = 512;        // 0 map update, 1 propose/weight, 2 resample, 3 match (grid stage), 4 match (NDT stage)
     std::vector<hipEvent_t> ring[N_KERN][2];

@@ -429,7 +429,7 @@ void launch_unpack(const DevView& v, const ResampleBuffers& b, const void* d_job
 struct PackJobHost { int32_t particle, tile, x0, x1, ya, yb; long long off; };
 struct UnpackJobHost { int32_t particle, pos, has, x0, x1, ya, yb, pad; long long off; };
 void launch_propose_weight(const DevView& v, const double* d_match, const int32_t* d_match_of, const double* d_guesses, uint8_t* d_bad,
-                           uint64_t seed, uint32_t stream, double* d_dbg_w, hipStream_t s);
+                           uint64_t seed, uint32_t stream, double* d_dbg_w, int p0, int n, hipStream_t s, hipEvent_t done = nullptr);
 void launch_bad_weight(const DevView& v, const uint8_t* d_bad, hipStream_t s);
 size_t match_lds_bytes(int N, int B, int n_coarse, int per_rot);
 int match_sc_capacity(int N, int B, size_t lds);
@@ -439,8 +439,8 @@ int ndt_cells(double mcs);
 void match_geometry(const rbpf_config& c, double cell_size, int& N, int& ds, double& mcs, double& d0, int& n_coarse_rot);
 int match_max_coarse(int n_coarse_rot, double max_range_m, double mcs);
 bool launch_match_particles(const DevView& v, int mode, const double* d_ref, int n_ref, double* d_out, int N, int ds,
-                            double mcs, double d0, int ncr, double max_range, int cap_sel, size_t lds, int stage, hipStream_t s,
-                            hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);   // t0 / t1: timing events carried by the stage's kernel dispatch
+                            double mcs, double d0, int ncr, double max_range, int cap_sel, size_t lds, int stage, int p0, int n,
+                            hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);   // t0 / t1: events carried by the stage's kernel dispatch
 void launch_match_single(const DevView& v, const double* d_ref, int n_ref, const double* guess3, const double* range3,
                          const float* d_sel_x, const float* d_sel_y, int n_sel, double* d_out, int N, int ds, double mcs,
                          double d0, int ncr, int cap_sel, size_t lds, uint32_t* d_ndt_occ, double* d_ndt_aux, hipStream_t s);
