@@ -463,13 +463,48 @@ def grid_search(occ, ox, oy, bx, by, guess, rng3, mcs, d0, ncr, cell_off, sincos
         out[3:12] = c.reshape(-1)
         out[12] = 0.5 * full
     return {"out": out, "ok": ok, "coarse": S, "fine": F, "coarse_best": (cir, ctx, cty), "best": best,
-            "full_score": full, "fx": fx, "fy": fy, "gthf": gthf, "ntx": ntx, "nty": nty, "nr": nr, "NP": NP,
+            "full_score": full, "bdx": bdx, "bdy": bdy, "bth": bth,
+            "fx": fx, "fy": fy, "gthf": gthf, "ntx": ntx, "nty": nty, "nr": nr, "NP": NP,
             "edge_effect": bool((S != S_k).any() or (F != F_k).any())}
 
 
 def _ieee_remainder(x: float, y: float) -> float:
     from math import remainder
     return remainder(x, y)
+
+
+def ndt_cells(mcs: float) -> int:
+    """ndt_cells (kernels_match.hip): the NDT cell edge of 0.1 m in matcher cells; below 2 the stage stays off."""
+    return int(floor(NDT_CELL_M / mcs + 0.5))
+
+
+def ndt_stage(occ, ox, oy, pts, r, guess, window, mcs, cell_off, nc, mode):
+    """The second matcher stage as ndt_kernel composes it around ndt_refine (matchScanCustom.m:32-57).  occ, ox, oy: the
+    region's occupancy and origin; pts: beams_in_cells(...); r: grid_search's dict; window: (rx, ry, rotation range) in
+    metres / radians; mode: ndt_refine (1: the reference's acceptance rule, 2: every valid pose is taken).
+    Returns a dict: row (13, what match_results reports), entered, valid, accepted, evals, score, margin
+    (2 * score / grid score: the acceptance rule is margin > 1) and, if entered, start / pose (region cells) and dd (the
+    pose's offset from the guess, metres / radians)."""
+    from math import remainder
+    row = np.array(r["out"], dtype=np.float64)
+    res = {"row": row, "entered": False, "valid": False, "accepted": False, "evals": 0, "score": 0.0, "margin": 0.0}
+    if not (r["ok"] and len(pts) > 0 and nc >= 2):
+        return res
+    gx, gy, gth = float(guess[0]), float(guess[1]), float(guess[2])
+    X0 = gx / mcs - float(ox) + cell_off
+    Y0 = gy / mcs - float(oy) + cell_off
+    start = (X0 + r["bdx"] / mcs, Y0 + r["bdy"] / mcs, gth + r["bth"])
+    p, score, evals = ndt_refine(occ, pts, start, nc, ox, oy)
+    ddx, ddy, ddt = (p[0] - X0) * mcs, (p[1] - Y0) * mcs, p[2] - gth
+    valid = (abs(ddx) < window[0] and abs(ddy) < window[1] and abs(remainder(ddt, 6.283185307179586)) < window[2]
+             and (gx + ddx != 0.0 or gy + ddy != 0.0 or gth + ddt != 0.0))
+    grid_score = 0.5 * float(r["full_score"])
+    accepted = bool(valid and (mode == 2 or 2.0 * score > grid_score))
+    if accepted:
+        row[0], row[1], row[2], row[12] = gx + ddx, gy + ddy, gth + ddt, score
+    res.update(entered=True, valid=bool(valid), accepted=accepted, evals=int(evals), score=float(score),
+               margin=(2.0 * score / grid_score if grid_score > 0 else np.inf), start=start, pose=p, dd=(ddx, ddy, ddt))
+    return res
 
 
 def twin_gate(out13, guess, pose_range):

@@ -2,7 +2,8 @@
 
 Pose bit for bit, score exactly, covariance to rtol 1e-12 (its sums run in another order and use the device's exp).  The
 sines and cosines come from the device (ParticleEngine.native_sincosf), so every beam position is the kernel's own.
-Every engine runs with ndt_refine=0: with the NDT stage on, its pose may replace the grid one."""
+Every engine runs with ndt_refine=0: with the NDT stage on, its pose may replace the grid one (that stage on the same
+paths: tests/test_gpu_matcher_ndt.py, which borrows the helpers below)."""
 import numpy as np
 import pytest
 
@@ -180,19 +181,21 @@ def test_twin_fuzz(eng):
 
 
 # ---- particle path: rbpf_scan_update_begin's built-in matcher, read back with match_results -----------------------------
-def mapped_engine(P, poses, cs=0.05, B=1081, n_scans=3, **kw):
+def mapped_engine(P, poses, cs=0.05, B=1081, n_scans=3, ndt_refine=0, **kw):
     from thesis_amd.engine import ParticleEngine
     from thesis_amd.datasets import synthetic
     ang = synthetic.beam_angles(B)
     rng = np.random.Generator(np.random.PCG64(11))
-    e = ParticleEngine(P, max_beams=B, cell_size=cs, pool_tiles=8 * P, ndt_refine=0, **kw)
+    e = ParticleEngine(P, max_beams=B, cell_size=cs, pool_tiles=8 * P, ndt_refine=ndt_refine, **kw)
     for _ in range(n_scans):
         e.set_scan(synthetic.cast_scan((0.0, 0.0, 0.0), ang, rng), ang)
         e.map_update(poses)
     return e, ang, rng
 
 
-def oracle_particle(e, p, x, y, pose, cov, adj, last=None):
+def oracle_particle(e, p, x, y, pose, cov, adj, last=None, sincos=None):
+    """The grid stage's oracle for particle p.  The dict also carries what the NDT stage's oracle needs (occ, origin,
+    beams, window, mcs, pose).  sincos: the device's (e.native_sincosf) unless given."""
     cfg = e.cfg
     N, ds, mcs, d0, ncr = mo.match_geometry(cfg.cell_size, cfg.match_max_range)
     beams = mo.select_beams(x, y, cfg.match_min_range, cfg.match_max_range, adj)
@@ -204,8 +207,8 @@ def oracle_particle(e, p, x, y, pose, cov, adj, last=None):
         tiles = dict(e.tiles(p))
         occ, ox, oy = mo.field_from_tiles(tiles, pose, N, ds, mcs, cfg.cell_size, float(cfg.tile_len_m), cfg.lattice_radius,
                                           int(np.floor(cfg.occupied_threshold / cfg.quantum + 1e-9)))
-    r = mo.grid_search(occ, ox, oy, bx, by, pose, (rx, ry, PI / 6), mcs, d0, ncr, 0.0, e.native_sincosf)
-    r.update(N=N, ds=ds)
+    r = mo.grid_search(occ, ox, oy, bx, by, pose, (rx, ry, PI / 6), mcs, d0, ncr, 0.0, sincos or e.native_sincosf)
+    r.update(N=N, ds=ds, mcs=mcs, occ=occ, ox=ox, oy=oy, bx=bx, by=by, window=(rx, ry, PI / 6), pose=np.array(pose, dtype=np.float64))
     return r
 
 
@@ -266,24 +269,35 @@ def test_particle_path_max_range_15():
         e.close()
 
 
-def test_particle_path_negative_side_and_tile_seam():
-    """Particles on the negative side of a tile and across the tile seams at +-20 m: the index map's defect columns and
-    slow words, against the reference's write formula."""
+def seam_engine(ndt_refine=0):
+    """Four particles on the negative side of a tile and across the tile seams at +-20 m, each with a two-scan map of a
+    lobed room round it; returns the engine and the scan (x, y) to match."""
     poses = np.array([[-11.0, -12.5, 0.3], [-19.6, -3.2, -1.2], [19.9, 20.3, 2.0], [-0.3, 19.8, 1.0]])
     P = len(poses)
     from thesis_amd.engine import ParticleEngine
     from thesis_amd.datasets import synthetic
+    from oracle import rbpf_oracle as orc
     ang = synthetic.beam_angles(1081)
     rng = np.random.Generator(np.random.PCG64(4))
-    e = ParticleEngine(P, max_beams=1081, pool_tiles=64, ndt_refine=0)
+    e = ParticleEngine(P, max_beams=1081, pool_tiles=64, ndt_refine=ndt_refine)
     try:
         for k in range(2):
             r = 5.0 + 2.0 * np.sin(3 * ang + k) + rng.normal(0, 0.01, 1081)
             e.set_scan(r, ang)
             e.map_update(poses)
         e.set_state(poses=poses + [0.08, -0.05, 0.02], covs=np.diag([4e-5, 4e-5, 1e-5]))
-        from oracle import rbpf_oracle as orc
-        x, y = orc.scan_xy(5.0 + 2.0 * np.sin(3 * ang + 1), ang)
+    except Exception:
+        e.close()
+        raise
+    x, y = orc.scan_xy(5.0 + 2.0 * np.sin(3 * ang + 1), ang)
+    return e, x, y
+
+
+def test_particle_path_negative_side_and_tile_seam():
+    """Particles on the negative side of a tile and across the tile seams at +-20 m: the index map's defect columns and
+    slow words, against the reference's write formula."""
+    e, x, y = seam_engine()
+    try:
         check_particles(e, x, y)
     finally:
         e.close()
