@@ -298,7 +298,12 @@ int  rbpf_unpack_particles(rbpf_handle* h, const int32_t* local_idx, int32_t n, 
  * serialised into d_buf. */
 int32_t rbpf_pack_raw_width(rbpf_handle* h);
 /* meta_out of rbpf_meta_from_raw, meta_in of rbpf_unpack_particles: [n][rbpf_pack_meta_width()] host ints that
- * describe the payload layout for the receiver */
+ * describe the payload layout for the receiver.  A row: tile count, payload bytes / 16, then per lattice position
+ * (lx + R) * L + (ly + R) six ints (has, x0, x1, y0, y1, offset / 16): the tile's written box, inclusive, which the
+ * receiver's tile gets exactly, and where its bytes start in the particle's payload; a held tile nothing was written to
+ * is (1, 0, -1, 0, -1, offset) and takes no bytes.  A particle's payload: 128 bytes of state (13 doubles x, y, theta,
+ * cov[9], weight), then per written tile the rows x0..x1 of the columns [y0 & ~15, min((y1 | 15) + 1, dim)) as int8 and
+ * (x1 - x0 + 1) * ceil(dim / 32) occupancy words, each tile padded to a multiple of 16 bytes. */
 int32_t rbpf_pack_meta_width(rbpf_handle* h);
 int  rbpf_gather_pack_meta(rbpf_handle* h, const int32_t* local_idx, int32_t n, void* d_raw);
 int  rbpf_meta_from_raw(rbpf_handle* h, const int32_t* raw, int32_t n, int32_t* meta_out, int64_t* bytes_out);

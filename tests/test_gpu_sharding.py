@@ -83,7 +83,8 @@ def test_ranks_on_one_gpu_equal_one_engine(world, p_local, steps):
         for k in range(steps):
             assert hist_r[k][0] == hist[k][0]
             if hist[k][0]:
-                assert np.array_equal(hist_r[k][1], hist[k][1])      # same ancestors as the single engine
+                assert np.array_equal(hist_r[k][1], hist[k][1]), (   # same ancestors as the single engine
+                    rank, k, np.nonzero(hist_r[k][1] != hist[k][1])[0][:8], [np.array_equal(r[6][k][1], hist_r[k][1]) for r in results])
         np.testing.assert_array_equal(p_r, poses[gids])
         np.testing.assert_array_equal(c_r, covs[gids])
         np.testing.assert_array_equal(w_r, w[gids])

@@ -496,7 +496,7 @@ __global__ __launch_bounds__(BLOCK) void pack_kernel(DevView v, const PackJob* _
 }
 
 // one workgroup per (incoming particle, lattice position): install the received tile (or release the slot's old one)
-struct UnpackJob { int32_t particle, pos, has, x0, x1, ya, yb, pad; long long off; };
+struct UnpackJob { int32_t particle, pos, has, x0, x1, y0, y1, pad; long long off; };   // the written box, inclusive; x0 > x1: nothing written
 
 __global__ __launch_bounds__(BLOCK) void unpack_kernel(DevView v, const UnpackJob* __restrict__ jobs, const unsigned char* __restrict__ buf,
                                                        int32_t* pending_free, int32_t* n_pending) {
@@ -548,19 +548,24 @@ __global__ __launch_bounds__(BLOCK) void unpack_kernel(DevView v, const UnpackJo
         }
         __syncthreads();
     }
-    if (j.x0 <= j.x1) {
+    const bool written = j.x0 <= j.x1 && j.y0 <= j.y1;
+    if (written) {
         const unsigned char* src = buf + j.off;
         int8_t* dst = v.pool + (size_t)td * cells;
-        const int per_row = (j.yb - j.ya) / 16, rows = j.x1 - j.x0 + 1;
+        const int ya = j.y0 & ~15, yb = min((j.y1 | 15) + 1, v.dim);      // the columns in the payload, exactly as layout_packed (rbpf_api.hip) derives them
+        const int per_row = (yb - ya) / 16, rows = j.x1 - j.x0 + 1;
         for (int q = tid; q < rows * per_row; q += BLOCK) {
-            const int x = j.x0 + q / per_row, y = j.ya + (q % per_row) * 16;
+            const int x = j.x0 + q / per_row, y = ya + (q % per_row) * 16;
             *reinterpret_cast<uint4*>(dst + (size_t)x * v.dim + y) = reinterpret_cast<const uint4*>(src)[q];
         }
         const uint32_t* socc = reinterpret_cast<const uint32_t*>(src + (size_t)rows * per_row * 16);
         uint32_t* docc = v.occ + ((size_t)td * v.dim + j.x0) * v.ow;
         for (int q = tid; q < rows * v.ow; q += BLOCK) docc[q] = socc[q];
     }
-    if (tid == 0) { v.tile_bbox[4 * td + 0] = j.x0; v.tile_bbox[4 * td + 1] = j.x1; v.tile_bbox[4 * td + 2] = j.ya; v.tile_bbox[4 * td + 3] = j.yb - 1; }
+    if (tid == 0) {                                     // the sender's written box as it is; nothing written: the empty box every other place stores
+        v.tile_bbox[4 * td + 0] = written ? j.x0 : INT_MAX; v.tile_bbox[4 * td + 1] = written ? j.x1 : -1;
+        v.tile_bbox[4 * td + 2] = written ? j.y0 : INT_MAX; v.tile_bbox[4 * td + 3] = written ? j.y1 : -1;
+    }
 }
 
 // ---- kernels: the stages one by one (any P), or the small ones fused into one single-workgroup launch ------------

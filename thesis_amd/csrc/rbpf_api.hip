@@ -1152,7 +1152,12 @@ int rbpf_apply_resample_local(rbpf_handle* h, const int32_t* new_src, const int3
     return RBPF_OK;                                     // no host synchronisation; device errors surface at the next check
 }
 
-// meta record of one particle: [0] tiles, [1] payload bytes / 16, then per lattice position (has, x0, x1, ya, yb, offset / 16)
+// meta record of one particle: [0] tiles, [1] payload bytes / 16, then per lattice position (has, x0, x1, y0, y1, offset / 16):
+// the written box itself, inclusive, which the receiver stores as it is; a held tile nothing was written to is
+// (1, 0, -1, 0, -1, offset) and takes no bytes.  The payload holds the columns [ya, yb) of the rows x0..x1, ya = y0 & ~15,
+// yb = min((y1 | 15) + 1, dim) - both sides derive them from y0, y1 -, then the rows' occupancy words, padded to 16 bytes.
+// layout_packed (sizes, offsets, pack jobs) and unpack_kernel each compute ya, yb: the two derivations must stay identical, or the
+// receiver reads other bytes than the sender wrote (tests/test_gpu_migrate.py holds both to the model's byte total).
 int32_t rbpf_pack_meta_width(rbpf_handle* h) { return h ? 2 + 6 * h->v.L * h->v.L : -1; }
 
 // job lists of the pack / unpack kernels go through one pinned buffer (S_JOBS -> B_JOBS): the copy is asynchronous and the
@@ -1188,9 +1193,9 @@ static int64_t layout_packed(const DevView& v, const int32_t* g, int n, const in
             ++nt;
             mm[0] = 1;
             int x0 = e[1], x1 = e[2], y0 = e[3], y1 = e[4];
-            if (x0 > x1 || y0 > y1) { mm[1] = 0; mm[2] = -1; mm[3] = 0; mm[4] = 0; mm[5] = (int32_t)((off - start) / 16); continue; }   // empty tile
+            if (x0 > x1 || y0 > y1) { mm[1] = 0; mm[2] = -1; mm[3] = 0; mm[4] = -1; mm[5] = (int32_t)((off - start) / 16); continue; }   // empty tile
             int ya = y0 & ~15, yb = std::min((y1 | 15) + 1, v.dim);
-            mm[1] = x0; mm[2] = x1; mm[3] = ya; mm[4] = yb; mm[5] = (int32_t)((off - start) / 16);
+            mm[1] = x0; mm[2] = x1; mm[3] = y0; mm[4] = y1; mm[5] = (int32_t)((off - start) / 16);
             if (jobs) jobs->push_back({local_idx[i], e[0], x0, x1, ya, yb, (long long)off});
             int64_t bytes = (int64_t)(x1 - x0 + 1) * (yb - ya) + (int64_t)(x1 - x0 + 1) * v.ow * 4;
             off += (bytes + 15) & ~(int64_t)15;

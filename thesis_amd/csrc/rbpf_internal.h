@@ -427,7 +427,7 @@ void launch_gather_meta(const DevView& v, const int32_t* d_local, int n, int32_t
 void launch_pack(const DevView& v, const void* d_jobs, int n_jobs, void* d_buf, hipStream_t s);
 void launch_unpack(const DevView& v, const ResampleBuffers& b, const void* d_jobs, int n_jobs, const void* d_buf, hipStream_t s);
 struct PackJobHost { int32_t particle, tile, x0, x1, ya, yb; long long off; };
-struct UnpackJobHost { int32_t particle, pos, has, x0, x1, ya, yb, pad; long long off; };
+struct UnpackJobHost { int32_t particle, pos, has, x0, x1, y0, y1, pad; long long off; };
 void launch_propose_weight(const DevView& v, const double* d_match, const int32_t* d_match_of, const double* d_guesses, uint8_t* d_bad,
                            uint64_t seed, uint32_t stream, double* d_dbg_w, int p0, int n, hipStream_t s, hipEvent_t done = nullptr);
 void launch_bad_weight(const DevView& v, const uint8_t* d_bad, hipStream_t s);
