@@ -32,6 +32,116 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _torch_device(cfg):
+    """(torch, the engine's device as torch names it).  Called only where a tensor is involved: nothing else imports torch."""
+    import torch
+    return torch, torch.device("cuda", int(cfg.device))
+
+
+def particle_index(engine, particle, allow_none: bool = True) -> int:
+    """A `particle` argument as the int the library takes: an index, "best" (the first argmax of engine.weights(), read only
+    then: it is a device read that also launches a held-back map update) or, where the caller admits it, None (-1: every
+    particle).  `engine` needs weights() alone."""
+    if isinstance(particle, str):
+        if particle != "best":
+            raise ValueError(f"unknown particle {particle!r}")
+        return int(np.argmax(engine.weights()))
+    return -1 if particle is None and allow_none else int(particle)
+
+
+def _box4(box, default):
+    """A `box` argument, or default() for None, as the int32 [4] the library takes, and the shape (nx, ny) of a raster over
+    it, clamped at 0: a box with x1 < x0 or y1 < y0 is the library's to refuse."""
+    b = np.array([int(x) for x in (default() if box is None else box)], dtype=np.int32)
+    if b.shape != (4,):
+        raise ValueError("box must be (x0, x1, y0, y1)")
+    return b, (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))
+
+
+def _poses_angles(poses, angles):
+    """(poses [N, 3], angles [B]) as contiguous float64; a [3] pose is N = 1."""
+    ps, a = _f64(poses), _f64(angles)
+    if ps.ndim == 1:
+        ps = ps.reshape(1, -1)
+    if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1:
+        raise ValueError("poses must be [N, 3] (or [3]) and angles 1-D")
+    return ps, a
+
+
+def _scan_batch(poses, ranges, angles):
+    """(poses [N, 3], ranges [N, B], angles [B]) as contiguous float64; a [3] pose with a [B] scan is N = 1."""
+    ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
+    if ps.ndim == 1:
+        ps = ps.reshape(1, -1)
+    if rg.ndim == 1:
+        rg = rg.reshape(1, -1)
+    if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
+        raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+    return ps, rg, a
+
+
+class _Outputs:
+    """The outputs of one library call and its order against torch: the one place that decides whether a call returns numpy
+    arrays or tensors on the engine's device, and when a tensor handed to or taken from torch is ready.
+
+        out = self._outputs(device)
+        a = out.empty(shape, "int32")            # numpy, or torch on the engine's device with device=True
+        t = out.adopt(tensor)                    # an input (or an `into`) that torch's side wrote; held until the call is over
+        with out:
+            self._check(self._lib.rbpf_...(..., out.ptr(t), out.ptr(a)))
+
+    The rule: torch allocates and writes in the order of its current stream, the library works on the engine's.  Where the
+    engine has borrowed that very stream (set_stream) nothing waits.  Else torch's stream is synchronised before the call
+    whenever a tensor is involved, and the engine after it whenever the outputs are on the device, so that they are ready
+    for work on torch's current stream.  After an exception nothing more is waited for.  Of the engine it reads cfg.device,
+    _borrowed_stream and _stream_ptr and calls synchronize(), nothing else."""
+
+    def __init__(self, engine, device: bool):
+        self._engine, self.device = engine, bool(device)
+        self.torch = self.dev = self._cur = None             # set once a tensor is involved
+        self._same_stream, self._held = False, []
+        if self.device:
+            self._use_torch()
+
+    def _use_torch(self):
+        if self.torch is None:
+            e = self._engine
+            self.torch, self.dev = _torch_device(e.cfg)
+            self._cur = self.torch.cuda.current_stream(self.dev)
+            self._same_stream = e._borrowed_stream and e._stream_ptr == self._cur.cuda_stream
+
+    def empty(self, shape, dtype, device_dtype=None):
+        """An uninitialised output of numpy's `dtype`; on the device of `device_dtype` where torch lacks the other."""
+        if not self.device:
+            return np.empty(shape, dtype=dtype)
+        return self.torch.empty(shape, dtype=getattr(self.torch, np.dtype(device_dtype or dtype).name), device=self.dev)
+
+    def adopt(self, x):
+        """Takes an input, or an output that exists already; a tensor puts the call behind torch's stream."""
+        if hasattr(x, "data_ptr"):
+            self._use_torch()
+        self._held.append(x)
+        return x
+
+    @staticmethod
+    def ptr(x):
+        """The address of an array or tensor for the library, None for an absent one; 1 where a zero-size one has none."""
+        if x is None:
+            return None
+        return C.c_void_p((x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data) or 1)
+
+    def __enter__(self):
+        if self._cur is not None and not self._same_stream:
+            self._cur.synchronize()                          # the tensors were written or allocated in torch's stream order
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None and self.device and not self._same_stream:
+            self._engine.synchronize()
+        self._held.clear()                                   # kept alive until the call was over
+        return False
+
+
 class ViewGain(NamedTuple):
     """ParticleEngine.view_gain: per pose [N], or per particle and pose [P, N] (numpy arrays, or torch tensors on the GPU)."""
     gain: Any        # int64: sum of table[v - vmin] over the distinct cells a scan there would observe
@@ -346,6 +456,41 @@ class ParticleEngine:
     def synchronize(self):
         self._check(self._lib.rbpf_synchronize(self._h))
 
+    def _outputs(self, device: bool) -> _Outputs:
+        return _Outputs(self, device)
+
+    def _particle(self, particle, allow_none: bool = True) -> int:
+        return particle_index(self, particle, allow_none)
+
+    def _int8_cells(self, cells, what: str, axes: str):
+        """A raster argument as (contiguous 2-D int8 numpy array, or int8 tensor on the engine's device; its shape); `what`
+        and `axes` word the caller's errors."""
+        if hasattr(cells, "data_ptr"):                   # a torch tensor
+            torch, dev = _torch_device(self.cfg)
+            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
+                raise ValueError(f"a tensor {what} must be 2-D int8 on {dev}")
+            cells = cells.contiguous()
+            return cells, tuple(cells.shape)
+        a = np.asarray(cells)
+        if a.ndim != 2:
+            raise ValueError(f"{what} cells must be 2-D {axes}")
+        if a.dtype != np.int8:
+            if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
+                raise ValueError(f"{what} cells must be int8 lattice values")
+        a = np.ascontiguousarray(a, dtype=np.int8)
+        return a, a.shape
+
+    def _value_table(self, table) -> np.ndarray:
+        """A `table` argument as int32, one entry per lattice value; None is explore.entropy_table(cfg)."""
+        if table is None:
+            from .explore import entropy_table
+            table = entropy_table(self.cfg)
+        tab = np.ascontiguousarray(table, dtype=np.int32)
+        nv = int(round((float(self.cfg.max_odds_occ) - float(self.cfg.min_odds_emp)) / float(self.cfg.quantum))) + 1
+        if tab.shape != (nv,):
+            raise ValueError(f"table must have {nv} entries, one per lattice value")
+        return tab
+
     def set_profiling(self, on):
         """True / False: timing events around every kernel family / none; a list of family names (KERNELS): only those
         (each record costs a few microseconds of stream time).  Restarts the counters."""
@@ -554,74 +699,32 @@ class ParticleEngine:
             raise ValueError("the raster has no int8 cells (a whole-filter render has prob / occ_frac): convert them with "
                              "thesis_amd.mapio.cells_from_probability first")
         p = -1 if particle is None else int(particle)
-        cells, flags, cur, same_stream = raster.cells, 0, None, False
-        if hasattr(cells, "data_ptr"):                   # a torch tensor
-            import torch
-            dev = torch.device("cuda", int(cfg.device))
-            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
-                raise ValueError(f"a tensor raster must be 2-D int8 on {dev}")
-            cells = cells.contiguous()
-            shape, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr()), _lib.RBPF_LOAD_DEVICE_IN
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-        else:
-            a = np.asarray(cells)
-            if a.ndim != 2:
-                raise ValueError("raster cells must be 2-D [nx][ny]")
-            if a.dtype != np.int8:
-                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
-                    raise ValueError("raster cells must be int8 lattice values")
-            cells = np.ascontiguousarray(a, dtype=np.int8)
-            shape, ptr = cells.shape, C.c_void_p(cells.ctypes.data)
+        cells, shape = self._int8_cells(raster.cells, "raster", "[nx][ny]")
         b = np.array([raster.x0, raster.x0 + shape[0], raster.y0, raster.y0 + shape[1]], dtype=np.int32)
-        if shape[0] * shape[1] == 0:
-            ptr = C.c_void_p(1)                          # an empty box writes nothing; the library only checks the box
-        if cur is not None and not same_stream:
-            cur.synchronize()                            # the tensor was written in torch's stream order
-        self._check(self._lib.rbpf_load_map(self._h, p, _ip(b), ptr, flags))
-        del cells                                        # kept alive until the call returned (it is complete on return)
+        out = self._outputs(False)
+        out.adopt(cells)
+        flags = _lib.RBPF_LOAD_DEVICE_IN if hasattr(cells, "data_ptr") else 0
+        with out:                                        # (an empty box writes nothing; the library only checks the box)
+            self._check(self._lib.rbpf_load_map(self._h, p, _ip(b), out.ptr(cells), flags))
 
     # -- map placement (include/rbpf_hip.h: rbpf_place_map; thesis_amd/mapio.py: SourceMap) ----------------
     PLACE_MODES = {"replace": _lib.RBPF_PLACE_REPLACE, "known": _lib.RBPF_PLACE_KNOWN, "add": _lib.RBPF_PLACE_ADD}
 
     def _place_inputs(self, src, box, samples):
-        """The arguments place_map and warp_map share: (cells kept alive, pointer, shape, input flag, pose, box, samples,
-        torch's current stream or None, whether the engine works on that stream)."""
+        """The arguments place_map and warp_map share: (cells, their shape, input flag, pose, box, its shape, samples)."""
         from .mapio import placed_box
         cfg = self.cfg
         if abs(float(src.quantum) - float(cfg.quantum)) > 1e-9 * abs(float(cfg.quantum)):
             raise ValueError(f"source quantum = {src.quantum!r} differs from the engine's {cfg.quantum!r}")
-        cells, flags, cur, same_stream = src.cells, 0, None, False
-        if hasattr(cells, "data_ptr"):                   # a torch tensor
-            import torch
-            dev = torch.device("cuda", int(cfg.device))
-            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
-                raise ValueError(f"a tensor source must be 2-D int8 on {dev}")
-            cells = cells.contiguous()
-            shape, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr() or 1), _lib.RBPF_PLACE_DEVICE_IN
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-        else:
-            a = np.asarray(cells)
-            if a.ndim != 2:
-                raise ValueError("source cells must be 2-D [nsx][nsy]")
-            if a.dtype != np.int8:
-                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
-                    raise ValueError("source cells must be int8 lattice values")
-            cells = np.ascontiguousarray(a, dtype=np.int8)
-            shape, ptr = cells.shape, C.c_void_p(cells.ctypes.data or 1)
+        cells, shape = self._int8_cells(src.cells, "source", "[nsx][nsy]")
         cell = float(cfg.tile_len_m) / self.dim
-        if box is None:
-            box = placed_box(src, cell, self.dim, int(cfg.lattice_radius))
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
+        b, oshape = _box4(box, lambda: placed_box(src, cell, self.dim, int(cfg.lattice_radius)))
         if samples is None:
             samples = min(8, max(2, int(np.ceil(2.0 * cell / float(src.cell_size)))))
         pose = _f64([float(v) for v in src.origin])
         if pose.shape != (3,):
             raise ValueError("source origin must be (x, y, yaw)")
-        return cells, ptr, shape, flags, pose, b, int(samples), cur, same_stream
+        return cells, shape, _lib.RBPF_PLACE_DEVICE_IN if hasattr(cells, "data_ptr") else 0, pose, b, oshape, int(samples)
 
     def place_map(self, src, particle: Optional[int] = None, box=None, samples: Optional[int] = None, mode: str = "replace"):
         """Resamples the map `src` (a mapio.SourceMap: any cell size, origin and yaw; e.g. mapio.read_map_image, or
@@ -634,12 +737,12 @@ class ParticleEngine:
         engine's device.  All or nothing: on an error no map changes.  Returns the box."""
         if mode not in self.PLACE_MODES:
             raise ValueError(f"unknown mode {mode!r}")
-        cells, ptr, shape, flags, pose, b, S, cur, same_stream = self._place_inputs(src, box, samples)
-        if cur is not None and not same_stream:
-            cur.synchronize()                            # the tensor was written in torch's stream order
-        self._check(self._lib.rbpf_place_map(self._h, -1 if particle is None else int(particle), _ip(b), ptr, shape[0], shape[1],
-                                             float(src.cell_size), _dp(pose), S, self.PLACE_MODES[mode], flags, None, None))
-        del cells                                        # kept alive until the call returned (it is complete on return)
+        cells, shape, flags, pose, b, _, S = self._place_inputs(src, box, samples)
+        out = self._outputs(False)
+        out.adopt(cells)
+        with out:
+            self._check(self._lib.rbpf_place_map(self._h, -1 if particle is None else int(particle), _ip(b), out.ptr(cells), shape[0],
+                                                 shape[1], float(src.cell_size), _dp(pose), S, self.PLACE_MODES[mode], flags, None, None))
         return tuple(int(x) for x in b)
 
     def warp_map(self, src, box=None, samples: Optional[int] = None, device: bool = False):
@@ -647,28 +750,14 @@ class ParticleEngine:
         rasters [x1-x0, y1-y0] of `box` (covered: some sample of the cell met the source; warped: the largest source value
         met, 0 where none).  No engine state changes.  device=True: torch tensors on the engine's device, ready for work
         on torch's current stream."""
-        cells, ptr, shape, flags, pose, b, S, cur, same_stream = self._place_inputs(src, box, samples)
-        oshape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))   # a bad box is the library's to refuse
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            if cur is None:
-                cur = torch.cuda.current_stream(dev)
-                same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            warped = torch.empty(oshape, dtype=torch.int8, device=dev)
-            covered = torch.empty(oshape, dtype=torch.uint8, device=dev)
-            ptrs = [C.c_void_p(warped.data_ptr() or 1), C.c_void_p(covered.data_ptr() or 1)]   # (an empty tensor has no data pointer)
-            flags |= _lib.RBPF_PLACE_DEVICE_OUT
-        else:
-            warped, covered = np.empty(oshape, dtype=np.int8), np.empty(oshape, dtype=np.uint8)
-            ptrs = [C.c_void_p(warped.ctypes.data or 1), C.c_void_p(covered.ctypes.data or 1)]
-        if cur is not None and not same_stream:
-            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
-        self._check(self._lib.rbpf_place_map(self._h, -1, _ip(b), ptr, shape[0], shape[1], float(src.cell_size), _dp(pose), S,
-                                             _lib.RBPF_PLACE_REPLACE, flags | _lib.RBPF_PLACE_DRY, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
-        del cells
+        cells, shape, flags, pose, b, oshape, S = self._place_inputs(src, box, samples)
+        out = self._outputs(device)
+        out.adopt(cells)
+        warped, covered = out.empty(oshape, "int8"), out.empty(oshape, "uint8")
+        flags |= _lib.RBPF_PLACE_DRY | (_lib.RBPF_PLACE_DEVICE_OUT if device else 0)
+        with out:
+            self._check(self._lib.rbpf_place_map(self._h, -1, _ip(b), out.ptr(cells), shape[0], shape[1], float(src.cell_size), _dp(pose),
+                                                 S, _lib.RBPF_PLACE_REPLACE, flags, out.ptr(warped), out.ptr(covered)))
         return warped, covered, tuple(int(x) for x in b)
 
     @property
@@ -757,11 +846,7 @@ class ParticleEngine:
         (`fields` picks them); `weights`: None (uniform), P values, or "resample" (resample_weights of weights()).
         device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
         from .mapio import MapRaster, resample_weights
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
+        p = self._particle(particle)
         w = None
         if isinstance(weights, str):
             if weights != "resample":
@@ -771,33 +856,14 @@ class ParticleEngine:
             w = _f64(weights)
             if w.shape != (self.P,):
                 raise ValueError(f"weights must have shape ({self.P},)")
-        if box is None:
-            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
-        nx, ny = int(b[1]) - int(b[0]), int(b[3]) - int(b[2])
-        shape = (max(nx, 0), max(ny, 0))                 # a box with x1 < x0 or y1 < y0 is the library's to refuse
+        b, shape = _box4(box, lambda: self.map_extent(None if p < 0 else p) or (0, 0, 0, 0))
         want = [p >= 0, p < 0 and "prob" in fields, p < 0 and "occ_frac" in fields]
-        dtypes = ("int8", "float32", "float32")
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [torch.empty(shape, dtype=getattr(torch, d), device=dev) if k else None for k, d in zip(want, dtypes)]
-            ptrs = [None if o is None else C.c_void_p(o.data_ptr()) for o in outs]
-        else:
-            outs = [np.empty(shape, dtype=d) if k else None for k, d in zip(want, dtypes)]
-            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
-        if not (device and nx >= 0 and ny >= 0 and nx * ny == 0):   # an empty tensor has no data pointer
-            if device and not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-            self._check(self._lib.rbpf_render_map(self._h, p, _ip(b), None if w is None else _dp(w),
-                                                  _lib.RBPF_RENDER_DEVICE_OUT if device else 0, *ptrs))
-            if device and not same_stream:
-                self.synchronize()
+        out = self._outputs(device)
+        outs = [out.empty(shape, d) if k else None for k, d in zip(want, ("int8", "float32", "float32"))]
+        if not (device and b[1] >= b[0] and b[3] >= b[2] and shape[0] * shape[1] == 0):   # an empty tensor has no data pointer
+            with out:
+                self._check(self._lib.rbpf_render_map(self._h, p, _ip(b), None if w is None else _dp(w),
+                                                      _lib.RBPF_RENDER_DEVICE_OUT if device else 0, *map(out.ptr, outs)))
         return MapRaster(x0=int(b[0]), y0=int(b[2]), cell_size=float(self.cfg.cell_size), quantum=float(self.cfg.quantum),
                          dim=self.dim, tile_len=float(self.cfg.tile_len_m), cells=outs[0], prob=outs[1], occ_frac=outs[2])
 
@@ -809,38 +875,16 @@ class ParticleEngine:
         N == P; e.g. poses()).  Returns ranges [N, B] in metres, max_range (default cfg.weight_max_range) where nothing
         occupied was met; with return_status also status [N, B] uint8 (1 hit, 0 none within max_range, 2 left the tile
         lattice).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
-        ps = _f64(poses)
-        if ps.ndim == 1:
-            ps = ps.reshape(1, -1)
-        a = _f64(angles)
-        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1:
-            raise ValueError("poses must be [N, 3] (or [3]) and angles 1-D")
+        p = self._particle(particle)
+        ps, a = _poses_angles(poses, angles)
         shape = (ps.shape[0], a.shape[0])
         mr = float(self.cfg.weight_max_range if max_range is None else max_range)
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            r = torch.empty(shape, dtype=torch.float64, device=dev)
-            st = torch.empty(shape, dtype=torch.uint8, device=dev) if return_status else None
-            ptrs = [C.c_void_p(r.data_ptr() or 1), None if st is None else C.c_void_p(st.data_ptr() or 1)]   # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            r = np.empty(shape, dtype=np.float64)
-            st = np.empty(shape, dtype=np.uint8) if return_status else None
-            ptrs = [C.c_void_p(r.ctypes.data), None if st is None else C.c_void_p(st.ctypes.data)]
-        self._check(self._lib.rbpf_cast_scans(self._h, p, _dp(ps), shape[0], _dp(a), shape[1], mr,
-                                              _lib.RBPF_CAST_DEVICE_OUT if device else 0, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        r = out.empty(shape, "float64")
+        st = out.empty(shape, "uint8") if return_status else None
+        with out:
+            self._check(self._lib.rbpf_cast_scans(self._h, p, _dp(ps), shape[0], _dp(a), shape[1], mr,
+                                                  _lib.RBPF_CAST_DEVICE_OUT if device else 0, out.ptr(r), out.ptr(st)))
         return (r, st) if return_status else r
 
     # -- view gain (include/rbpf_hip.h: rbpf_view_gain; DESIGN.md 3.11; thesis_amd/explore.py) ---------------------------------
@@ -853,43 +897,16 @@ class ParticleEngine:
         range the map update draws; `table` (one int in 0 .. 2^20 per lattice value) to explore.entropy_table(cfg), with
         which gain / 65536 reads as bits.  device=True: torch tensors on the engine's device, ready for work on torch's
         current stream."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
-        ps = _f64(poses)
-        if ps.ndim == 1:
-            ps = ps.reshape(1, -1)
-        a = _f64(angles)
-        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1:
-            raise ValueError("poses must be [N, 3] (or [3]) and angles 1-D")
-        if table is None:
-            from .explore import entropy_table
-            table = entropy_table(self.cfg)
-        tab = np.ascontiguousarray(table, dtype=np.int32)
-        nv = int(round((float(self.cfg.max_odds_occ) - float(self.cfg.min_odds_emp)) / float(self.cfg.quantum))) + 1
-        if tab.shape != (nv,):
-            raise ValueError(f"table must have {nv} entries, one per lattice value")
+        p = self._particle(particle)
+        ps, a = _poses_angles(poses, angles)
+        tab = self._value_table(table)
         shape = (ps.shape[0],) if p >= 0 else (self.P, ps.shape[0])
         mr = float(self.cfg.max_ray_m if max_range is None else max_range)
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [torch.empty(shape, dtype=d, device=dev) for d in (torch.int64, torch.int32, torch.int32)]
-            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            outs = [np.empty(shape, dtype=d) for d in (np.int64, np.int32, np.int32)]
-            ptrs = [C.c_void_p(o.ctypes.data) for o in outs]
-        self._check(self._lib.rbpf_view_gain(self._h, p, _dp(ps), ps.shape[0], _dp(a), a.shape[0], mr, _ip(tab),
-                                             _lib.RBPF_GAIN_DEVICE_OUT if device else 0, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        outs = [out.empty(shape, d) for d in ("int64", "int32", "int32")]
+        with out:
+            self._check(self._lib.rbpf_view_gain(self._h, p, _dp(ps), ps.shape[0], _dp(a), a.shape[0], mr, _ip(tab),
+                                                 _lib.RBPF_GAIN_DEVICE_OUT if device else 0, *map(out.ptr, outs)))
         return ViewGain(*outs)
 
     # -- travel cost (include/rbpf_hip.h: rbpf_travel_cost; DESIGN.md 3.12; thesis_amd/plan.py) ---------------------------------
@@ -906,11 +923,7 @@ class ParticleEngine:
         map, e.g. poses()).  plan.path_to walks a path down the field, plan.cost_metres converts.  device=True: torch tensors
         on the engine's device (clearance as int16), ready for work on torch's current stream."""
         from .plan import Travel
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
+        p = self._particle(particle)
         s = _f64(starts)
         if s.ndim == 1:
             s = s.reshape(1, -1)
@@ -927,37 +940,21 @@ class ParticleEngine:
             g = np.ascontiguousarray(g[:, :2])
         if p < 0 and g is None:
             raise ValueError("particle=None computes goal costs only: give goals")
-        if box is None:
-            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
+        b, shape = _box4(box, lambda: self.map_extent(None if p < 0 else p) or (0, 0, 0, 0))
         inv = self.dim / float(self.cfg.tile_len_m)
         inflate = int(np.floor(float(radius_m) * inv * 5.0))
         cmax = max(inflate + 1, inflate + 1 if clear_max is None else int(clear_max))
-        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
         gshape = None if g is None else ((g.shape[0],) if p >= 0 else (self.P, g.shape[0]))
-        want = [(shape, "int32") if p >= 0 else None, (shape, "int16" if device else "uint16") if p >= 0 else None,
-                (gshape, "int32") if g is not None else None]
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [None if w is None else torch.empty(w[0], dtype=getattr(torch, w[1]), device=dev) for w in want]
-            ptrs = [None if o is None else C.c_void_p(o.data_ptr() or 1) for o in outs]   # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            outs = [None if w is None else np.empty(w[0], dtype=w[1]) for w in want]
-            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
+        out = self._outputs(device)
+        outs = [out.empty(shape, "int32") if p >= 0 else None,
+                out.empty(shape, "uint16", device_dtype="int16") if p >= 0 else None,       # torch has no arithmetic on uint16
+                out.empty(gshape, "int32") if g is not None else None]
         flags = (_lib.RBPF_TRAVEL_DEVICE_OUT if device else 0) | (_lib.RBPF_TRAVEL_THROUGH_UNKNOWN if through_unknown else 0)
         rounds = C.c_int32(0)
-        self._check(self._lib.rbpf_travel_cost(self._h, p, _ip(b), _dp(s), s.shape[0], None if g is None else _dp(g),
-                                               0 if g is None else g.shape[0], inflate, cmax, flags, *ptrs, C.byref(rounds)))
-        if device and not same_stream:
-            self.synchronize()
+        with out:
+            self._check(self._lib.rbpf_travel_cost(self._h, p, _ip(b), _dp(s), s.shape[0], None if g is None else _dp(g),
+                                                   0 if g is None else g.shape[0], inflate, cmax, flags, *map(out.ptr, outs),
+                                                   C.byref(rounds)))
         return Travel(outs[0], outs[1], outs[2], int(rounds.value), tuple(int(x) for x in b), float(self.cfg.tile_len_m) / self.dim,
                       inv, inflate, cmax)
 
@@ -981,37 +978,16 @@ class ParticleEngine:
         particle in its own map, regions [P, max_regions], counts [P, 3], no label.  device=True: torch tensors on the engine's
         device (regions as int64 [..., 10]), ready for work on torch's current stream."""
         from .explore import Frontiers, REGION_DTYPE
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
-        if box is None:
-            box = self.map_extent(None if p < 0 else p) or (0, 0, 0, 0)
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
+        p = self._particle(particle)
+        b, shape = _box4(box, lambda: self.map_extent(None if p < 0 else p) or (0, 0, 0, 0))
         K = int(max_regions)
-        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
         lead = () if p >= 0 else (self.P,)
-        want = [(shape, "int32") if labels and p >= 0 else None, (lead + (max(K, 0), 10), "int64"), (lead + (3,), "int32")]
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [None if w is None else torch.empty(w[0], dtype=getattr(torch, w[1]), device=dev) for w in want]
-            ptrs = [None if o is None else C.c_void_p(o.data_ptr() or 1) for o in outs]   # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            outs = [None if w is None else np.empty(w[0], dtype=w[1]) for w in want]
-            ptrs = [None if o is None else C.c_void_p(o.ctypes.data) for o in outs]
-        self._check(self._lib.rbpf_frontier_regions(self._h, p, _ip(b), int(clearance_cells), int(min_size), K,
-                                                    _lib.RBPF_FRONTIER_DEVICE_OUT if device else 0, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        outs = [out.empty(shape, "int32") if labels and p >= 0 else None, out.empty(lead + (max(K, 0), 10), "int64"),
+                out.empty(lead + (3,), "int32")]
+        with out:
+            self._check(self._lib.rbpf_frontier_regions(self._h, p, _ip(b), int(clearance_cells), int(min_size), K,
+                                                        _lib.RBPF_FRONTIER_DEVICE_OUT if device else 0, *map(out.ptr, outs)))
         regions = outs[1] if device else outs[1].view(REGION_DTYPE)[..., 0]
         return Frontiers(outs[0], regions, outs[2], tuple(int(x) for x in b), float(self.cfg.tile_len_m) / self.dim)
 
@@ -1034,11 +1010,7 @@ class ParticleEngine:
         [..., 13] on the engine's device (the fields in the order of include/rbpf_hip.h), ready for work on torch's current
         stream; mapeval.MapScores.from_fields reads it."""
         from .mapeval import MapScores
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = -1 if particle is None else int(particle)
+        p = self._particle(particle)
         cells = reference
         if hasattr(reference, "cells") and hasattr(reference, "x0"):      # a MapRaster
             if reference.cells is None:
@@ -1051,60 +1023,21 @@ class ParticleEngine:
                 box = (reference.x0, reference.x0 + int(cells.shape[0]), reference.y0, reference.y0 + int(cells.shape[1]))
         if box is None:
             raise ValueError("an array reference needs box = (x0, x1, y0, y1)")
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
-        shape = (int(b[1]) - int(b[0]), int(b[3]) - int(b[2]))
-        flags, cur, same_stream = 0, None, False
-        if hasattr(cells, "data_ptr"):                   # a torch tensor
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            if cells.dtype != torch.int8 or cells.device != dev or cells.dim() != 2:
-                raise ValueError(f"a tensor reference must be 2-D int8 on {dev}")
-            cells = cells.contiguous()
-            have, ptr, flags = tuple(cells.shape), C.c_void_p(cells.data_ptr() or 1), _lib.RBPF_SCORE_DEVICE_IN
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-        else:
-            a = np.asarray(cells)
-            if a.ndim != 2:
-                raise ValueError("reference cells must be 2-D [nx][ny]")
-            if a.dtype != np.int8:
-                if a.dtype.kind not in "iu" or (a.size and (a.min() < -128 or a.max() > 127)):
-                    raise ValueError("reference cells must be int8 lattice values")
-            cells = np.ascontiguousarray(a, dtype=np.int8)
-            have, ptr = cells.shape, C.c_void_p(cells.ctypes.data or 1)
+        b, _ = _box4(box, None)
+        shape = (int(b[1]) - int(b[0]), int(b[3]) - int(b[2]))           # not clamped: no reference fits a bad box
+        cells, have = self._int8_cells(cells, "reference", "[nx][ny]")
         if tuple(have) != shape:
             raise ValueError(f"reference shape {tuple(have)} differs from the box's {shape}")
-        nv = int(round((float(self.cfg.max_odds_occ) - float(self.cfg.min_odds_emp)) / float(self.cfg.quantum))) + 1
-        if table is None:
-            from .explore import entropy_table
-            table = entropy_table(self.cfg)
-        tab = np.ascontiguousarray(table, dtype=np.int32)
-        if tab.shape != (nv,):
-            raise ValueError(f"table must have {nv} entries, one per lattice value")
-        oshape = ((self.P,) if p < 0 else ()) + (_lib.RBPF_SCORE_FIELDS,)
+        tab = self._value_table(table)
+        out = self._outputs(device)
+        out.adopt(cells)
+        fields = out.empty(((self.P,) if p < 0 else ()) + (_lib.RBPF_SCORE_FIELDS,), "int64")
+        flags = (_lib.RBPF_SCORE_DEVICE_IN if hasattr(cells, "data_ptr") else 0) | (_lib.RBPF_SCORE_DEVICE_OUT if device else 0)
+        with out:
+            self._check(self._lib.rbpf_score_maps(self._h, p, _ip(b), out.ptr(cells), int(tol_cells), _ip(tab), flags, out.ptr(fields)))
         if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            if cur is None:
-                cur = torch.cuda.current_stream(dev)
-                same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            out = torch.empty(oshape, dtype=torch.int64, device=dev)
-            optr = C.c_void_p(out.data_ptr())
-            flags |= _lib.RBPF_SCORE_DEVICE_OUT
-        else:
-            out = np.empty(oshape, dtype=np.int64)
-            optr = C.c_void_p(out.ctypes.data)
-        if cur is not None and not same_stream:
-            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
-        self._check(self._lib.rbpf_score_maps(self._h, p, _ip(b), ptr, int(tol_cells), _ip(tab), flags, optr))
-        if device and not same_stream:
-            self.synchronize()
-        del cells                                        # kept alive until the call returned
-        if device:
-            return out
-        return MapScores.from_fields(out, tuple(int(x) for x in b), int(tol_cells), float(self.cfg.quantum))
+            return fields
+        return MapScores.from_fields(fields, tuple(int(x) for x in b), int(tol_cells), float(self.cfg.quantum))
 
     # -- global localization (include/rbpf_hip.h: rbpf_locate_scan; thesis_amd/locate.py) ---------------------------------------
     def locate_scan(self, ranges, angles, particle="best", box=None, n_rot: int = 720, device: bool = False):
@@ -1114,38 +1047,16 @@ class ParticleEngine:
         rasters of the best score per cell and the smallest rotation index that attains it, -1 where no robot can stand
         (locate.hypotheses turns them into poses).  device=True: torch tensors on the engine's device, ready
         for work on torch's current stream."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = int(particle)
+        p = self._particle(particle, allow_none=False)
         r, a = _f64(ranges), _f64(angles)
         if r.ndim != 1 or a.shape != r.shape:
             raise ValueError("ranges and angles must be 1-D and of equal length")
-        if box is None:
-            box = self.map_extent(p) or (0, 0, 0, 0)
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
-        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            best = torch.empty(shape, dtype=torch.int32, device=dev)
-            rot = torch.empty(shape, dtype=torch.int32, device=dev)
-            ptrs = [C.c_void_p(best.data_ptr() or 1), C.c_void_p(rot.data_ptr() or 1)]   # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            best, rot = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
-            ptrs = [C.c_void_p(best.ctypes.data), C.c_void_p(rot.ctypes.data)]
-        self._check(self._lib.rbpf_locate_scan(self._h, p, _ip(b), _dp(r), _dp(a), r.shape[0], int(n_rot),
-                                               _lib.RBPF_LOCATE_DEVICE_OUT if device else 0, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        b, shape = _box4(box, lambda: self.map_extent(p) or (0, 0, 0, 0))
+        out = self._outputs(device)
+        best, rot = out.empty(shape, "int32"), out.empty(shape, "int32")
+        with out:
+            self._check(self._lib.rbpf_locate_scan(self._h, p, _ip(b), _dp(r), _dp(a), r.shape[0], int(n_rot),
+                                                   _lib.RBPF_LOCATE_DEVICE_OUT if device else 0, out.ptr(best), out.ptr(rot)))
         return best, rot, tuple(int(x) for x in b)
 
     def relocalize(self, ranges, angles, particle="best", k: int = 8, n_rot: int = 720, seed: int = 0, box=None,
@@ -1174,40 +1085,19 @@ class ParticleEngine:
         on an occupied cell.  Returns (best, rot, box): int32 [x1-x0, y1-y0] rasters of the best score per
         cell and the smallest rotation index of the window that attains it.  device=True: torch tensors on the engine's
         device, ready for work on torch's current stream."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = int(particle)
+        p = self._particle(particle, allow_none=False)
         o = _f64(occ_xy)
         f = _f64(np.empty((0, 2)) if free_xy is None else free_xy)
         if o.ndim != 2 or o.shape[1] != 2 or f.ndim != 2 or f.shape[1] != 2:
             raise ValueError("occ_xy and free_xy must be [n, 2]")
-        if box is None:
-            box = self.map_extent(p) or (0, 0, 0, 0)
-        b = np.array([int(x) for x in box], dtype=np.int32)
-        if b.shape != (4,):
-            raise ValueError("box must be (x0, x1, y0, y1)")
+        b, shape = _box4(box, lambda: self.map_extent(p) or (0, 0, 0, 0))
         r_begin, r_count = (0, int(n_rot)) if rot_window is None else (int(rot_window[0]), int(rot_window[1]))
-        shape = (max(int(b[1]) - int(b[0]), 0), max(int(b[3]) - int(b[2]), 0))     # a bad box is the library's to refuse
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            best = torch.empty(shape, dtype=torch.int32, device=dev)
-            rot = torch.empty(shape, dtype=torch.int32, device=dev)
-            ptrs = [C.c_void_p(best.data_ptr() or 1), C.c_void_p(rot.data_ptr() or 1)]   # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            best, rot = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
-            ptrs = [C.c_void_p(best.ctypes.data or 1), C.c_void_p(rot.ctypes.data or 1)]
-        self._check(self._lib.rbpf_align_points(self._h, p, _ip(b), _dp(o), o.shape[0], _dp(f) if f.shape[0] else None, f.shape[0],
-                                                int(n_rot), r_begin, r_count, _lib.RBPF_ALIGN_DEVICE_OUT if device else 0, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        best, rot = out.empty(shape, "int32"), out.empty(shape, "int32")
+        with out:
+            self._check(self._lib.rbpf_align_points(self._h, p, _ip(b), _dp(o), o.shape[0], _dp(f) if f.shape[0] else None, f.shape[0],
+                                                    int(n_rot), r_begin, r_count, _lib.RBPF_ALIGN_DEVICE_OUT if device else 0,
+                                                    out.ptr(best), out.ptr(rot)))
         return best, rot, tuple(int(x) for x in b)
 
     def align_map(self, src, particle="best", k: int = 4, n_rot: int = 360, refine: int = 8, box=None):
@@ -1217,11 +1107,7 @@ class ParticleEngine:
         (one coarse step either way, 5 x 5 cells) sharpens each.  Returns locate.Hypotheses, best first: poses[n] is the
         rigid transform for src.moved, e.g. place_map(src.moved(hyp.poses[0]), mode="add")."""
         from . import align
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        p = int(particle)
+        p = self._particle(particle, allow_none=False)
         if box is None:
             box = self.map_extent(p)
             if box is None:
@@ -1267,31 +1153,16 @@ class ParticleEngine:
         bin_xy metres and 2 pi / heading_bins (26-neighbourhood, cyclic heading), heaviest first, one estimate per mode
         (Modes; `weights` as estimate()).  While the filter is multimodal - after relocalize(), in a symmetric building -
         estimate() averages hypotheses; this tells them apart, and locate.converged(modes) says when one is left.  Needs no
-        tracking, changes nothing.  device=True: torch tensors, written in stream order without a host wait."""
+        tracking, changes nothing.  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
         mode, w = self._weights_arg(weights)
         bxy, n_th, K = float(bin_xy), int(heading_bins), int(max_modes)
         Kc = min(max(K, 0), _lib.RBPF_MODES_MAX)          # bad parameters are the library's to refuse
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            info = torch.empty(4, dtype=torch.int64, device=dev)
-            f = torch.empty((Kc, _lib.RBPF_EST_F64), dtype=torch.float64, device=dev)
-            i = torch.empty((Kc, _lib.RBPF_EST_I32), dtype=torch.int32, device=dev)
-            lab = torch.empty(self.P, dtype=torch.int32, device=dev) if labels else None
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr() or 1)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            info, f, i = np.empty(4, dtype=np.int64), np.empty((Kc, _lib.RBPF_EST_F64)), np.empty((Kc, _lib.RBPF_EST_I32), dtype=np.int32)
-            lab = np.empty(self.P, dtype=np.int32) if labels else None
-            ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 1)
-        self._check(self._lib.rbpf_pose_modes(self._h, mode, None if w is None else _dp(w), bxy, n_th, K,
-                                              _lib.RBPF_MODES_DEVICE_OUT if device else 0, ptr(info), ptr(f), ptr(i), ptr(lab)))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        info, f, i = out.empty(4, "int64"), out.empty((Kc, _lib.RBPF_EST_F64), "float64"), out.empty((Kc, _lib.RBPF_EST_I32), "int32")
+        lab = out.empty(self.P, "int32") if labels else None
+        with out:
+            self._check(self._lib.rbpf_pose_modes(self._h, mode, None if w is None else _dp(w), bxy, n_th, K,
+                                                  _lib.RBPF_MODES_DEVICE_OUT if device else 0, *map(out.ptr, (info, f, i, lab))))
         k = Kc if device else min(int(info[0]), Kc)
         f, i = f[:k], i[:k]
         return Modes(count=info[0] if device else int(info[0]), bins=info[1] if device else int(info[1]),
@@ -1347,35 +1218,20 @@ class ParticleEngine:
             pl = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
         n = self.P if pl is None else len(pl)
         T = max(int(t1) - int(t0), 0)                     # a bad range is the library's to refuse
-        cur, same_stream = None, False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            idx = torch.empty((T, n), dtype=torch.int32, device=dev)
-            pose = torch.empty((T, n, 3), dtype=torch.float64, device=dev) if poses else None
-            ptrs = [C.c_void_p(idx.data_ptr() or 1), None if pose is None else C.c_void_p(pose.data_ptr() or 1)]
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            idx = np.empty((T, n), dtype=np.int32)
-            pose = np.empty((T, n, 3), dtype=np.float64) if poses else None
-            ptrs = [C.c_void_p(idx.ctypes.data or 1), None if pose is None else C.c_void_p(pose.ctypes.data or 1)]
-        self._check(self._lib.rbpf_track_lineage(self._h, int(t0), int(t1), None if pl is None else _ip(pl), 0 if pl is None else len(pl),
-                                                 *ptrs, _lib.RBPF_TRACK_DEVICE_OUT if device else 0))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        idx = out.empty((T, n), "int32")
+        pose = out.empty((T, n, 3), "float64") if poses else None
+        with out:
+            self._check(self._lib.rbpf_track_lineage(self._h, int(t0), int(t1), None if pl is None else _ip(pl), 0 if pl is None else len(pl),
+                                                     out.ptr(idx), out.ptr(pose), _lib.RBPF_TRACK_DEVICE_OUT if device else 0))
         return idx, pose
 
     def trajectory(self, particle="best") -> np.ndarray:
         """[T, 3]: the recorded poses of the ancestors of one current particle (an index, or "best": estimate().best), one row
         per record."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
+        if isinstance(particle, str) and particle == "best":
             particle = self.estimate().best
-        return self.lineage([int(particle)])[1][:, 0, :]
+        return self.lineage([self._particle(particle, allow_none=False)])[1][:, 0, :]
 
     def trajectory_summary(self, weights="resample", t0: int = 0, t1: Optional[int] = None) -> TrajectorySummary:
         """The smoothed trajectory: per record the estimate (as estimate(), `weights` likewise) over the poses the current
@@ -1427,13 +1283,7 @@ class ParticleEngine:
         each axis.  Beams shorter than `min_range` or NaN are skipped, beams longer than `max_range` (default cfg.max_ray_m) are
         free to max_range and hit nothing.  `into`: an earlier BuiltMap of the same geometry, added to in place (a long log in
         chunks).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
-        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
-        if ps.ndim == 1:
-            ps = ps.reshape(1, -1)
-        if rg.ndim == 1:
-            rg = rg.reshape(1, -1)
-        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
-            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        ps, rg, a = _scan_batch(poses, ranges, angles)
         inv = self.dim / float(self.cfg.tile_len_m) if cell_size is None else 1.0 / float(cell_size)
         cs = float(self.cfg.cell_size) if cell_size is None else float(cell_size)
         mr = float(self.cfg.max_ray_m if max_range is None else max_range)
@@ -1444,32 +1294,20 @@ class ParticleEngine:
                 raise ValueError("`into` was built at another cell size")
             box = (into.x0, into.x0 + into.hits.shape[0], into.y0, into.y0 + into.hits.shape[1])
             device = not isinstance(into.hits, np.ndarray)
-        if box is None:
-            box = self.build_box(ps, inv, mr)
-        b4 =np.array([int(q) for q in box], dtype=np.int32)
-        shape = (max(int(b4[1]) - int(b4[0]), 0), max(int(b4[3]) - int(b4[2]), 0))       # an empty box is the library's to refuse
+        b4, shape = _box4(box, lambda: self.build_box(ps, inv, mr))
         flags = (_lib.RBPF_BUILD_DEVICE_OUT if device else 0) | (_lib.RBPF_BUILD_ACCUMULATE if into is not None else 0)
-        same_stream = False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [into.hits, into.seen] if into is not None else [torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(2)]
-            if any(o.dtype != torch.int32 or not o.is_contiguous() or o.device != dev for o in outs):
-                raise ValueError("`into` must hold contiguous int32 tensors on the engine's device")
-            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated (or last written) in torch's stream order
+        out = self._outputs(device)
+        if into is None:
+            outs = [out.empty(shape, "int32") for _ in range(2)]
         else:
-            outs = [into.hits, into.seen] if into is not None else [np.empty(shape, dtype=np.int32) for _ in range(2)]
-            if any(o.dtype != np.int32 or not o.flags.c_contiguous or not o.flags.writeable for o in outs):
+            outs = [out.adopt(into.hits), out.adopt(into.seen)]           # tensors were last written in torch's stream order
+            if device and any(o.dtype != out.torch.int32 or not o.is_contiguous() or o.device != out.dev for o in outs):
+                raise ValueError("`into` must hold contiguous int32 tensors on the engine's device")
+            if not device and any(o.dtype != np.int32 or not o.flags.c_contiguous or not o.flags.writeable for o in outs):
                 raise ValueError("`into` must hold contiguous, writeable int32 arrays")
-            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
-        self._check(self._lib.rbpf_build_map(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], inv, _ip(b4), float(min_range),
-                                             mr, flags, *ptrs))
-        if device and not same_stream:
-            self.synchronize()
+        with out:
+            self._check(self._lib.rbpf_build_map(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], inv, _ip(b4), float(min_range),
+                                                 mr, flags, *map(out.ptr, outs)))
         return BuiltMap(outs[0], outs[1], int(b4[0]), int(b4[2]), cs, inv)
 
     @staticmethod
@@ -1495,43 +1333,20 @@ class ParticleEngine:
         translation, so a guess that is already best comes back bit for bit.  A [3] pose with a [B] scan is N = 1.
         return_scores: the whole score volume as well.  max_range is limited by the window that fits one workgroup's LDS
         (refine_max_range).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
-        if isinstance(particle, str):
-            if particle != "best":
-                raise ValueError(f"unknown particle {particle!r}")
-            particle = int(np.argmax(self.weights()))
-        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
-        if ps.ndim == 1:
-            ps = ps.reshape(1, -1)
-        if rg.ndim == 1:
-            rg = rg.reshape(1, -1)
-        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
-            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        p = self._particle(particle, allow_none=False)
+        ps, rg, a = _scan_batch(poses, ranges, angles)
         n, nw, nk = ps.shape[0], 2 * int(window) + 1, 2 * int(rotations) + 1
         lo = float(self.cfg.match_min_range if min_range is None else min_range)
         hi = float(self.cfg.match_max_range if max_range is None else max_range)
-        shapes = [(n, 3), (n, 6)] + ([(n, max(nk, 0), max(nw, 0), max(nw, 0))] if return_scores else [])   # a bad window is the library's to refuse
-        same_stream = False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [torch.empty(sh, dtype=torch.float64 if k == 0 else torch.int32, device=dev) for k, sh in enumerate(shapes)]
-            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            outs = [np.empty(sh, dtype=np.float64 if k == 0 else np.int32) for k, sh in enumerate(shapes)]
-            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
-        if not return_scores:
-            ptrs.append(None)
-        self._check(self._lib.rbpf_refine_poses(self._h, int(particle), _dp(ps), n, _dp(rg), _dp(a), a.shape[0], lo, hi, int(substeps),
-                                                int(window), int(rotations), float(rot_step), *ptrs,
-                                                _lib.RBPF_REFINE_DEVICE_OUT if device else 0))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        outs = [out.empty((n, 3), "float64"), out.empty((n, 6), "int32"),
+                out.empty((n, max(nk, 0), max(nw, 0), max(nw, 0)), "int32") if return_scores else None]   # a bad window is the library's to refuse
+        with out:
+            self._check(self._lib.rbpf_refine_poses(self._h, p, _dp(ps), n, _dp(rg), _dp(a), a.shape[0], lo, hi, int(substeps),
+                                                    int(window), int(rotations), float(rot_step), *map(out.ptr, outs),
+                                                    _lib.RBPF_REFINE_DEVICE_OUT if device else 0))
         n6 = outs[1]
-        return RefineResult(outs[0], n6[:, 0:3], n6[:, 3], n6[:, 4], n6[:, 5], outs[2] if return_scores else None, int(substeps),
+        return RefineResult(outs[0], n6[:, 0:3], n6[:, 3], n6[:, 4], n6[:, 5], outs[2], int(substeps),
                             float(rot_step), float(self.cfg.cell_size))
 
     def refine_max_range(self, substeps: int = 4, window: int = 12) -> float:
@@ -1553,13 +1368,7 @@ class ParticleEngine:
         for bit.  A [3] triple is M = 1.  return_scores: the whole score volume as well.  max_range is limited as in
         refine_poses (match_max_range).  device=True: torch tensors on the engine's device, ready for work on torch's current
         stream."""
-        ps, rg, a = _f64(poses), _f64(ranges), _f64(angles)
-        if ps.ndim == 1:
-            ps = ps.reshape(1, -1)
-        if rg.ndim == 1:
-            rg = rg.reshape(1, -1)
-        if ps.ndim != 2 or ps.shape[1] != 3 or a.ndim != 1 or rg.shape != (ps.shape[0], a.shape[0]):
-            raise ValueError("poses must be [N, 3], angles [B] and ranges [N, B]")
+        ps, rg, a = _scan_batch(poses, ranges, angles)
         pr = np.ascontiguousarray(pairs, dtype=np.int32)
         if pr.ndim == 1:
             pr = pr.reshape(1, -1)
@@ -1576,29 +1385,15 @@ class ParticleEngine:
         nw, nk = 2 * int(window) + 1, 2 * int(rotations) + 1
         lo = float(self.cfg.match_min_range if min_range is None else min_range)
         hi = float(self.cfg.match_max_range if max_range is None else max_range)
-        shapes = [(m, 3), (m, 8)] + ([(m, max(nk, 0), max(nw, 0), max(nw, 0))] if return_scores else [])   # a bad window is the library's to refuse
-        same_stream = False
-        if device:
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device))
-            cur = torch.cuda.current_stream(dev)
-            same_stream = self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-            outs = [torch.empty(sh, dtype=torch.float64 if k == 0 else torch.int32, device=dev) for k, sh in enumerate(shapes)]
-            ptrs = [C.c_void_p(o.data_ptr() or 1) for o in outs]         # (an empty tensor has no data pointer)
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            outs = [np.empty(sh, dtype=np.float64 if k == 0 else np.int32) for k, sh in enumerate(shapes)]
-            ptrs = [C.c_void_p(o.ctypes.data or 1) for o in outs]
-        if not return_scores:
-            ptrs.append(None)
-        self._check(self._lib.rbpf_match_pairs(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], _ip(pr), m,
-                                               None if gs is None else _dp(gs), inv, lo, hi, int(substeps), int(window), int(rotations),
-                                               float(rot_step), *ptrs, _lib.RBPF_PAIRS_DEVICE_OUT if device else 0))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        outs = [out.empty((m, 3), "float64"), out.empty((m, 8), "int32"),
+                out.empty((m, max(nk, 0), max(nw, 0), max(nw, 0)), "int32") if return_scores else None]   # a bad window is the library's to refuse
+        with out:
+            self._check(self._lib.rbpf_match_pairs(self._h, _dp(ps), ps.shape[0], _dp(rg), _dp(a), a.shape[0], _ip(pr), m,
+                                                   None if gs is None else _dp(gs), inv, lo, hi, int(substeps), int(window), int(rotations),
+                                                   float(rot_step), *map(out.ptr, outs), _lib.RBPF_PAIRS_DEVICE_OUT if device else 0))
         m8 = outs[1]
-        return PairResult(outs[0], m8[:, 0:3], m8[:, 3], m8[:, 4], m8[:, 5], m8[:, 6], outs[2] if return_scores else None, int(substeps),
+        return PairResult(outs[0], m8[:, 0:3], m8[:, 3], m8[:, 4], m8[:, 5], m8[:, 6], outs[2], int(substeps),
                           float(rot_step), cs)
 
     def match_max_range(self, cell_size: Optional[float] = None, substeps: int = 1, window: int = 16) -> float:
@@ -1612,13 +1407,6 @@ class ParticleEngine:
         return float(np.nextafter(most, 0.0)) if np.ceil(most * inv) > reach else most
 
     # -- places by appearance (include/rbpf_hip.h: rbpf_describe_scans, rbpf_match_places; thesis_amd/loops.py) ---
-    def _torch_stream(self):
-        """(torch, device, torch's current stream there, whether the engine runs on that very stream)."""
-        import torch
-        dev = torch.device("cuda", int(self.cfg.device))
-        cur = torch.cuda.current_stream(dev)
-        return torch, dev, cur, self._borrowed_stream and self._stream_ptr == cur.cuda_stream
-
     def describe_scans(self, ranges, angles, rings: int = 24, min_range: Optional[float] = None, max_range: Optional[float] = None,
                        device: bool = False) -> ScanDescriptors:
         """What each scan looks like from where it was taken: `ranges` [N, B] (beam directions `angles` [B]) become polar
@@ -1635,21 +1423,12 @@ class ParticleEngine:
         n, r = rg.shape[0], int(rings)
         lo = float(self.cfg.match_min_range if min_range is None else min_range)
         hi = float(self.cfg.match_max_range if max_range is None else max_range)
-        same_stream = False
-        if device:
-            torch, dev, cur, same_stream = self._torch_stream()
-            desc = torch.empty((n, max(r, 0)), dtype=torch.int64, device=dev)     # a bad ring count is the library's to refuse
-            info = torch.empty((n, 2), dtype=torch.int32, device=dev)
-            ptrs = [C.c_void_p(desc.data_ptr() or 1), C.c_void_p(info.data_ptr() or 1)]
-            if not same_stream:
-                cur.synchronize()                        # the tensors were allocated in torch's stream order
-        else:
-            desc, info = np.empty((n, max(r, 0)), dtype=np.uint64), np.empty((n, 2), dtype=np.int32)
-            ptrs = [C.c_void_p(desc.ctypes.data or 1), C.c_void_p(info.ctypes.data or 1)]
-        self._check(self._lib.rbpf_describe_scans(self._h, _dp(rg), n, _dp(a), a.shape[0], lo, hi, r, *ptrs,
-                                                  _lib.RBPF_PLACES_DEVICE_OUT if device else 0))
-        if device and not same_stream:
-            self.synchronize()
+        out = self._outputs(device)
+        desc = out.empty((n, max(r, 0)), "uint64", device_dtype="int64")       # a bad ring count is the library's to refuse
+        info = out.empty((n, 2), "int32")
+        with out:
+            self._check(self._lib.rbpf_describe_scans(self._h, _dp(rg), n, _dp(a), a.shape[0], lo, hi, r, out.ptr(desc), out.ptr(info),
+                                                      _lib.RBPF_PLACES_DEVICE_OUT if device else 0))
         return ScanDescriptors(desc, info[:, 0], info[:, 1])
 
     def match_places(self, queries, refs=None, ref_limit=None, k: int = 4, device: bool = False) -> PlaceMatches:
@@ -1664,8 +1443,8 @@ class ParticleEngine:
         def table(t):
             t = t.desc if isinstance(t, ScanDescriptors) else t
             if hasattr(t, "data_ptr"):
-                import torch
-                if t.dtype != torch.int64 or t.dim() != 2 or t.device != torch.device("cuda", int(self.cfg.device)):
+                torch, dev = _torch_device(self.cfg)
+                if t.dtype != torch.int64 or t.dim() != 2 or t.device != dev:
                     raise ValueError("a descriptor tensor must be [N, R] int64 on the engine's device")
                 return t.contiguous()
             t = np.asarray(t)
@@ -1684,34 +1463,21 @@ class ParticleEngine:
             lim = np.ascontiguousarray(ref_limit, dtype=np.int32)
             if lim.shape != (nq,):
                 raise ValueError("ref_limit must be [Q]")
-        dev_in = hasattr(qd, "data_ptr") or hasattr(rd, "data_ptr")
-        flags, same_stream, cur = 0, False, None
-        if dev_in or device:
-            torch, dev, cur, same_stream = self._torch_stream()
-        if dev_in:
+        flags = _lib.RBPF_PLACES_DEVICE_OUT if device else 0
+        if hasattr(qd, "data_ptr") or hasattr(rd, "data_ptr"):       # one table is on the GPU: the other goes there too
+            torch, dev = _torch_device(self.cfg)
             up = lambda t: t if hasattr(t, "data_ptr") else torch.from_numpy(t.view(np.int64)).to(dev)
-            qd, rd = up(qd), (up(rd) if rd is not qd else None)
+            qd, rd = up(qd), (None if rd is qd else up(rd))
             rd = qd if rd is None else rd
             flags |= _lib.RBPF_PLACES_DEVICE_IN
-            tabs = [C.c_void_p(qd.data_ptr() or 1), C.c_void_p(rd.data_ptr() or 1)]
-        else:
-            tabs = [C.c_void_p(qd.ctypes.data or 1), C.c_void_p(rd.ctypes.data or 1)]
+        out = self._outputs(device)
+        out.adopt(qd)
+        out.adopt(rd)
         kk = min(max(k, 0), _lib.RBPF_PLACES_MAX_K)          # a bad k is the library's to refuse
-        if device:
-            qk4 = torch.empty((nq, kk, 4), dtype=torch.int32, device=dev)
-            q2 = torch.empty((nq, 2), dtype=torch.int32, device=dev)
-            outs = [C.c_void_p(qk4.data_ptr() or 1), C.c_void_p(q2.data_ptr() or 1)]
-            flags |= _lib.RBPF_PLACES_DEVICE_OUT
-        else:
-            qk4, q2 = np.empty((nq, kk, 4), dtype=np.int32), np.empty((nq, 2), dtype=np.int32)
-            outs = [C.c_void_p(qk4.ctypes.data or 1), C.c_void_p(q2.ctypes.data or 1)]
-        if cur is not None and not same_stream:
-            cur.synchronize()                            # the tensors were written or allocated in torch's stream order
-        self._check(self._lib.rbpf_match_places(self._h, tabs[0], nq, tabs[1], nr, int(qd.shape[1]), None if lim is None else _ip(lim), k,
-                                                *outs, flags))
-        if device and not same_stream:
-            self.synchronize()
-        del qd, rd                                       # kept alive until the call returned
+        qk4, q2 = out.empty((nq, kk, 4), "int32"), out.empty((nq, 2), "int32")
+        with out:
+            self._check(self._lib.rbpf_match_places(self._h, out.ptr(qd), nq, out.ptr(rd), nr, int(qd.shape[1]),
+                                                    None if lim is None else _ip(lim), k, out.ptr(qk4), out.ptr(q2), flags))
         return PlaceMatches(qk4[..., 0], qk4[..., 1], qk4[..., 2], qk4[..., 3], q2[:, 0], q2[:, 1])
 
     # -- score surface (include/rbpf_hip.h: rbpf_score_surface; thesis_amd/loops.py) -----------------------------
@@ -1736,11 +1502,8 @@ class ParticleEngine:
         if vol is None:
             raise ValueError("the result carries no score volume: ask for return_scores=True")
         dev_in = hasattr(vol, "data_ptr")
-        torch = dev = cur = None
-        same_stream = False
-        if dev_in or device:
-            torch, dev, cur, same_stream = self._torch_stream()
         if dev_in:
+            torch, dev = _torch_device(self.cfg)
             if vol.dtype != torch.int32 or vol.dim() != 4 or vol.device != dev:
                 raise ValueError("a score tensor must be [N, 2R+1, 2W+1, 2W+1] int32 on the engine's device")
             vol = vol.contiguous()
@@ -1763,28 +1526,16 @@ class ParticleEngine:
         ex_t, ex_r = self.surface_exclusion(W, R) if exclude is None else (int(exclude[0]), int(exclude[1]))
         k = int(peaks)
         kk = min(max(k, 0), 8)                               # a bad count is the library's to refuse
-        flags = 0
-        if dev_in:
-            dr_in = torch.from_numpy(dr).to(dev)
-            ins = [C.c_void_p(vol.data_ptr() or 1), C.c_void_p(dr_in.data_ptr() or 1)]
-            flags |= _lib.RBPF_SURFACE_DEVICE_IN
-        else:
-            ins = [C.c_void_p(vol.ctypes.data or 1), C.c_void_p(dr.ctypes.data or 1)]
-        if device:
-            rec = torch.empty((n, kk, 16), dtype=torch.int64, device=dev)
-            cnt = torch.empty((n,), dtype=torch.int32, device=dev)
-            outs = [C.c_void_p(rec.data_ptr() or 1), C.c_void_p(cnt.data_ptr() or 1)]
-            flags |= _lib.RBPF_SURFACE_DEVICE_OUT
-        else:
-            rec, cnt = np.empty((n, kk, 16), dtype=np.int64), np.empty((n,), dtype=np.int32)
-            outs = [C.c_void_p(rec.ctypes.data or 1), C.c_void_p(cnt.ctypes.data or 1)]
-        if cur is not None and not same_stream:
-            cur.synchronize()                                # the tensors were written or allocated in torch's stream order
-        self._check(self._lib.rbpf_score_surface(self._h, ins[0], n, R, W, ins[1], ex_t, ex_r, k, *outs, flags))
-        if device and not same_stream:
-            self.synchronize()
-        del vol, ins                                         # kept alive until the call returned
-        dr_out = torch.from_numpy(dr).to(dev) if device else dr
+        dr_in = torch.from_numpy(dr).to(dev) if dev_in else dr
+        out = self._outputs(device)
+        out.adopt(vol)
+        out.adopt(dr_in)
+        rec, cnt = out.empty((n, kk, 16), "int64"), out.empty((n,), "int32")
+        flags = (_lib.RBPF_SURFACE_DEVICE_IN if dev_in else 0) | (_lib.RBPF_SURFACE_DEVICE_OUT if device else 0)
+        with out:
+            self._check(self._lib.rbpf_score_surface(self._h, out.ptr(vol), n, R, W, out.ptr(dr_in), ex_t, ex_r, k, out.ptr(rec),
+                                                     out.ptr(cnt), flags))
+        dr_out = out.torch.from_numpy(dr).to(out.dev) if device else dr
         steps = (int(res.substeps), float(res.rot_step), float(res.cell_size)) if res is not None else (None, None, None)
         return ScoreSurface.from_records(rec, cnt, dr_out, *steps)
 

@@ -9,6 +9,8 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
+from .engine import particle_index
+
 
 def entropy_table(cfg) -> np.ndarray:
     """int32 table over the lattice values vmin .. vmax (61 with the default constants): round(65536 H2(sigma(|v| quantum))),
@@ -80,10 +82,7 @@ def next_view(engine, angles, particle="best", weights=None, k: int = 8, spacing
     """The k candidate poses whose scan would observe the most: candidates from the map of `particle` (an index or "best";
     with None the best particle's map), scored by view_gain in that map, or with particle=None in every particle's map and
     averaged with `weights` (uniform by default)."""
-    if isinstance(particle, str) and particle != "best":
-        raise ValueError(f"unknown particle {particle!r}")
-    best = int(np.argmax(engine.weights()))
-    src = best if particle is None or isinstance(particle, str) else int(particle)
+    src = particle_index(engine, "best" if particle is None else particle)
     cand = candidate_poses(engine.render_map(src), spacing_m, n_headings, clearance_cells, float(engine.cfg.occupied_threshold))
     if len(cand) == 0:
         raise ValueError("the map has no frontier cell with that clearance: nowhere to look")
@@ -112,10 +111,7 @@ def next_reachable_view(engine, angles, start, particle="best", weights=None, k:
     reach < min_reach are dropped; score = gain in bits - travel_weight * (weighted mean of the cost in metres over the
     particles that reach it).  The k best are returned, ties to the lower index; none if no candidate can be reached."""
     from .plan import cost_metres
-    if isinstance(particle, str) and particle != "best":
-        raise ValueError(f"unknown particle {particle!r}")
-    best = int(np.argmax(engine.weights()))
-    src = best if particle is None or isinstance(particle, str) else int(particle)
+    src = particle_index(engine, "best" if particle is None else particle)
     cand = candidate_poses(engine.render_map(src), spacing_m, n_headings, clearance_cells, float(engine.cfg.occupied_threshold))
     if len(cand) == 0:
         raise ValueError("the map has no frontier cell with that clearance: nowhere to look")
@@ -222,8 +218,7 @@ def next_frontier_view(engine, angles, particle="best", weights=None, k: int = 8
     (ParticleEngine.frontier_regions) of `particle` (an index or "best"), scored by view_gain in that map.  particle=None: the
     regions of EVERY particle's map, pooled by posterior_regions with `weights` (uniform by default), so that a frontier the best
     map lacks is proposed too, scored in every map and averaged."""
-    if isinstance(particle, str) and particle != "best":
-        raise ValueError(f"unknown particle {particle!r}")
+    which = particle_index(engine, particle)
     th = 2.0 * np.pi * np.arange(int(n_headings)) / int(n_headings)
     if particle is None:
         fr = engine.frontier_regions(None, clearance_cells=clearance_cells, min_size=min_size, max_regions=max_regions, labels=False)
@@ -232,7 +227,6 @@ def next_frontier_view(engine, angles, particle="best", weights=None, k: int = 8
         cand = np.concatenate([np.repeat(xy, len(th), axis=0), np.tile(th, len(xy))[:, None]], axis=1).reshape(-1, 3)
         size, support, which = pr.size, pr.support, None
     else:
-        which = int(np.argmax(engine.weights())) if isinstance(particle, str) else int(particle)
         fr = engine.frontier_regions(which, clearance_cells=clearance_cells, min_size=min_size, max_regions=max_regions, labels=False)
         cand = region_poses(fr, n_headings)
         size = np.asarray(fr.regions["size"][:int(fr.counts[2])], dtype=np.int64)
