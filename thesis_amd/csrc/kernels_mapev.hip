@@ -76,10 +76,16 @@ static inline void ev_turnover_begin(hipStream_t) { }
 static inline void ev_turnover_end(const DevView&, int, hipStream_t) { }
 #endif
 
+#ifndef EV_RUN                                  // (4 measured slower than 2: DESIGN.md section 6)
+#define EV_RUN 2
+#endif
 static const int EB = 1024;                    // threads per particle
 static const int HIT_BOUND = 62;               // per direction class; two classes can meet in a cell, +1 for the flag's count bit: 125 < 128
 static const int EVCAP = 3072;                 // passes over flagged cells kept per particle (more: exact replay of every flagged cell)
 static const int NPAIR = 3;                    // pairs (beam, e) per thread kept in registers: 3 * EB pairs = 1536 beams
+static const int EV_R = EV_RUN;                // whole chunks of a ray that one work item of the level walk takes
+static const int EV_LGR = EV_R == 4 ? 2 : EV_R == 2 ? 1 : 0;
+static_assert(EV_R == 1 << EV_LGR, "the run length is 1, 2 or 4");
 static const int FOLD_SPAN = 64;               // a flagged cell whose pairs lie within this many of each other is folded from a 64-bit set in registers
 
 struct EvGeom {
@@ -157,6 +163,12 @@ __device__ __forceinline__ uint32_t ev_lds_add_rtn(int byte_addr, uint32_t val) 
     return __hip_atomic_fetch_add((lds_u32*)(uintptr_t)(uint32_t)byte_addr, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// The flag of a field from the word an add returned: bit (sh mod 32) of it.  The bit-field extract reads only the low five bits
+// of its offset, so the field's bit address goes in as it is (a shift by `sh & 31` costs a masking instruction per step).
+__device__ __forceinline__ uint32_t ev_flag_bit(uint32_t word, int sh) {
+    return __builtin_amdgcn_ubfe(word, (uint32_t)sh, 1u);
+}
+
 // open addressing, linear probing, keys never ~0
 __device__ __forceinline__ int ev_hash_insert(uint32_t* keys, int T, int logT, uint32_t sc, bool& created) {
     uint32_t h = (sc * 2654435761u) >> (32 - logT);
@@ -218,7 +230,7 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
     uint32_t* const r_fs = reinterpret_cast<uint32_t*>(smem + G.o_fs);     // [B] 32-bit fixed-point slope
     int32_t*  const r_end = reinterpret_cast<int32_t*>(smem + G.o_end);    // [B] packed end cell relative to the start
     uint16_t* const r_nE = reinterpret_cast<uint16_t*>(smem + G.o_nE);     // [B] steps the walk takes
-    uint16_t* const perm = reinterpret_cast<uint16_t*>(smem + G.o_perm);   // rays ordered by falling count of whole chunks
+    uint16_t* const perm = reinterpret_cast<uint16_t*>(smem + G.o_perm);   // the rays with a run, ordered by falling count of runs (EV_R whole chunks each)
     uint8_t*  const r_info = smem + G.o_info;                              // [B]
     uint16_t* const r_kl = reinterpret_cast<uint16_t*>(smem + G.o_kl);     // [B] first whole chunk of the ray's share of the level walk | chunks << 8 (a strip: those inside it)
     uint16_t* const ux = reinterpret_cast<uint16_t*>(smem + G.o_ux);       // U of global column fxl + i
@@ -307,7 +319,7 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                 atomicAdd(reinterpret_cast<unsigned int*>(s_bins) + (key >> 1), 1u << ((key & 1) * 16));
                 if (nE > NEAR_R) atomicAdd(reinterpret_cast<unsigned int*>(s_far) + (key >> 1), 1u << ((key & 1) * 16));   // only these reach the 8-bit fields
                 const int nfull = (nE - NEAR_R) / LCH;                               // whole chunks beyond the 16-bit block
-                if (nE > NEAR_R && nfull >= 1) atomicAdd(&s_lcnt[min(nfull, MAXLEV)], 1);
+                if (nE > NEAR_R && nfull >= EV_R) atomicAdd(&s_lcnt[min(nfull / EV_R, MAXLEV)], 1);   // the levels of the runs (a strip makes its own)
             }
             r_fs[b] = fs;
             r_end[b] = (int32_t)(((uint32_t)ddx & 0xFFFFu) | ((uint32_t)ddy << 16));
@@ -347,11 +359,11 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
         mx2 = wave_max(mx2);
         if (lane == 0 && mx2 > HIT_BOUND) s_exact = 1;
     }
-    // rays ordered by falling count of whole chunks
+    // rays ordered by falling count of runs
     for (int b = tid; b < v.B; b += EB) {
         const int nE = r_nE[b];
         const int nfull = (nE - NEAR_R) / LCH;
-        if (nE > NEAR_R && nfull >= 1) perm[atomicAdd(&s_lfill[min(nfull, MAXLEV)], 1)] = (uint16_t)b;
+        if (nE > NEAR_R && nfull >= EV_R) perm[atomicAdd(&s_lfill[min(nfull / EV_R, MAXLEV)], 1)] = (uint16_t)b;
     }
     glitch_mask<EB>(gyb, gym, s_ggf, ggf_base, 192, sg, G.fanw, fyl, nfx, C, v.dim, gpt, tid);
     __syncthreads();
@@ -479,12 +491,13 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                 }
                 __builtin_amdgcn_sched_barrier(0);                                     // sixteen adds in flight, then their answers
 #pragma unroll
-                for (int u = 0; u < NEAR_R; ++u) m = __builtin_amdgcn_alignbit(u < nE ? ret[u] >> (sh[u] & 31) : 0u, m, 1);
+                for (int u = 0; u < NEAR_R; ++u) m = __builtin_amdgcn_alignbit(u < nE ? ev_flag_bit(ret[u], sh[u]) : 0u, m, 1);
                 if (m) log_events(m, b, 0, 0, 0, 0, false);
             }
         }
-        // ---- walk: lanes are rays, a work item is one 16-step chunk of 64 rays.  Level k >= 1 = steps NEAR_R + 16 (k - 1) .. + 15;
-        //      the rays that own a whole k-th chunk are perm[0 .. N_k); lane l of the w-th wave of a level takes ray l * waves + w.
+        // ---- walk: lanes are rays, chunk k >= 1 of a ray = its steps NEAR_R + 16 (k - 1) .. + 15.  A work item is a run of EV_R whole
+        //      chunks of 64 rays (or one left-over chunk: see the level walk); the rays that own an r-th run are perm[0 .. N_r); lane l of
+        //      the w-th wave of a level takes ray l * waves + w.
         //      A step: field += 2 with the old word returned, bit 0 of the old field = flagged; the address moves by one of two
         //      constants, chosen by the carry of the slope accumulator. ----
         {
@@ -493,7 +506,9 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
             const int win_lo = cnt_lds, win_n = rows_w * stride;
             // one predicated chunk of ray b (steps j0 .. j0 + 15, those in [jlo, jhi] and inside the window count): the tail of a
             // ray, or - in a strip - a chunk the strip's edge cuts.  Branch-free: a dead step adds nothing to a word of the lane's own.
-            auto walk_pred = [&](int b, int j0, int jlo, int jhi) {
+            // `strip` (a constant where it is called) = false: one window holds the fan, the chunk is a ray's tail and a step counts if it lies
+            // below the ray's end - no lower bound, no test against the window.
+            auto walk_pred = [&](int b, int j0, int jlo, int jhi, const bool strip) {
                 const uint32_t fs = r_fs[b];
                 const RayDir d = ray_dir(b);
                 const int sxs = d.sx * stride;
@@ -505,7 +520,7 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                 uint32_t ret[LCH]; int sh[LCH];
 #pragma unroll
                 for (int u = 0; u < LCH; ++u) {
-                    const bool in = j0 + u >= jlo && j0 + u <= jhi && (unsigned)(c - win_lo) < (unsigned)win_n;
+                    const bool in = strip ? j0 + u >= jlo && j0 + u <= jhi && (unsigned)(c - win_lo) < (unsigned)win_n : j0 + u <= jhi;
                     sh[u] = c << 3;
                     ret[u] = ev_lds_add_rtn(in ? c & ~3 : win_lo + 4 * lane, (in ? 2u : 0u) << (sh[u] & 31));
                     inm |= in ? 1u << u : 0u;
@@ -515,7 +530,7 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int u = 0; u < LCH; ++u) m = __builtin_amdgcn_alignbit((inm >> u) & (ret[u] >> (sh[u] & 31)), m, 1);
+                for (int u = 0; u < LCH; ++u) m = __builtin_amdgcn_alignbit((inm >> u) & ev_flag_bit(ret[u], sh[u]), m, 1);
                 if (m) log_events(m, b, j0, ev_lo, ev_hi, gx_base, !whole);
             };
             if (whole) {
@@ -524,12 +539,12 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                     const int nE = (int)r_nE[b];
                     if (nE <= NEAR_R) continue;
                     const int j0 = NEAR_R + ((nE - NEAR_R) / LCH) * LCH;            // first step after the whole chunks
-                    if (j0 < nE) walk_pred(b, j0, j0, nE - 1);
+                    if (j0 < nE) walk_pred(b, j0, j0, nE - 1, false);
                 }
             } else {
                 // A strip holds a part of every ray: the steps NEAR_R .. nE - 1 whose row lies in the strip are a run
                 // [lo, hi] (rows never turn back along a ray).  The whole chunks inside the run are the ray's share of the
-                // strip's level walk (relative levels: rays ordered by how many such chunks they have); the one or two chunks
+                // strip's level walk (relative levels: rays ordered by how many runs of such chunks they have); the one or two chunks
                 // that the strip's edge or the ray's end cuts are walked here, predicated.
                 if (tid <= MAXLEV) s_lcnt[tid] = 0;
                 BAR_LDS();
@@ -566,69 +581,95 @@ __device__ __forceinline__ void map_update_ev_particle(const DevView& v, const i
                             const int a = lo == NEAR_R + (kf - 1) * LCH ? kf : kf + 1;             // first chunk that lies inside as a whole
                             const int e = min(hi == NEAR_R + kl * LCH - 1 ? kl : kl - 1, nfull);   // last one
                             if (e >= a) { ka = a; len = e - a + 1; }
-                            if (kf < a || kf > e) walk_pred(b, NEAR_R + (kf - 1) * LCH, lo, hi);
-                            if (kl != kf && (kl < a || kl > e)) walk_pred(b, NEAR_R + (kl - 1) * LCH, lo, hi);
+                            if (kf < a || kf > e) walk_pred(b, NEAR_R + (kf - 1) * LCH, lo, hi, true);
+                            if (kl != kf && (kl < a || kl > e)) walk_pred(b, NEAR_R + (kl - 1) * LCH, lo, hi, true);
                         }
                     }
                     r_kl[b] = (uint16_t)(ka | (len << 8));
-                    if (len) atomicAdd(&s_lcnt[min(len, MAXLEV)], 1);
+                    if (len >= EV_R) atomicAdd(&s_lcnt[min(len / EV_R, MAXLEV)], 1);
                 }
                 BAR_LDS();
-                if (wave == 0) level_sums(lane, s_lcnt, s_lfill, s_nk, s_lp, &s_nlev);   // relative levels: rays with at least k whole chunks inside the strip
+                if (wave == 0) level_sums(lane, s_lcnt, s_lfill, s_nk, s_lp, &s_nlev);   // relative levels: rays with at least k runs of whole chunks inside the strip
                 BAR_LDS();
                 for (int b = tid; b < v.B; b += EB) {
                     const int len = (int)r_kl[b] >> 8;
-                    if (len) perm[atomicAdd(&s_lfill[min(len, MAXLEV)], 1)] = (uint16_t)b;
+                    if (len >= EV_R) perm[atomicAdd(&s_lfill[min(len / EV_R, MAXLEV)], 1)] = (uint16_t)b;
                 }
                 BAR_LDS();
             }
-            // ---- the level walk: every lane runs all 16 steps of a whole chunk (inside the window as a whole) ----
+            // ---- the level walk: every lane runs all 16 steps of whole chunks (inside the window as a whole).  A ray's share of `len`
+            //      whole chunks from chunk `ka` on (r_kl) is len / R RUNS of R consecutive chunks and len % R left-over chunks behind them.
+            //      A work item is a run of 64 rays - direction, start address and the next item's fetch once, the slope accumulator and the
+            //      address carried from chunk to chunk - or one left-over chunk of 64 rays.  The runs are levelled by their number (s_lp,
+            //      s_nk, perm: run level r holds the rays with at least r runs); behind them come R - 1 levels of left-overs over ALL
+            //      rays in beam order, lane l of a level's w-th wave asks ray l * waves + w and sits idle unless that ray has more than
+            //      `level` left-overs (no second order of the rays: (R - 1) * B / 64 items, a few of a thousand). ----
             const int nlev_w = UNI(s_nlev);
-            const int nitems = UNI(s_lp[nlev_w + 1]);                             // (levels above nlev have no waves: s_lp stays flat)
+            const int nruns = UNI(s_lp[nlev_w + 1]);                              // the runs' items (levels above nlev have no waves: s_lp stays flat)
+            const int nwb = (v.B + 63) >> 6;
+            const int nitems = nruns + (EV_R - 1) * nwb;
+            const int wave_u = UNI(wave);                                         // (the items' numbers and the levels' bookkeeping in scalar registers)
             // the next item's ray is fetched while this one's adds are in flight
-            int k = 1, kn = 1;
+            int kn = 1;
             int lp_c = UNI(s_lp[1]), lp_n = UNI(s_lp[2]), nk_c = UNI(s_nk[1]);    // first item of the level, of the next level; rays of the level
-            int nb = -1, nka = 1; uint32_t nfs = 0; int32_t nend = 0;
+            int nb = -1, nk0 = 1; uint32_t nfs = 0; int32_t nend = 0;             // the next item: ray, its first chunk, slope, end cell
             auto fetch_item = [&](int q) {
                 nb = -1;
                 if (q >= nitems) return;
-                while (kn < nlev_w && q >= lp_n) { ++kn; lp_c = lp_n; lp_n = UNI(s_lp[kn + 1]); nk_c = UNI(s_nk[kn]); }
-                const int nwk = (nk_c + 63) >> 6, wslot = q - lp_c;
-                const int ii = lane * nwk + wslot;
-                if (ii < nk_c) { nb = perm[ii]; nfs = r_fs[nb]; nend = r_end[nb]; nka = (int)r_kl[nb] & 0xFF; }
+                if (q < nruns) {
+                    while (kn < nlev_w && q >= lp_n) { ++kn; lp_c = lp_n; lp_n = UNI(s_lp[kn + 1]); nk_c = UNI(s_nk[kn]); }
+                    const int nwk = (nk_c + 63) >> 6, wslot = q - lp_c;
+                    const int ii = lane * nwk + wslot;
+                    if (ii < nk_c) { nb = perm[ii]; nfs = r_fs[nb]; nend = r_end[nb]; nk0 = ((int)r_kl[nb] & 0xFF) + ((kn - 1) << EV_LGR); }
+                } else {
+                    int wslot = q - nruns, lv = 0;                                // left-over level lv: the rays with more than lv left-overs
+                    while (wslot >= nwb) { wslot -= nwb; ++lv; }
+                    const int bb = lane * nwb + wslot;
+                    if (bb < v.B) {
+                        const int kl = (int)r_kl[bb], len = kl >> 8;
+                        if ((len & (EV_R - 1)) > lv) { nb = bb; nfs = r_fs[bb]; nend = r_end[bb]; nk0 = (kl & 0xFF) + (len & ~(EV_R - 1)) + lv; }
+                    }
+                }
             };
             // (Drawing the items from a queue balances the waves - the oldest wave of every SIMD is served first and waits a third
             // of the walk for the youngest - and was 0.7 % faster, at the price of 20 spilled registers: 330 MB of scratch traffic per
             // 4096-particle launch.  A fixed share per wave it is.)
-            fetch_item(wave);
-            for (int q = wave; q < nitems; q += EB / 64) {
+            fetch_item(wave_u);
+            for (int q = wave_u; q < nitems; q = UNI(q + EB / 64)) {
                 const int b = nb; const uint32_t fs = nfs; const int32_t re = nend;
-                k = kn + nka - 1;                                                 // the ray's chunk at this relative level
+                const int k = nk0;                                                // the item's first chunk
+                const int nch = q < nruns ? EV_R : 1;                               // its chunks
                 if (b < 0) { fetch_item(q + EB / 64); continue; }
                 const int ex = (int)(int16_t)(re & 0xFFFF), ey = (int)(int16_t)((uint32_t)re >> 16);
                 const int aex = ex < 0 ? -ex : ex, aey = ey < 0 ? -ey : ey;
                 const int sxs = ex > 0 ? stride : -stride, sy1 = ey > 0 ? 1 : -1;
                 const int cj = aey > aex ? sy1 : sxs, cm = aey > aex ? sxs : sy1;
-                const int j0 = NEAR_R + (k - 1) * LCH;
+                int j0 = NEAR_R + (k - 1) * LCH;
                 const unsigned long long pr64 = (unsigned long long)fs * (unsigned)j0 + 0x80000000ull;
-                uint32_t acc = (uint32_t)pr64, m = 0;
+                uint32_t acc = (uint32_t)pr64;
                 int c = base0 + __mul24(j0, cj) + __mul24((int)(pr64 >> 32), cm);
                 const int d0 = cj, d1 = cj + cm;
-                uint32_t ret[LCH]; int sh[LCH];
+                // chunk after chunk: sixteen adds in flight, one wait, their sixteen answers; after step 15 the accumulator and the
+                // address are those of the next chunk's step 0 (not unrolled: one set of answers' registers)
+#pragma nounroll
+                for (int i = 0; i < nch; ++i, j0 += LCH) {
+                    uint32_t m = 0;
+                    uint32_t ret[LCH]; int sh[LCH];
 #pragma unroll
-                for (int u = 0; u < LCH; ++u) {
-                    sh[u] = c << 3;
-                    ret[u] = ev_lds_add_rtn(c & ~3, 2u << (sh[u] & 31));
-                    const uint32_t nacc = acc + fs;
-                    c += nacc < acc ? d1 : d0;
-                    acc = nacc;
+                    for (int u = 0; u < LCH; ++u) {
+                        sh[u] = c << 3;
+                        ret[u] = ev_lds_add_rtn(c & ~3, 2u << (sh[u] & 31));
+                        const uint32_t nacc = acc + fs;
+                        c += nacc < acc ? d1 : d0;
+                        acc = nacc;
+                    }
+                    if (i == 0) fetch_item(q + EB / 64);
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_waitcnt(0xC07F);                            // lgkmcnt(0): one wait, then the sixteen answers
+#pragma unroll
+                    for (int u = 0; u < LCH; ++u) m = __builtin_amdgcn_alignbit(ev_flag_bit(ret[u], sh[u]), m, 1);
+                    if (m) log_events(m, b, j0, ev_lo, ev_hi, gx_base, !whole);
                 }
-                fetch_item(q + EB / 64);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);                                // lgkmcnt(0): one wait, then the sixteen answers
-#pragma unroll
-                for (int u = 0; u < LCH; ++u) m = __builtin_amdgcn_alignbit(ret[u] >> (sh[u] & 31), m, 1);
-                if (m) log_events(m, b, j0, ev_lo, ev_hi, gx_base, !whole);
             }
         }
         BAR_LDS();
