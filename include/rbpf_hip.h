@@ -553,6 +553,44 @@ int  rbpf_travel_cost(rbpf_handle* h, int32_t particle, const int32_t* box4, con
  * every block in every round would be out3[0] * out3[2] block runs. */
 int  rbpf_travel_stats(rbpf_handle* h, uint64_t* out3);
 
+/* ---- path checks: is this path free, in which share of the posterior, and which of these rollouts keeps clear of the walls? ----
+ * n_paths polylines walked cell by cell through the map of `particle` and every step's cell tested.  xy is [path_start[n_paths]][2]
+ * waypoints in metres, path_start [n_paths + 1] their CSR offsets, strictly increasing from 0: every path has at least one
+ * waypoint.  v(X, Y), occ(c) (strict), inv, the cell of a point (floor(x * inv), float64, on the host), d(c) over ALL occupied cells
+ * of the map, the chamfer units, 0 <= inflate < clear_max <= 320 and blocked(c) with or without the through-unknown flag are those
+ * of rbpf_travel_cost.
+ * The walk, in exact integers and in closed form (no step depends on the step before it): step 0 of a path is the cell of waypoint
+ * 0.  A segment from cell A to cell B with ax = |XB - XA|, ay = |YB - YA|, n = max(ax, ay) and signs sx, sy adds the steps
+ * t = 1 .. n: if ax >= ay, X = XA + sx t and Y = YA + sy floor((2 t ay + n) / (2 n)); otherwise with the roles of x and y swapped.
+ * n = 0 adds nothing.  Consecutive cells are 8-neighbours, step n stands on B, and steps[k] = 1 + the sum of n over path k.
+ *   ok(c)         = !blocked(c) and d(c) > inflate; with RBPF_PATHS_START_EXEMPT ok(cell of step 0) is true wherever that cell is tested
+ *   blocked step  = its cell is not ok, or it is diagonal (both coordinates differ from the cell (Xp, Yp) of the step before) and
+ *                   (X, Yp) or (Xp, Y) is not ok: T and the no-corner-cut rule of rbpf_travel_cost, so a path that plan.path_to walks
+ *                   down a cost field checks clear in the same map with the same inflate and RBPF_PATHS_START_EXEMPT
+ *   out[..][4]    = {first_blocked: the least blocked step, -1 if none;  first_unknown: the least step whose cell has v == 0, -1 if
+ *                   none;  min_clearance: min over the path's cells (side cells not included) of min(d, clear_max);  n_unknown: the
+ *                   number of steps whose cell has v == 0, a cell visited again counted again}                       (int32)
+ * All four are order-free reductions of exact integers: bit-identical from call to call.
+ * particle >= 0: out is [n_paths][4].  particle == -1: out is [P][n_paths][4], EVERY path in EVERY particle's map (as
+ * rbpf_view_gain).  particle == -1 with RBPF_PATHS_OWN: n_paths = P * K, the paths [p K, (p + 1) K) are checked in the map of
+ * particle p alone (rollouts from each particle's own pose), and out is [P][K][4].
+ * steps (may be NULL) is a host array [n_paths], computed on the host and complete on return whatever the flags.
+ * A waypoint whose cell lies outside the tile lattice is RBPF_EINVAL (the message names the path and the waypoint), so every walked
+ * cell lies in the lattice and only the clearance margin can leave it, where v = 0.  Also RBPF_EINVAL: a NULL xy, path_start or out, a
+ * non-finite coordinate, an offset table that does not start at 0 or does not increase strictly, n_paths < 1, a bad particle,
+ * inflate, clear_max or flag, RBPF_PATHS_OWN without particle == -1 or with n_paths % P != 0, a path of more than 2^20 steps, and
+ * 2^29 or more results (P * n_paths with particle == -1 without RBPF_PATHS_OWN, n_paths otherwise).  A call between
+ * rbpf_scan_update_begin and _end is RBPF_ESTATE.  Everything is checked before anything is queued, and nothing is written on an
+ * error.  The call changes no engine state (maps, particles, random streams, counters, duplicate grouping).  It runs on the
+ * handle's stream, in one launch over (particle, path) with no per-particle scratch; without RBPF_PATHS_DEVICE_OUT out is a host
+ * array, complete on return.  DESIGN.md 3.22 has the kernel. */
+#define RBPF_PATHS_DEVICE_OUT      1u  /* out is a device pointer, written in stream order, no host wait */
+#define RBPF_PATHS_THROUGH_UNKNOWN 2u  /* as RBPF_TRAVEL_THROUGH_UNKNOWN */
+#define RBPF_PATHS_START_EXEMPT    4u  /* the cell of a path's first waypoint counts as traversable (the robot is where it is) */
+#define RBPF_PATHS_OWN             8u  /* particle == -1 only: path group p belongs to particle p */
+int  rbpf_check_paths(rbpf_handle* h, int32_t particle, const double* xy, const int32_t* path_start, int32_t n_paths,
+                      int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out, int32_t* steps);
+
 /* ---- frontier regions: where does the known map end, and how large is each opening? ---------------------------------------
  * The frontier cells of the box box4 (cells, raster layout and v(X, Y) as for rbpf_travel_cost; occ(c) = v(c) * quantum >
  * occupied_threshold, strict) in the map of `particle`, their connected components, and a table of the largest.  With nx = x1-x0,

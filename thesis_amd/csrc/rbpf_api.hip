@@ -12,6 +12,7 @@
 
 #include "rbpf_host.h"
 #include "rbpf_scanbatch.h"
+#include "rbpf_pathbatch.h"
 
 using namespace rbpf;
 
@@ -2185,6 +2186,50 @@ int rbpf_travel_stats(rbpf_handle* h, uint64_t* out3) {
     if (!h) return RBPF_EINVAL;
     if (!out3) return fail(h, RBPF_EINVAL, "out3 is NULL");
     for (int k = 0; k < 3; ++k) out3[k] = h->travel_stats[k];
+    return RBPF_OK;
+}
+
+// ---- path checks (kernels_paths.hip; the host side is rbpf_pathbatch.h) ---------------------------------------------------------
+static_assert(RBPF_PATHS_DEVICE_OUT == PATHS_DEVICE_OUT && RBPF_PATHS_THROUGH_UNKNOWN == PATHS_THROUGH_UNKNOWN &&
+              RBPF_PATHS_START_EXEMPT == PATHS_START_EXEMPT && RBPF_PATHS_OWN == PATHS_OWN, "rbpf_pathbatch.h repeats the flags of rbpf_hip.h");
+int rbpf_check_paths(rbpf_handle* h, int32_t particle, const double* xy, const int32_t* path_start, int32_t n_paths, int32_t inflate,
+                     int32_t clear_max, uint32_t flags, int32_t* out, int32_t* steps) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    ARG_TRY(h, check_path_args(xy, path_start, out, particle, v.P, n_paths, inflate, clear_max, flags));
+    ARG_TRY(h, check_path_results(particle, v.P, n_paths, flags));
+    const long long off = (long long)v.R * v.dim + v.dim / 2;             // mosaic X + off counts from the lattice's first cell
+    PathBatch pb;
+    path_batch_build(pb, xy, path_start, n_paths, (double)v.dim / v.tile_len, -off, (long long)v.L * v.dim - off);
+    ARG_TRY(h, pb.error());
+    MID_STEP_TRY(h, "a path check");
+    const bool dev_out = (flags & RBPF_PATHS_DEVICE_OUT) != 0;
+    const size_t nw = pb.wstep.size(), nres = (size_t)path_results(particle, v.P, n_paths, flags);
+    Carve c;                                                               // scratch: [cells] [steps of the waypoints] [offsets] | host out
+    const size_t cell_at = c.pack(nw * 8), wstep_at = c.pack(nw * 4), start_at = c.pack(((size_t)n_paths + 1) * 4), in_b = c.close();
+    const size_t out_at = c.take(dev_out ? 0 : nres * 16);
+    HIP_TRY(h, h->reserve(B_PATHS, c.total()));
+    const Block& d = h->buf[B_PATHS];
+    Staging& st = h->stage[S_PATHS];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    memcpy(st.p + cell_at, pb.cells.data(), nw * 8);
+    memcpy(st.p + wstep_at, pb.wstep.data(), nw * 4);
+    memcpy(st.p + start_at, path_start, ((size_t)n_paths + 1) * 4);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    PathArgs a;
+    a.cells = d.as<const int32_t>(cell_at); a.wstep = d.as<const int32_t>(wstep_at); a.path_start = d.as<const int32_t>(start_at);
+    a.n_paths = n_paths; a.particle = particle >= 0 ? particle : 0;
+    a.own_k = path_group_size(n_paths, v.P, flags);
+    a.pairs = (long long)nres;
+    a.inflate = inflate; a.clear_max = clear_max;
+    a.through_unknown = (flags & RBPF_PATHS_THROUGH_UNKNOWN) != 0; a.start_exempt = (flags & RBPF_PATHS_START_EXEMPT) != 0;
+    a.out = dev_out ? out : d.as<int32_t>(out_at);
+    launch_check_paths(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    if (!dev_out)
+        if (const int rc = fetch(h, {{out, a.out, nres * 16}})) return rc;
+    if (steps) memcpy(steps, pb.steps.data(), (size_t)n_paths * 4);        // behind everything that can fail: nothing is written on an error
     return RBPF_OK;
 }
 

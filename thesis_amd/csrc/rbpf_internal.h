@@ -317,6 +317,22 @@ struct TravelArgs : BlockRelaxArgs {      // ras: the cost field, TRAVEL_INF on 
     int32_t* goal_out;                 // [n_part][n_goals] output or null
 };
 
+// path checks (kernels_paths.hip): polylines of waypoint cells walked through one particle's map, every particle's map
+// or each its own particle's; one wave per (particle, path), result r = particle * n_paths + path (particle counted from 0 only
+// when every particle is asked for), or r = path where a path belongs to one particle (own_k)
+struct PathArgs {
+    const int32_t* cells;              // [n_waypoints][2] waypoint cells, counted from the lattice's first cell
+    const int32_t* wstep;              // [n_waypoints] the step of its path at which the walk stands on the waypoint
+    const int32_t* path_start;         // [n_paths + 1] first waypoint of each path
+    int n_paths;
+    int particle;                      // the map of result 0: the particle asked for, or 0
+    int own_k;                         // > 0: path k is checked in the map of particle k / own_k alone
+    long long pairs;                   // results: n_paths, or n_particles * n_paths
+    int inflate, clear_max;            // a cell carries the robot if d > inflate; min_clearance is capped at clear_max
+    int through_unknown, start_exempt; // 1: blocked = occupied, else v >= 0; 1: the cell of step 0 always carries the robot
+    int32_t* out;                      // [pairs][4] first_blocked, first_unknown, min_clearance, n_unknown
+};
+
 // frontier regions (kernels_frontier.hip): frontier cells of a box of one particle's map, or of a batch of particles'
 // maps, their connected components and a table of the largest.  Blocks, particles of the batch and box-relative cells as in
 // TravelArgs; the label of a cell is L = i * ny + j.
@@ -473,6 +489,7 @@ void launch_score_surface(const SurfaceArgs& a, hipStream_t s);                 
 void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);   // a.packed and a.n_items preset to 0
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
+void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s);   // one wave per (particle, path)
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran
 void launch_travel_output(const TravelArgs& a, hipStream_t s);                   // cost_out and goal_out from the finished field

@@ -965,6 +965,51 @@ class ParticleEngine:
         self._check(self._lib.rbpf_travel_stats(self._h, out))
         return {"rounds": int(out[0]), "block_runs": int(out[1]), "blocks": int(out[2])}
 
+    # -- path checks (include/rbpf_hip.h: rbpf_check_paths; thesis_amd/plan.py) ------------------------------------
+    def check_paths(self, paths, particle="best", radius_m: float = 0.0, clear_max: Optional[int] = None, through_unknown: bool = False,
+                    start_exempt: bool = False, own: bool = False, device: bool = False):
+        """Walks `paths` cell by cell through a particle's map and tests every step: `paths` is [K, M, 2+] (metres; further
+        columns are ignored) or a list of K arrays [m_k, 2+].  A step is blocked if its cell is not known free (with
+        through_unknown: is occupied) or its clearance does not exceed inflate = floor(radius_m * cells per metre * 5), or if it is
+        diagonal and cuts a corner; start_exempt: the cell of a path's first waypoint always carries the robot.  `particle`: an
+        index, "best" (the first argmax of weights()), or None: every path in EVERY particle's map, results [P, K].  own=True
+        (particle=None only): `paths` is [P, K, M, 2+] and the paths of group p are checked in particle p's map alone, e.g.
+        rollouts from every particle's own pose.  Returns plan.PathCheck(first_blocked, first_unknown, min_clearance, n_unknown,
+        steps, cell, inflate, clear_max): int32 [K] or [P, K]; steps is numpy int32 [K] ([P, K] with own).  min_clearance is
+        capped at `clear_max` (default and at least inflate + 1).  device=True: torch tensors on the engine's device, ready for
+        work on torch's current stream (steps stays numpy)."""
+        from .plan import PathCheck
+        p = self._particle(particle)
+        if own:
+            if p >= 0:
+                raise ValueError("own=True needs particle=None")
+            a = _f64(paths)
+            if a.ndim != 4 or a.shape[0] != self.P or a.shape[3] < 2:
+                raise ValueError("with own=True paths must be [P, K, M, 2+]")
+            lead, plist = a.shape[:2], list(a.reshape((-1,) + a.shape[2:]))
+        else:
+            plist = list(paths) if isinstance(paths, (list, tuple)) else list(_f64(paths))
+            lead = (len(plist),)
+        plist = [_f64(q) for q in plist]
+        if not plist or any(q.ndim != 2 or q.shape[1] < 2 or q.shape[0] < 1 for q in plist):
+            raise ValueError("paths must be [K, M, 2+] or a list of [m, 2+] arrays, K >= 1 and every m >= 1")
+        xy = np.ascontiguousarray(np.concatenate([q[:, :2] for q in plist]))
+        start = np.zeros(len(plist) + 1, dtype=np.int32)
+        np.cumsum([q.shape[0] for q in plist], out=start[1:])
+        inv = self.dim / float(self.cfg.tile_len_m)
+        inflate = int(np.floor(float(radius_m) * inv * 5.0))
+        cmax = max(inflate + 1, inflate + 1 if clear_max is None else int(clear_max))
+        shape = lead if p >= 0 or own else (self.P,) + lead
+        steps = np.zeros(len(plist), dtype=np.int32)
+        out = self._outputs(device)
+        res = out.empty(shape + (4,), "int32")
+        flags = ((_lib.RBPF_PATHS_DEVICE_OUT if device else 0) | (_lib.RBPF_PATHS_THROUGH_UNKNOWN if through_unknown else 0)
+                 | (_lib.RBPF_PATHS_START_EXEMPT if start_exempt else 0) | (_lib.RBPF_PATHS_OWN if own else 0))
+        with out:
+            self._check(self._lib.rbpf_check_paths(self._h, p, _dp(xy), _ip(start), len(plist), inflate, cmax, flags, out.ptr(res), _ip(steps)))
+        return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps.reshape(lead), float(self.cfg.tile_len_m) / self.dim,
+                         inflate, cmax)
+
     # -- frontier regions (include/rbpf_hip.h: rbpf_frontier_regions; DESIGN.md 3.13; thesis_amd/explore.py) ----------------------
     def frontier_regions(self, particle="best", box=None, clearance_cells: int = 4, min_size: int = 1, max_regions: int = 64,
                          labels: bool = True, device: bool = False):

@@ -1,5 +1,6 @@
 """Paths from a travel-cost field (ParticleEngine.travel_cost; include/rbpf_hip.h, rbpf_travel_cost).  Host side,
-NumPy only: the field is the work of the GPU, a path is a walk down it."""
+NumPy only: the field is the work of the GPU, a path is a walk down it.  Below that, what goes with ParticleEngine.check_paths
+(rbpf_check_paths): the result type, the cells of a walk, any-angle shortcuts, velocity rollouts and their ranking."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -57,3 +58,170 @@ def path_to(travel: Travel, goal_xy):
         cells.append((i, j))
     out = np.array(cells[::-1], dtype=np.float64) + np.array([x0 + 0.5, y0 + 0.5])
     return out * float(travel.cell)
+
+
+# ---- path checks (ParticleEngine.check_paths; include/rbpf_hip.h, rbpf_check_paths) -----------------------------
+def _host(a):
+    """A result as numpy, wherever it lives."""
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+class PathCheck(NamedTuple):
+    first_blocked: np.ndarray        # int32 [K], or [P, K]: the least blocked step of each path, -1 if none
+    first_unknown: np.ndarray        # int32 likewise: the least step on an unknown cell (lattice value 0), -1 if none
+    min_clearance: np.ndarray        # int32 likewise: min over the path's cells of min(chamfer distance to an occupied cell, clear_max)
+    n_unknown: np.ndarray            # int32 likewise: steps on unknown cells
+    steps: np.ndarray                # int32 [K] (with own=True [P, K]): steps of each path, 1 + the sum of its segments' max(|dX|, |dY|)
+    cell: float                      # metres per cell
+    inflate: int                     # a cell carries the robot if its clearance exceeds inflate
+    clear_max: int
+
+    @property
+    def clear(self):
+        """bool, the shape of first_blocked: no step of the path is blocked."""
+        return self.first_blocked < 0
+
+    def p_clear(self, weights=None):
+        """float64 [K]: the share of the particles in whose map each path is clear, weighted by `weights` [P] (non-negative,
+        normalised here; default: equal).  For one particle's result it is clear as 0.0 / 1.0."""
+        c = _host(self.first_blocked) < 0
+        if c.ndim == 1:
+            return c.astype(np.float64)
+        w = np.full(c.shape[0], 1.0) if weights is None else np.asarray(weights, dtype=np.float64)
+        if w.shape != (c.shape[0],) or not np.all(w >= 0) or not w.sum() > 0:
+            raise ValueError("weights must be [P], non-negative and not all zero")
+        return (w / w.sum()) @ c.astype(np.float64)
+
+    def clearance_metres(self):
+        """min_clearance in metres (float64): chamfer units are a fifth of a cell."""
+        return _host(self.min_clearance).astype(np.float64) * (float(self.cell) / AXIAL)
+
+
+def walk_cells(cells):
+    """int64 [S, 2]: the walk of rbpf_check_paths through the waypoint cells `cells` [m, 2], in its closed form: a segment from A
+    to B with n = max(|dX|, |dY|) adds the steps t = 1 .. n, the major coordinate moving by one a step and the minor one by
+    floor((2 t a + n) / (2 n)), a its whole change.  S = 1 + the sum of n."""
+    c = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+    out = [c[:1]]
+    for A, B in zip(c[:-1], c[1:]):
+        d = B - A
+        a = np.abs(d)
+        n = int(a.max())
+        if n == 0:
+            continue
+        t = np.arange(1, n + 1, dtype=np.int64)
+        major = 0 if a[0] >= a[1] else 1
+        minor = 1 - major
+        seg = np.empty((n, 2), np.int64)
+        seg[:, major] = A[major] + (-1 if d[major] < 0 else 1) * t
+        seg[:, minor] = A[minor] + (-1 if d[minor] < 0 else 1) * ((2 * t * a[minor] + n) // (2 * n))
+        out.append(seg)
+    return np.concatenate(out)
+
+
+def path_cells(path, inv: float):
+    """int64 [S, 2]: the cells rbpf_check_paths walks along `path` [m, 2+] (metres; a point lies in cell floor(x * inv)), step by
+    step: row s is the place of a first_blocked or first_unknown of s."""
+    p = np.asarray(path, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or len(p) < 1:
+        raise ValueError("path must be [m, 2+] with m >= 1")
+    return walk_cells(np.floor(p[:, :2] * np.float64(inv)).astype(np.int64))
+
+
+def shortcut(path, segments_clear, lookahead: int = 64):
+    """Any-angle smoothing of `path` [n, 2+] (e.g. the cell path of path_to): the chain of its waypoints from the first to the
+    last of least Euclidean length whose legs are all clear; ties go to fewer waypoints, then to the lower waypoint index.
+    `segments_clear(legs) -> bool [len(legs)]` is asked once, for the straight legs path[i] -> path[j] of all pairs
+    0 < j - i <= lookahead, each a [2, 2] polyline.  Returns the chain [k, 2]; ValueError where no chain of clear legs joins
+    the ends (the path itself does not check clear)."""
+    p = np.asarray(path, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or len(p) < 1:
+        raise ValueError("path must be [n, 2+] with n >= 1")
+    p = p[:, :2]
+    n, look = len(p), max(1, int(lookahead))
+    if n == 1:
+        return p.copy()
+    pairs = [(i, j) for i in range(n - 1) for j in range(i + 1, min(i + look, n - 1) + 1)]
+    ok = np.asarray(segments_clear([p[[i, j]] for i, j in pairs]), dtype=bool)
+    if ok.shape != (len(pairs),):
+        raise ValueError("segments_clear must return one bool per leg")
+    best = [(0.0, 0, -1)] + [None] * (n - 1)              # (length, waypoints so far, predecessor)
+    for (i, j), good in zip(pairs, ok):                   # pairs in the order of i: every best[i] is final when it is read
+        if not good or best[i] is None:
+            continue
+        cand = (best[i][0] + float(np.hypot(*(p[j] - p[i]))), best[i][1] + 1)
+        # lengths within rounding of each other (collinear waypoints) are a tie: sums of square roots are not exact
+        tie = best[j] is not None and abs(cand[0] - best[j][0]) <= 1e-12 * max(cand[0], best[j][0])
+        if best[j] is None or (cand[1] < best[j][1] if tie else cand[0] < best[j][0]):
+            best[j] = cand + (i,)
+    if best[-1] is None:
+        raise ValueError("no chain of clear legs joins the ends of the path")
+    chain, k = [], n - 1
+    while k >= 0:
+        chain.append(k)
+        k = best[k][2]
+    return p[chain[::-1]]
+
+
+def shortcut_in(engine, path, particle="best", radius_m: float = 0.0, min_share: float = 1.0, weights=None, lookahead: int = 64,
+                through_unknown: bool = False, start_exempt: bool = True):
+    """shortcut(path) with the legs checked by engine.check_paths in the map of `particle`, or with particle=None in every
+    particle's: a leg is clear if its share PathCheck.p_clear(weights) reaches `min_share`.  start_exempt holds for the legs that
+    leave the path's first waypoint, as it would for the path itself; they are checked in a call of their own."""
+    p0 = np.asarray(path, dtype=np.float64)[0, :2]
+
+    def clear(legs):
+        ok = np.zeros(len(legs), dtype=bool)
+        first = np.array([start_exempt and np.array_equal(leg[0], p0) for leg in legs], dtype=bool)
+        for exempt in (False, True):
+            idx = np.flatnonzero(first == exempt)
+            if len(idx):
+                chk = engine.check_paths(np.stack([legs[k] for k in idx]), particle=particle, radius_m=radius_m,
+                                         through_unknown=through_unknown, start_exempt=exempt)
+                ok[idx] = chk.p_clear(weights) >= float(min_share)
+        return ok
+
+    return shortcut(path, clear, lookahead)
+
+
+def rollouts(poses, speeds, turn_rates, horizon_s: float, dt: float):
+    """Constant-(v, w) arcs from `poses` ([3] or [P, 3]: x, y, theta) in closed form: [K, M, 2] for one pose, [P, K, M, 2] for
+    [P, 3], rollout k driving speeds[k] (m/s) and turn_rates[k] (rad/s) for M = round(horizon_s / dt) + 1 points at t = 0, dt, ...
+    The point at t is the chord of the arc: x + v t sinc(w t / 2) cos(theta + w t / 2), and y with sin: exact, and the straight
+    line at w = 0."""
+    ps = np.asarray(poses, dtype=np.float64)
+    v, w = np.asarray(speeds, dtype=np.float64).reshape(-1), np.asarray(turn_rates, dtype=np.float64).reshape(-1)
+    if ps.shape[-1] != 3 or ps.ndim not in (1, 2) or v.shape != w.shape or not dt > 0 or not horizon_s >= 0:
+        raise ValueError("poses must be [3] or [P, 3], speeds and turn_rates [K], dt > 0 and horizon_s >= 0")
+    t = np.arange(int(round(float(horizon_s) / float(dt))) + 1, dtype=np.float64) * float(dt)
+    half = 0.5 * w[:, None] * t[None, :]                                   # [K, M]
+    chord = v[:, None] * t[None, :] * np.sinc(half / np.pi)                # numpy's sinc(x) is sin(pi x) / (pi x)
+    q = ps.reshape(-1, 3)
+    ang = q[:, None, None, 2] + half[None]
+    out = np.stack([q[:, None, None, 0] + chord[None] * np.cos(ang), q[:, None, None, 1] + chord[None] * np.sin(ang)], axis=-1)
+    return out[0] if ps.ndim == 1 else out
+
+
+def rank_rollouts(check: PathCheck, end_cost=None, weights=None, min_p_clear: float = 0.95, clearance_weight: float = 0.0):
+    """The rollouts of `check` ([K], or [P, K] from particle=None or own=True) worth driving, best first, as indices into K: those
+    with p_clear(weights) >= min_p_clear, ordered by the least expected end_cost - clearance_weight * expected min_clearance
+    (both in chamfer units), or without `end_cost` by the largest expected min_clearance; ties go to the lower index.  `end_cost`
+    ([K] or [P, K]) is the cost at the arcs' ends, e.g. the goal_cost of a travel_cost whose START is the goal; -1 (no way)
+    counts as infinite."""
+    fb = _host(check.first_blocked)
+    many = fb.ndim == 2
+    w = None
+    if many:
+        w = np.full(fb.shape[0], 1.0) if weights is None else np.asarray(weights, dtype=np.float64)
+        w = w / w.sum()
+    # over the particles that carry weight: an infinite cost in a particle of weight 0 must not turn the mean into 0 * inf
+    mean = lambda a: (w[w > 0] @ a[w > 0]) if many and a.ndim == 2 else a
+    p = check.p_clear(weights)
+    clearance = mean(_host(check.min_clearance).astype(np.float64))
+    if end_cost is None:
+        score = -clearance
+    else:
+        c = _host(end_cost).astype(np.float64)
+        score = mean(np.where(c < 0, np.inf, c)) - float(clearance_weight) * clearance
+    keep = np.flatnonzero(p >= float(min_p_clear))
+    return keep[np.argsort(score[keep], kind="stable")]
