@@ -591,6 +591,49 @@ int  rbpf_travel_stats(rbpf_handle* h, uint64_t* out3);
 int  rbpf_check_paths(rbpf_handle* h, int32_t particle, const double* xy, const int32_t* path_start, int32_t n_paths,
                       int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out, int32_t* steps);
 
+/* ---- scan checks: how well does the scan the robot took agree with a particle's map? ----------------------------------------
+ * ranges is [n_scans][n_beams] in metres, n_scans 1 (one scan, checked at every pose) or n_poses (scan n at pose n); non-finite
+ * and non-positive ranges are data and are classified below.  particle >= 0: every pose (x, y, theta) is checked in that particle's
+ * map; particle == -1: n_poses must equal P and pose n is checked in particle n's map, the pairing of rbpf_cast_scans.
+ * Beam b of pose n is the ray of rbpf_cast_scans (same host libm cos / sin of theta and of the angles, same float64 supercover walk
+ * with every operation rounded on its own, same tie rule, strict "occupied" test and lattice test); only the limit
+ * differs.  With inv = dim / tile_len, z the beam's measured range, tz = z * inv, ttol = tol * inv and tmax = max_range * inv, each
+ * beam gets a class (uint8):
+ *   0 RBPF_SCAN_SKIP     !(z > 0) - NaN, -inf, 0 and negatives - or z < min_range.  No walk.
+ *   a returned beam, z < max_range, is walked with tlim = min(tz + ttol, tmax):
+ *   1 RBPF_SCAN_MATCH    the walk hits (status 1) at entry parameter t, and d = t - tz >= -ttol
+ *   2 RBPF_SCAN_LONG     the walk hits and d < -ttol: the map holds a wall well in front of the measured end
+ *   3 RBPF_SCAN_SHORT    no hit within tlim (status 0) and v(E) < 0, E the last cell the walk tested whose entry parameter is <= tz
+ *                        (the origin cell is entered at 0) and v the lattice value of rbpf_render_map (0 without a tile and outside a
+ *                        tile's written box): the beam ended in observed-free space, on something the map does not hold
+ *   4 RBPF_SCAN_NEW      status 0 and v(E) >= 0: the end lies in unknown space, or on a cell not yet over the threshold
+ *   5 RBPF_SCAN_OFF      the ray or its origin left the tile lattice (status 2), for returned and no-return beams alike
+ *   a no-return beam, z >= max_range (+inf included), is walked with tlim = tmax:
+ *   6 RBPF_SCAN_MISSING  the walk hits: the map holds a wall within max_range that the sensor did not report
+ *   7 RBPF_SCAN_CLEAR    no hit
+ * Cost, in exact integers: a MATCH or LONG beam has the bin q = clamp(floor(d * bins_per_cell + 0.5), -half_bins, half_bins), the
+ * clamp applied to the float64 before the conversion, and costs class_cost8[class] + hit_tab[q + half_bins]; every other beam costs
+ * class_cost8[class].  hit_tab has 2 * half_bins + 1 entries; 1 <= half_bins <= 4096, 1 <= bins_per_cell <= 64; every entry of both
+ * tables lies in 0 .. 2^20 (thesis_amd/sensor.py builds them from a beam model: cost / 65536 then reads as bits).
+ *   cost[n_poses]             int64: the sum over the pose's beams.  Required.
+ *   counts[n_poses][8]        int32: beams per class.  May be NULL.
+ *   classes[n_poses][n_beams] uint8.  May be NULL.
+ *   votes[n_beams][8]         int32: in how many of the n_poses poses the beam fell into each class.  May be NULL.
+ * All are order-free reductions of exact integers: bit-identical from call to call.  DESIGN.md 3.23 has the kernel.
+ * A NULL poses_n3, ranges, angles, hit_tab, class_cost8 or cost, a non-finite pose or angle, max_range not finite or not > 0,
+ * min_range or tol not finite or < 0, a bad half_bins or bins_per_cell, a table entry out of range, n_scans neither 1 nor n_poses,
+ * n_poses < 1, n_beams < 1, n_poses * n_beams >= 2^31, a bad particle, n_poses != P with particle == -1 or an unknown flag is
+ * RBPF_EINVAL; a call between rbpf_scan_update_begin and _end is RBPF_ESTATE; everything is checked before anything is queued, and
+ * nothing is written on an error.  The call changes no engine state (maps, particles, random streams, counters, duplicate
+ * grouping).  It runs on the handle's stream; without RBPF_SCANS_DEVICE_OUT the outputs are host arrays, complete on return. */
+#define RBPF_SCANS_DEVICE_OUT 1u   /* cost / counts / classes / votes are device pointers, written in stream order, no host wait */
+enum { RBPF_SCAN_SKIP = 0, RBPF_SCAN_MATCH = 1, RBPF_SCAN_LONG = 2, RBPF_SCAN_SHORT = 3, RBPF_SCAN_NEW = 4, RBPF_SCAN_OFF = 5,
+       RBPF_SCAN_MISSING = 6, RBPF_SCAN_CLEAR = 7 };
+int  rbpf_check_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* ranges,
+                      int32_t n_scans, const double* angles, int32_t n_beams, double max_range, double min_range, double tol,
+                      const int32_t* hit_tab, int32_t half_bins, int32_t bins_per_cell, const int32_t* class_cost8, uint32_t flags,
+                      int64_t* cost, int32_t* counts, uint8_t* classes, int32_t* votes);
+
 /* ---- frontier regions: where does the known map end, and how large is each opening? ---------------------------------------
  * The frontier cells of the box box4 (cells, raster layout and v(X, Y) as for rbpf_travel_cost; occ(c) = v(c) * quantum >
  * occupied_threshold, strict) in the map of `particle`, their connected components, and a table of the largest.  With nx = x1-x0,

@@ -2037,6 +2037,60 @@ int rbpf_view_gain(rbpf_handle* h, int32_t particle, const double* poses_n3, int
     return dev_out ? RBPF_OK : fetch(h, {{gain, a.gain, nres * 8}, {seen, a.seen, nres * 4}, {unknown, a.unknown, nres * 4}});
 }
 
+// ---- scan checks (kernels_scancheck.hip) ------------------------------------------------------------------------------------------
+int rbpf_check_scans(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* ranges, int32_t n_scans,
+                     const double* angles, int32_t n_beams, double max_range, double min_range, double tol, const int32_t* hit_tab,
+                     int32_t half_bins, int32_t bins_per_cell, const int32_t* class_cost8, uint32_t flags, int64_t* cost, int32_t* counts,
+                     uint8_t* classes, int32_t* votes) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    if (!poses_n3 || !ranges || !angles || !hit_tab || !class_cost8 || !cost)
+        return fail(h, RBPF_EINVAL, "poses, ranges, angles, hit_tab, class_cost8 or cost is NULL");
+    if (flags & ~RBPF_SCANS_DEVICE_OUT) return fail(h, RBPF_EINVAL, "unknown flags");
+    if (particle < -1 || particle >= v.P) return fail(h, RBPF_EINVAL, "particle index out of range");
+    ARG_TRY(h, check_counts(n_poses, 1, n_beams, 0, "n_poses >= 1, n_beams >= 1 and n_poses * n_beams < 2^31 are required"));
+    if (particle < 0 && n_poses != v.P) return fail(h, RBPF_EINVAL, "particle -1 checks pose n in particle n's map: n_poses must equal n_particles");
+    ARG_TRY(h, check_scan_count(n_scans, n_poses));
+    ARG_TRY(h, check_ranges(max_range, min_range));
+    ARG_TRY(h, check_tol(tol));
+    ARG_TRY(h, check_beam_tables(hit_tab, half_bins, bins_per_cell, class_cost8));
+    ARG_TRY(h, check_poses(poses_n3, n_poses));
+    ARG_TRY(h, check_angles(angles, n_beams));
+    MID_STEP_TRY(h, "a scan check");
+    const bool dev_out = (flags & RBPF_SCANS_DEVICE_OUT) != 0;
+    const size_t N = (size_t)n_poses, B = (size_t)n_beams, rays = N * B, nz = (size_t)n_scans * B, ntab = 8 + 2 * (size_t)half_bins + 1;
+    Carve c;                                                               // scratch: [poses] [beams] [ranges] [tables] | host cost, counts, votes, classes
+    const size_t pose_at = c.pack(N * 32), beam_at = c.pack(B * 16), range_at = c.pack(nz * 8), tab_at = c.pack(ntab * 4), in_b = c.close();
+    const size_t cost_at = c.take(dev_out ? 0 : N * 8), counts_at = c.take(dev_out || !counts ? 0 : N * 32);
+    const size_t votes_at = c.take(dev_out || !votes ? 0 : B * 32), classes_at = c.take(dev_out || !classes ? 0 : rays);
+    HIP_TRY(h, h->reserve(B_SCANCHECK, c.total()));
+    const Block& d = h->buf[B_SCANCHECK];
+    Staging& st = h->stage[S_SCANCHECK];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* zs = stage_beam2(stage_pose4(st.as<double>(), poses_n3, N), angles, B);
+    memcpy(zs, ranges, nz * 8);
+    stage_beam_tables(reinterpret_cast<int32_t*>(zs + nz), class_cost8, hit_tab, half_bins);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    ScanCheckArgs a;
+    a.pose4 = d.as<const double>(pose_at); a.beam2 = d.as<const double>(beam_at); a.ranges = d.as<const double>(range_at);
+    a.tabs = d.as<const int32_t>(tab_at);
+    a.n_poses = n_poses; a.B = n_beams; a.scan_each = n_scans == n_poses; a.particle = particle; a.half_bins = half_bins;
+    a.inv = (double)v.dim / v.tile_len;                                    // cells per metre, as rbpf_cast_scans forms it
+    a.tmax = max_range * a.inv; a.ttol = tol * a.inv;
+    a.max_range = max_range; a.min_range = min_range; a.bins_per_cell = (double)bins_per_cell;
+    a.cost = reinterpret_cast<unsigned long long*>(dev_out ? cost : d.as<int64_t>(cost_at));
+    a.counts = !counts ? nullptr : dev_out ? counts : d.as<int32_t>(counts_at);
+    a.votes = !votes ? nullptr : dev_out ? votes : d.as<int32_t>(votes_at);
+    a.classes = !classes ? nullptr : dev_out ? classes : d.as<uint8_t>(classes_at);
+    HIP_TRY(h, hipMemsetAsync(a.cost, 0, N * 8, h->stream));               // the kernel adds to all three
+    if (a.counts) HIP_TRY(h, hipMemsetAsync(a.counts, 0, N * 32, h->stream));
+    if (a.votes) HIP_TRY(h, hipMemsetAsync(a.votes, 0, B * 32, h->stream));
+    launch_check_scans(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return dev_out ? RBPF_OK : fetch(h, {{cost, a.cost, N * 8}, {counts, a.counts, N * 32}, {votes, a.votes, B * 32}, {classes, a.classes, rays}});
+}
+
 }  // extern "C"
 
 // ---- block relaxation (rbpf_blockrelax.h): what rbpf_travel_cost and rbpf_frontier_regions share on the host ------------------

@@ -57,6 +57,7 @@ enum {
     B_PLACES,                       // sectors and ranges, or limits and descriptor tables, dilated references, weights, chunk lists, host outputs
     B_SURFACE,                      // host volume, host drops, host outputs
     B_PATHS,                        // waypoint cells, waypoint steps, path offsets, host outputs
+    B_SCANCHECK,                    // poses, beams, ranges, cost tables, host outputs
     B_COUNT
 };
 
@@ -99,6 +100,7 @@ enum {
     S_TRACK,                        // the particle list or the weights
     S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_SURFACE,   // the upload of B_BUILD .. B_SURFACE: everything in front of the first '|' of its layout
     S_PATHS,                        // the upload of B_PATHS
+    S_SCANCHECK,                    // the upload of B_SCANCHECK
     S_COUNT
 };
 
@@ -155,7 +157,7 @@ struct rbpf_handle {
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;

@@ -333,6 +333,24 @@ struct PathArgs {
     int32_t* out;                      // [pairs][4] first_blocked, first_unknown, min_clearance, n_unknown
 };
 
+// scan checks (kernels_scancheck.hip): measured scans against the maps; ray r = pose * B + beam as in CastArgs
+struct ScanCheckArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
+    const double* beam2;               // [B][2] cos(angle), sin(angle)
+    const double* ranges;              // [n_scans][B] metres; NaN, +-inf, 0 and negatives are data
+    const int32_t* tabs;               // class_cost8 [8], then hit_tab [2 half_bins + 1]
+    int n_poses, B;
+    int scan_each;                     // 1: scan n belongs to pose n; 0: one scan for every pose
+    int particle;                      // >= 0: every pose in this particle's map; -1: pose n in particle n's
+    int half_bins;
+    double inv, tmax, ttol;            // cells per metre (dim / tile_len), max_range * inv, tol * inv
+    double max_range, min_range, bins_per_cell;
+    unsigned long long* cost;          // [n_poses], preset to 0
+    int32_t* counts;                   // [n_poses][8] or null, preset to 0
+    uint8_t* classes;                  // [n_poses][B] or null
+    int32_t* votes;                    // [B][8] or null, preset to 0
+};
+
 // frontier regions (kernels_frontier.hip): frontier cells of a box of one particle's map, or of a batch of particles'
 // maps, their connected components and a table of the largest.  Blocks, particles of the batch and box-relative cells as in
 // TravelArgs; the label of a cell is L = i * ny + j.
@@ -490,6 +508,7 @@ void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);  
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
 void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s);   // one wave per (particle, path)
+void launch_check_scans(const DevView& v, const ScanCheckArgs& a, hipStream_t s);   // a.cost, a.counts and a.votes preset to 0
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran
 void launch_travel_output(const TravelArgs& a, hipStream_t s);                   // cost_out and goal_out from the finished field

@@ -1,5 +1,5 @@
 // rbpf_scanbatch.h -- what the entry points over a batch of scans share on the host (rbpf_api.hip: cast, view gain, map building,
-// pose refinement, pair matching, scan description): the layout of a scratch block, the argument checks, the staging loops and
+// pose refinement, pair matching, scan description, scan checks): the layout of a scratch block, the argument checks, the staging loops and
 // the set-up of the pose search.  Plain C++17 and nothing of HIP, so that a program without a GPU can include it
 // (tests/host/scanbatch_test.cpp).
 #pragma once
@@ -40,6 +40,22 @@ static inline const char* check_finite(const double* p, long long n, const char*
 }
 static inline const char* check_poses(const double* poses_n3, int n) { return check_finite(poses_n3, 3LL * n, "poses must be finite"); }
 static inline const char* check_angles(const double* angles, int n) { return check_finite(angles, n, "angles must be finite"); }
+// scan checks (rbpf_check_scans): the tolerance, the pairing of scans with poses, and the two cost tables; the tables are read
+// only once their sizes are known to be good
+static inline const char* check_tol(double t) { return !std::isfinite(t) || t < 0.0 ? "tol must be finite and >= 0" : nullptr; }
+static inline const char* check_scan_count(long long n_scans, long long n_poses) {
+    return n_scans != 1 && n_scans != n_poses ? "n_scans must be 1 or n_poses" : nullptr;
+}
+static const int SCAN_HALF_BINS_MAX = 4096, SCAN_BINS_PER_CELL_MAX = 64, SCAN_COST_MAX = 1 << 20;
+static inline const char* check_beam_tables(const int32_t* hit_tab, int half_bins, int bins_per_cell, const int32_t* class_cost8) {
+    if (half_bins < 1 || half_bins > SCAN_HALF_BINS_MAX) return "1 <= half_bins <= 4096 is required";
+    if (bins_per_cell < 1 || bins_per_cell > SCAN_BINS_PER_CELL_MAX) return "1 <= bins_per_cell <= 64 is required";
+    for (int k = 0; k < 2 * half_bins + 1; ++k)
+        if (hit_tab[k] < 0 || hit_tab[k] > SCAN_COST_MAX) return "hit_tab entries must lie in 0 .. 2^20";
+    for (int k = 0; k < 8; ++k)
+        if (class_cost8[k] < 0 || class_cost8[k] > SCAN_COST_MAX) return "class_cost8 entries must lie in 0 .. 2^20";
+    return nullptr;
+}
 static inline bool search_substeps_ok(int S) { return S == 1 || S == 2 || S == 4 || S == 8 || S == 16; }
 static inline const char* check_search(int substeps, int n_trans, int n_rot) {
     if (!search_substeps_ok(substeps)) return "substeps must be 1, 2, 4, 8 or 16";
@@ -60,6 +76,11 @@ static inline double* stage_pose4(double* dst, const double* poses_n3, size_t n)
 }
 static inline double* stage_beam2(double* dst, const double* angles, size_t n) {         // [cos a, sin a]
     for (size_t b = 0; b < n; ++b, dst += 2) { dst[0] = cos(angles[b]); dst[1] = sin(angles[b]); }
+    return dst;
+}
+static inline int32_t* stage_beam_tables(int32_t* dst, const int32_t* class_cost8, const int32_t* hit_tab, int half_bins) {   // [class costs] [hit_tab]
+    for (int k = 0; k < 8; ++k) *dst++ = class_cost8[k];
+    for (int k = 0; k < 2 * half_bins + 1; ++k) *dst++ = hit_tab[k];
     return dst;
 }
 static inline double* stage_rotations(double* dst, double th0, int n_rot, double rot_step) {   // [cos, sin, th, 0] of th0 + (q - n_rot) rot_step

@@ -909,6 +909,44 @@ class ParticleEngine:
                                                  _lib.RBPF_GAIN_DEVICE_OUT if device else 0, *map(out.ptr, outs)))
         return ViewGain(*outs)
 
+    # -- scan checks (include/rbpf_hip.h: rbpf_check_scans; thesis_amd/sensor.py) --------------------------------
+    def check_scans(self, poses, ranges, angles, particle=None, max_range: Optional[float] = None, min_range: float = 0.0,
+                    tol: Optional[float] = None, model=None, device: bool = False, return_classes: bool = False,
+                    return_votes: bool = False):
+        """How well measured scans agree with a particle's map: `ranges` [B] (one scan, checked at every pose) or [N, B] (scan n at
+        pose n) in metres, NaN, inf, 0 and negatives allowed, with beam directions `angles` [B], at `poses` [N, 3] (or [3]).
+        `particle`: an index, "best" (the first argmax of weights()) or None (pose n in particle n's map, N == P; e.g. poses()).
+        Every beam walks the ray of cast_scans up to its measured end plus `tol` metres (default two cells) and falls into one of
+        the classes sensor.SKIP .. sensor.CLEAR; `model` (default sensor.beam_model(cfg)) prices them.  A beam at or beyond
+        `max_range` (default cfg.weight_max_range) is a no-return beam, one below `min_range` is skipped.  Returns
+        sensor.ScanCheck(cost int64 [N], counts int32 [N, 8], classes uint8 [N, B] with return_classes, votes int32 [B, 8] with
+        return_votes, else None).  device=True: torch tensors on the engine's device, ready for work on torch's current stream."""
+        from . import sensor
+        p = self._particle(particle)
+        ps, a = _poses_angles(poses, angles)
+        rg = _f64(ranges)
+        if rg.ndim == 1:
+            rg = rg.reshape(1, -1)
+        N, B = ps.shape[0], a.shape[0]
+        if rg.ndim != 2 or rg.shape[1] != B or rg.shape[0] not in (1, N):
+            raise ValueError("ranges must be [B] or [N, B] for poses [N, 3] and angles [B]")
+        m = sensor.beam_model(self.cfg) if model is None else model
+        hit = np.ascontiguousarray(m.hit_tab, dtype=np.int32)
+        cc = np.ascontiguousarray(m.class_cost, dtype=np.int32)
+        if hit.shape != (2 * int(m.half_bins) + 1,) or cc.shape != (8,):
+            raise ValueError("model.hit_tab must have 2 * half_bins + 1 entries and model.class_cost 8")
+        cell = float(self.cfg.tile_len_m) / self.dim
+        mr = float(self.cfg.weight_max_range if max_range is None else max_range)
+        out = self._outputs(device)
+        outs = [out.empty((N,), "int64"), out.empty((N, 8), "int32"), out.empty((N, B), "uint8") if return_classes else None,
+                out.empty((B, 8), "int32") if return_votes else None]
+        with out:
+            self._check(self._lib.rbpf_check_scans(self._h, p, _dp(ps), N, _dp(rg), rg.shape[0], _dp(a), B, mr, float(min_range),
+                                                   2.0 * cell if tol is None else float(tol), _ip(hit), int(m.half_bins),
+                                                   int(m.bins_per_cell), _ip(cc), _lib.RBPF_SCANS_DEVICE_OUT if device else 0,
+                                                   *map(out.ptr, outs)))
+        return sensor.ScanCheck(*outs, scale=int(m.scale))
+
     # -- travel cost (include/rbpf_hip.h: rbpf_travel_cost; DESIGN.md 3.12; thesis_amd/plan.py) ---------------------------------
     def travel_cost(self, starts, goals=None, particle="best", box=None, radius_m: float = 0.0, clear_max: Optional[int] = None,
                     through_unknown: bool = False, device: bool = False):
