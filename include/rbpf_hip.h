@@ -591,6 +591,41 @@ int  rbpf_travel_stats(rbpf_handle* h, uint64_t* out3);
 int  rbpf_check_paths(rbpf_handle* h, int32_t particle, const double* xy, const int32_t* path_start, int32_t n_paths,
                       int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out, int32_t* steps);
 
+/* ---- rollout checks: the same K motion templates from every pose, placed on the GPU ------------------------------------------
+ * What a local planner asks every control cycle: a fan of arcs in the robot's frame, driven from each of n_poses poses, each rollout
+ * walked and tested as a path of rbpf_check_paths.  tmpl_xy is [tmpl_start[n_tmpl]][2] waypoints (lx, ly) in metres in the robot's
+ * frame, tmpl_start [n_tmpl + 1] their CSR offsets, strictly increasing from 0; every template has 1 .. 128 waypoints.  poses_n3
+ * is [n_poses][3] = x, y, theta.  particle >= 0: every pose is checked in that particle's map; particle == -1: n_poses must equal
+ * P and pose p is checked in particle p's map, the pairing of rbpf_check_scans.  (Every template in every map is
+ * rbpf_check_paths's, with particle == -1.)
+ * The placement.  The host turns each pose into x, y, c = cos(theta), s = sin(theta) with its libm: the device never sees an
+ * angle.  Waypoint j of template k at pose n is, every operation a float64 operation rounded on its own and in this order,
+ *   wx = x + (c * lx - s * ly)          wy = y + (s * lx + c * ly)
+ *   cell = (floor(wx * inv), floor(wy * inv)),  inv = dim / tile_len as for rbpf_check_paths.
+ * The walk.  With the waypoint cells so placed, wstep[0] = 0, wstep[j] = wstep[j - 1] + max(|dX|, |dY|) of the cells of waypoints
+ * j - 1 and j, and steps = wstep[m - 1] + 1 for a template of m waypoints.  The closed-form walk, ok(c), the blocked step, the
+ * exemption of the cell of step 0 and the four outputs are those of rbpf_check_paths, applied to these cells.
+ *   out[n_poses][n_tmpl][4]   int32, the four results of rbpf_check_paths.  Required.
+ *   steps[n_poses][n_tmpl]    int32, computed on the device.  May be NULL.  It lives where out lives: a host array complete on
+ *                             return, or with RBPF_PATHS_DEVICE_OUT a device pointer written in stream order.
+ * flags: RBPF_PATHS_DEVICE_OUT, RBPF_PATHS_THROUGH_UNKNOWN and RBPF_PATHS_START_EXEMPT as for rbpf_check_paths; RBPF_PATHS_OWN and
+ * any other bit are RBPF_EINVAL.
+ * What is checked instead of N * K * M waypoints: with rmax the largest |lx| + |ly| over all template waypoints (it bounds both
+ * rotated coordinates whatever the heading, |c|, |s| <= 1) and reach = ceil(rmax * inv) + 2 cells, a pose is RBPF_EINVAL (the
+ * message names it) if the square of half-side reach round its own cell (floor(x * inv), floor(y * inv)) leaves the tile lattice,
+ * and the call is RBPF_EINVAL if (m_max - 1) * 2 * reach >= 2^20, m_max the waypoints of the longest template.  So every placed
+ * waypoint's cell lies in the lattice and no rollout has more than 2^20 steps (DESIGN.md 3.24 has the argument for the two cells).
+ * Also RBPF_EINVAL: a NULL poses_n3, tmpl_xy, tmpl_start or out, a non-finite pose or template coordinate or a non-finite
+ * rmax * inv, an offset table that does not start at 0 or does not increase strictly, a template of more than 128 waypoints,
+ * n_poses < 1 or n_tmpl < 1, a bad particle, particle == -1 with n_poses != P, a bad inflate or clear_max (the bounds of
+ * rbpf_check_paths), and n_poses * n_tmpl >= 2^29.  A call between rbpf_scan_update_begin and _end is RBPF_ESTATE.  Everything is
+ * checked before anything is queued, and nothing is written on an error.  The call changes no engine state (maps, particles,
+ * random streams, counters, duplicate grouping).  It runs on the handle's stream in one launch over (pose, template); what is
+ * uploaded is 32 bytes a pose and 16 a template waypoint.  DESIGN.md 3.24 has the kernel. */
+int  rbpf_check_rollouts(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* tmpl_xy,
+                         const int32_t* tmpl_start, int32_t n_tmpl, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out,
+                         int32_t* steps);
+
 /* ---- scan checks: how well does the scan the robot took agree with a particle's map? ----------------------------------------
  * ranges is [n_scans][n_beams] in metres, n_scans 1 (one scan, checked at every pose) or n_poses (scan n at pose n); non-finite
  * and non-positive ranges are data and are classified below.  particle >= 0: every pose (x, y, theta) is checked in that particle's

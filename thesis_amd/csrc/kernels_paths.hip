@@ -1,67 +1,18 @@
 // kernels_paths.hip -- path checks: polylines of waypoint cells walked through a particle's map, every step's cell tested for
-// "known free and clear of the walls" (include/rbpf_hip.h, rbpf_check_paths; the specification is DESIGN 3.22).
+// "known free and clear of the walls" (include/rbpf_hip.h, rbpf_check_paths and rbpf_check_rollouts; the specification is
+// DESIGN 3.22, the rollouts' placement 3.24).
 //
-// One wave works on one (particle, path), four waves to a 256-lane workgroup, so that a rollout of 60 steps leaves no wave of
-// its workgroup idle.  Lane l takes the steps l, l + 64, ...  A step's cell follows in closed form from the step's number alone:
-// the segment is found by a binary search over the steps at which the path reaches its waypoints (staged in LDS for paths of up
-// to PATH_STAGE waypoints, read from memory beyond that), the cell on the segment by path_cell.  No lane waits for another.
-//   clearance   the row trick of travel_mask_kernel without its rasters: in the row at offset dx only the occupied cell nearest in
-//               y counts, found with count-trailing / leading-zeros on the row's occupancy bits; rows in the order 0, +-1, +-2, ...
-//               until 5 |dx| >= min(best, cap), which is exact because 5 max(|dx|, |dy|) + 2 min(|dx|, |dy|) >= 5 |dx|.
-//   reduction   two mins and a sum by wave shuffles; lane 0 stores the four results.  No atomics, no scratch rasters.
-#include "rbpf_device.h"
+// One wave works on one path, four waves to a 256-lane workgroup, so that a rollout of 60 steps leaves no wave of its workgroup
+// idle.  Lane l takes the steps l, l + 64, ...  A step's cell follows in closed form from the step's number alone: the segment is
+// found by a binary search over the steps at which the path reaches its waypoints (staged in LDS for paths of up to PATH_STAGE
+// waypoints, read from memory beyond that), the cell on the segment by path_cell.  No lane waits for another.  The walk, the
+// clearance and the reduction are rbpf_pathwalk.h's, for both kernels.
+//   check_paths_kernel      (particle, path): waypoint cells and their steps come from the host
+//   check_rollouts_kernel   (pose, template): the lanes place the template's waypoints at the pose, a wave-wide prefix sum of the
+//                           segment lengths gives their steps, both straight into LDS; lane 0 also stores `steps`
+#include "rbpf_pathwalk.h"
 
 namespace rbpf {
-
-static const int PATH_WAVES = 4;       // (particle, path) pairs of a workgroup
-static const int PATH_STAGE = 128;     // waypoints of a path staged in LDS
-
-// Occupancy bits of n <= 64 cells of lattice row u from column w0 on: bit k = cell (u, w0 + k) is occupied.  0 outside the lattice,
-// without a tile and outside a tile's written box (as occ_word32), but read a tile's word at a time.
-__device__ __forceinline__ uint64_t occ_run64(const DevView& v, const int32_t* __restrict__ tab, int u, int w0, int n) {
-    const int dim = v.dim, edge = v.L * dim;
-    if (u < 0 || u >= edge) return 0ull;
-    const int a = u / dim, i = u - a * dim, hi = min(w0 + n, edge);
-    uint64_t bits = 0ull;
-    for (int w = max(w0, 0); w < hi; ) {
-        const int b = w / dim, j = w - b * dim;
-        const int end = min(b * dim + min((j | 31) + 1, dim), hi);        // the end of this word of this tile, or of the run
-        const int tile = tab[a * v.L + b];
-        if (tile >= 0) {
-            uint32_t word = v.occ[(size_t)tile * dim * v.ow + (size_t)i * v.ow + (j >> 5)] >> (j & 31);
-            if (end - w < 32) word &= (1u << (end - w)) - 1u;
-            bits |= (uint64_t)word << (w - w0);
-        }
-        w = end;
-    }
-    return bits;
-}
-
-// min(d, cap) at lattice cell (u, w), d the chamfer distance to the nearest occupied cell of the map; 1 <= cap <= 320
-__device__ inline int path_clearance(const DevView& v, const int32_t* __restrict__ tab, int u, int w, int cap) {
-    int best = cap;
-    for (int ax = 0; 5 * ax < best; ++ax) {
-        const int r = (best - 1) / 5;                                      // a cell farther off in y cannot improve best; r <= 63
-        for (int side = 0; side < (ax ? 2 : 1); ++side) {
-            const int row = side ? u - ax : u + ax;
-            const uint64_t right = occ_run64(v, tab, row, w, r + 1), left = occ_run64(v, tab, row, w - r, r + 1);   // bit r of left is column w
-            const int dr = right ? __builtin_ctzll(right) : 64, dl = left ? r - 63 + __builtin_clzll(left) : 64;
-            const int g = min(dr, dl);
-            if (g < 64) best = min(best, 5 * max(ax, g) + 2 * min(ax, g));
-        }
-    }
-    return best;
-}
-
-// The cell of step t = 0 .. n of the segment from A to B (rbpf_pathbatch.h, path_segment_cell: the same expression).  t <= n < 2^20
-// and the minor axis' change is <= n, so 2 t a + n < 2^42 in 64 bits: no overflow whatever the lattice.
-__device__ __forceinline__ void path_cell(int xa, int ya, int xb, int yb, int t, int& x, int& y) {
-    const int dx = xb - xa, dy = yb - ya, ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, n = max(ax, ay);
-    const int minor = (int)((2ull * (uint64_t)t * (uint64_t)min(ax, ay) + (uint64_t)n) / (2ull * (uint64_t)n));
-    const int sx = dx < 0 ? -1 : 1, sy = dy < 0 ? -1 : 1;
-    if (ax >= ay) { x = xa + sx * t; y = ya + sy * minor; }
-    else { y = ya + sy * t; x = xa + sx * minor; }
-}
 
 __global__ __launch_bounds__(64 * PATH_WAVES) void check_paths_kernel(DevView v, PathArgs a) {
     __shared__ int32_t s_step[PATH_WAVES][PATH_STAGE];
@@ -83,54 +34,64 @@ __global__ __launch_bounds__(64 * PATH_WAVES) void check_paths_kernel(DevView v,
     __syncthreads();
     if (!live) return;
     const int32_t* __restrict__ tab = v.tile_tab + (size_t)v.slot[p] * v.L * v.L;
-    const int dim = v.dim;
     auto step_of = [&](int j) { return staged ? s_step[wv][j] : g_step[j]; };
     auto cell_of = [&](int j, int& x, int& y) { if (staged) { x = s_cell[wv][j][0]; y = s_cell[wv][j][1]; } else { x = g_cell[2 * j]; y = g_cell[2 * j + 1]; } };
-    auto value = [&](int x, int y) -> int {               // every walked cell and its side cells lie in the lattice: the host checked the waypoints
-        const int ta = x / dim, tb = y / dim, tile = tab[ta * v.L + tb];
-        return tile >= 0 ? (int)v.pool[(size_t)tile * dim * dim + (size_t)(x - ta * dim) * dim + (y - tb * dim)] : 0;
-    };
-    int x0, y0;
-    cell_of(0, x0, y0);
-    auto ok = [&](int x, int y) -> bool {                 // a side cell of a diagonal step
-        if (a.start_exempt && x == x0 && y == y0) return true;
-        if (!a.through_unknown && value(x, y) >= 0) return false;
-        return path_clearance(v, tab, x, y, a.inflate + 1) > a.inflate;
-    };
-    const int S = step_of(nw - 1) + 1;
-    int blocked = INT32_MAX, unknown = INT32_MAX, clear = a.clear_max, n_unknown = 0;
-    for (int s = lane; s < S; s += 64) {
-        int x = x0, y = y0, xp = x0, yp = y0;
-        if (s > 0) {
-            int lo = 1, hi = nw - 1;                      // the first waypoint j with step_of(j) >= s: the step lies on segment j - 1 -> j
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (step_of(mid) < s) lo = mid + 1; else hi = mid; }
-            int xa, ya, xb, yb;
-            cell_of(lo - 1, xa, ya); cell_of(lo, xb, yb);
-            const int t = s - step_of(lo - 1);            // 1 .. n
-            path_cell(xa, ya, xb, yb, t, x, y);
-            path_cell(xa, ya, xb, yb, t - 1, xp, yp);      // t - 1 = 0 is A, where the step before stands
+    path_walk(v, tab, PathRule{a.inflate, a.clear_max, a.through_unknown, a.start_exempt}, nw, lane, step_of, cell_of, a.out + 4 * (size_t)r);
+}
+
+// Waypoint j of template k at pose n (include/rbpf_hip.h, rbpf_check_rollouts: the placement), every operation a float64 operation
+// rounded on its own, as kernels_pairs.hip places a beam's end.  The host has seen to it that no pose can put a waypoint of these
+// templates outside the lattice (rbpf_rolloutbatch.h), so the conversion and the sum with `off` stay far inside 32 bits.
+__global__ __launch_bounds__(64 * PATH_WAVES) void check_rollouts_kernel(DevView v, RolloutArgs a) {
+    __shared__ int32_t s_step[PATH_WAVES][PATH_STAGE];
+    __shared__ int32_t s_cell[PATH_WAVES][PATH_STAGE][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long r = (long long)blockIdx.x * PATH_WAVES + wv;          // the result this wave writes
+    const bool live = r < a.pairs;
+    const int n = live ? (int)(r / a.n_tmpl) : 0, k = live ? (int)(r - (long long)n * a.n_tmpl) : 0;
+    const int first = live ? a.tmpl_start[k] : 0, nw = live ? a.tmpl_start[k + 1] - first : 0;      // nw <= PATH_STAGE: the host checked
+    if (live) {
+        const double2 ps = reinterpret_cast<const double2*>(a.pose4)[2 * (size_t)n], cs = reinterpret_cast<const double2*>(a.pose4)[2 * (size_t)n + 1];
+        const double2* __restrict__ xy = reinterpret_cast<const double2*>(a.tmpl_xy) + first;
+        int carry = 0, lx = 0, ly = 0;                                      // the step and the cell of the waypoint before this round's first
+        for (int base = 0; base < nw; base += 64) {                        // nw is the wave's: every lane runs every round
+            const int j = base + lane;
+            int cx = 0, cy = 0;
+            if (j < nw) {
+                const double2 q = xy[j];
+                const double wx = __dadd_rn(ps.x, __dsub_rn(__dmul_rn(cs.x, q.x), __dmul_rn(cs.y, q.y)));
+                const double wy = __dadd_rn(ps.y, __dadd_rn(__dmul_rn(cs.y, q.x), __dmul_rn(cs.x, q.y)));
+                cx = (int)__builtin_floor(__dmul_rn(wx, a.inv)) + a.off;
+                cy = (int)__builtin_floor(__dmul_rn(wy, a.inv)) + a.off;
+            }
+            int qx = __shfl_up(cx, 1, 64), qy = __shfl_up(cy, 1, 64);      // the waypoint before this lane's
+            if (lane == 0) { qx = base ? lx : cx; qy = base ? ly : cy; }
+            int sum = j < nw ? max(abs(cx - qx), abs(cy - qy)) : 0;        // the segment that ends at waypoint j; 0 for waypoint 0
+            for (int off = 1; off < 64; off <<= 1) {                       // inclusive prefix sum over the wave
+                const int t = __shfl_up(sum, off, 64);
+                if (lane >= off) sum += t;
+            }
+            sum += carry;
+            if (j < nw) { s_step[wv][j] = sum; s_cell[wv][j][0] = cx; s_cell[wv][j][1] = cy; }
+            carry = __shfl(sum, 63, 64); lx = __shfl(cx, 63, 64); ly = __shfl(cy, 63, 64);      // read only if a round follows: lane 63 held a waypoint
         }
-        const int val = value(x, y), d = path_clearance(v, tab, x, y, a.clear_max);
-        bool free_ = (a.start_exempt && x == x0 && y == y0) || ((a.through_unknown || val < 0) && d > a.inflate);
-        if (free_ && x != xp && y != yp) free_ = ok(x, yp) && ok(xp, y);
-        if (!free_) blocked = min(blocked, s);
-        if (val == 0) { unknown = min(unknown, s); ++n_unknown; }
-        clear = min(clear, d);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        blocked = min(blocked, __shfl_down(blocked, off, 64));
-        unknown = min(unknown, __shfl_down(unknown, off, 64));
-        clear = min(clear, __shfl_down(clear, off, 64));
-        n_unknown += __shfl_down(n_unknown, off, 64);
-    }
-    if (lane == 0) {
-        int32_t* o = a.out + 4 * (size_t)r;
-        o[0] = blocked == INT32_MAX ? -1 : blocked; o[1] = unknown == INT32_MAX ? -1 : unknown; o[2] = clear; o[3] = n_unknown;
-    }
+    __syncthreads();
+    if (!live) return;
+    const int p = a.particle >= 0 ? a.particle : n;
+    const int32_t* __restrict__ tab = v.tile_tab + (size_t)v.slot[p] * v.L * v.L;
+    auto step_of = [&](int j) { return s_step[wv][j]; };
+    auto cell_of = [&](int j, int& x, int& y) { x = s_cell[wv][j][0]; y = s_cell[wv][j][1]; };
+    path_walk(v, tab, PathRule{a.inflate, a.clear_max, a.through_unknown, a.start_exempt}, nw, lane, step_of, cell_of, a.out + 4 * (size_t)r);
+    if (lane == 0 && a.steps) a.steps[r] = s_step[wv][nw - 1] + 1;
 }
 
 void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s) {
     check_paths_kernel<<<(unsigned)((a.pairs + PATH_WAVES - 1) / PATH_WAVES), 64 * PATH_WAVES, 0, s>>>(v, a);
+}
+
+void launch_check_rollouts(const DevView& v, const RolloutArgs& a, hipStream_t s) {
+    check_rollouts_kernel<<<(unsigned)((a.pairs + PATH_WAVES - 1) / PATH_WAVES), 64 * PATH_WAVES, 0, s>>>(v, a);
 }
 
 }  // namespace rbpf

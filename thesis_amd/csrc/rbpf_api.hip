@@ -13,6 +13,7 @@
 #include "rbpf_host.h"
 #include "rbpf_scanbatch.h"
 #include "rbpf_pathbatch.h"
+#include "rbpf_rolloutbatch.h"
 
 using namespace rbpf;
 
@@ -2285,6 +2286,49 @@ int rbpf_check_paths(rbpf_handle* h, int32_t particle, const double* xy, const i
         if (const int rc = fetch(h, {{out, a.out, nres * 16}})) return rc;
     if (steps) memcpy(steps, pb.steps.data(), (size_t)n_paths * 4);        // behind everything that can fail: nothing is written on an error
     return RBPF_OK;
+}
+
+// ---- rollout checks (kernels_paths.hip; the host side is rbpf_rolloutbatch.h) -----------------------------------------------------
+int rbpf_check_rollouts(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* tmpl_xy,
+                        const int32_t* tmpl_start, int32_t n_tmpl, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out,
+                        int32_t* steps) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    ARG_TRY(h, check_rollout_args(poses_n3, tmpl_xy, tmpl_start, out, particle, v.P, n_poses, n_tmpl, inflate, clear_max, flags));
+    ARG_TRY(h, check_rollout_results(n_poses, n_tmpl));
+    const long long off = (long long)v.R * v.dim + v.dim / 2;             // mosaic X + off counts from the lattice's first cell
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as rbpf_check_paths forms it
+    RolloutBatch rb;
+    rollout_templates(rb, tmpl_xy, tmpl_start, n_tmpl, inv);
+    ARG_TRY(h, rb.error());
+    rollout_poses(rb, poses_n3, n_poses, inv, -off, (long long)v.L * v.dim - off);
+    ARG_TRY(h, rb.error());
+    MID_STEP_TRY(h, "a rollout check");
+    const bool dev_out = (flags & RBPF_PATHS_DEVICE_OUT) != 0;
+    const size_t N = (size_t)n_poses, nw = (size_t)tmpl_start[n_tmpl], nres = (size_t)rollout_results(n_poses, n_tmpl);
+    Carve c;                                                               // scratch: [poses] [template waypoints] [offsets] | host out, host steps
+    const size_t pose_at = c.pack(N * 32), xy_at = c.pack(nw * 16), start_at = c.pack(((size_t)n_tmpl + 1) * 4), in_b = c.close();
+    const size_t out_at = c.take(dev_out ? 0 : nres * 16), steps_at = c.take(dev_out || !steps ? 0 : nres * 4);
+    HIP_TRY(h, h->reserve(B_ROLLOUTS, c.total()));
+    const Block& d = h->buf[B_ROLLOUTS];
+    Staging& st = h->stage[S_ROLLOUTS];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* txy = stage_pose4(st.as<double>(pose_at), poses_n3, N);
+    memcpy(txy, tmpl_xy, nw * 16);
+    memcpy(st.p + start_at, tmpl_start, ((size_t)n_tmpl + 1) * 4);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    RolloutArgs a;
+    a.pose4 = d.as<const double>(pose_at); a.tmpl_xy = d.as<const double>(xy_at); a.tmpl_start = d.as<const int32_t>(start_at);
+    a.n_tmpl = n_tmpl; a.particle = particle; a.off = (int)off; a.inv = inv;
+    a.pairs = (long long)nres;
+    a.inflate = inflate; a.clear_max = clear_max;
+    a.through_unknown = (flags & RBPF_PATHS_THROUGH_UNKNOWN) != 0; a.start_exempt = (flags & RBPF_PATHS_START_EXEMPT) != 0;
+    a.out = dev_out ? out : d.as<int32_t>(out_at);
+    a.steps = !steps ? nullptr : dev_out ? steps : d.as<int32_t>(steps_at);
+    launch_check_rollouts(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return dev_out ? RBPF_OK : fetch(h, {{out, a.out, nres * 16}, {steps, a.steps, nres * 4}});
 }
 
 // ---- frontier regions (kernels_frontier.hip) ----------------------------------------------------------------------------------

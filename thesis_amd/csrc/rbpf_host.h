@@ -58,6 +58,7 @@ enum {
     B_SURFACE,                      // host volume, host drops, host outputs
     B_PATHS,                        // waypoint cells, waypoint steps, path offsets, host outputs
     B_SCANCHECK,                    // poses, beams, ranges, cost tables, host outputs
+    B_ROLLOUTS,                     // poses, template waypoints, template offsets, host outputs
     B_COUNT
 };
 
@@ -101,6 +102,7 @@ enum {
     S_BUILD, S_REFINE, S_PAIRS, S_PLACES, S_SURFACE,   // the upload of B_BUILD .. B_SURFACE: everything in front of the first '|' of its layout
     S_PATHS,                        // the upload of B_PATHS
     S_SCANCHECK,                    // the upload of B_SCANCHECK
+    S_ROLLOUTS,                     // the upload of B_ROLLOUTS
     S_COUNT
 };
 
@@ -157,7 +159,8 @@ struct rbpf_handle {
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming}, {{MEM_PINNED}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;

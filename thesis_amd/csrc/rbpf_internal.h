@@ -333,6 +333,23 @@ struct PathArgs {
     int32_t* out;                      // [pairs][4] first_blocked, first_unknown, min_clearance, n_unknown
 };
 
+// rollout checks (kernels_paths.hip): templates in the robot's frame placed at poses on the device and walked as
+// paths; one wave per (pose, template), result r = pose * n_tmpl + template
+struct RolloutArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
+    const double* tmpl_xy;             // [n_waypoints][2] metres in the robot's frame
+    const int32_t* tmpl_start;         // [n_tmpl + 1] first waypoint of each template; every template has 1 .. PATH_STAGE
+    int n_tmpl;
+    int particle;                      // >= 0: every pose in this particle's map; -1: pose n in particle n's
+    int off;                           // mosaic cell X + off counts from the lattice's first cell
+    double inv;                        // cells per metre (dim / tile_len)
+    long long pairs;                   // results: n_poses * n_tmpl
+    int inflate, clear_max;            // as PathArgs
+    int through_unknown, start_exempt;
+    int32_t* out;                      // [pairs][4] first_blocked, first_unknown, min_clearance, n_unknown
+    int32_t* steps;                    // [pairs] or null
+};
+
 // scan checks (kernels_scancheck.hip): measured scans against the maps; ray r = pose * B + beam as in CastArgs
 struct ScanCheckArgs {
     const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
@@ -508,6 +525,7 @@ void launch_locate_scan(const DevView& v, const LocateArgs& a, hipStream_t s);  
 void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s);  // the field kernel alone: particle, x0, y0, M, rows, W, field
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
 void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s);   // one wave per (particle, path)
+void launch_check_rollouts(const DevView& v, const RolloutArgs& a, hipStream_t s);   // one wave per (pose, template)
 void launch_check_scans(const DevView& v, const ScanCheckArgs& a, hipStream_t s);   // a.cost, a.counts and a.votes preset to 0
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran

@@ -87,7 +87,7 @@ static inline bool path_batch_build(PathBatch& b, const double* xy, const int32_
 // The cell of step t = 0 .. n of the segment from cell A to cell B, n = max(|XB - XA|, |YB - YA|) >= 1: the major coordinate moves
 // by one a step, the minor one by floor((2 t a + n) / (2 n)), a its whole change.  t <= n < 2^20 and a <= n (a path has at most
 // 2^20 steps), so 2 t a + n < 2^42: the product is formed in 64 bits and cannot overflow whatever the lattice.  The kernel's copy of
-// this function is path_cell in kernels_paths.hip.
+// this function is path_cell in rbpf_pathwalk.h.
 static inline void path_segment_cell(int32_t xa, int32_t ya, int32_t xb, int32_t yb, int32_t t, int32_t& x, int32_t& y) {
     const int32_t dx = xb - xa, dy = yb - ya, ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, n = ax > ay ? ax : ay;
     const int32_t minor = (int32_t)((2ull * (uint64_t)t * (uint64_t)(ax >= ay ? ay : ax) + (uint64_t)n) / (2ull * (uint64_t)n));

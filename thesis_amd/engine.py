@@ -1048,6 +1048,43 @@ class ParticleEngine:
         return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps.reshape(lead), float(self.cfg.tile_len_m) / self.dim,
                          inflate, cmax)
 
+    # -- rollout checks (include/rbpf_hip.h: rbpf_check_rollouts; thesis_amd/plan.py) ----------------------------
+    def check_rollouts(self, poses, templates, particle=None, radius_m: float = 0.0, clear_max: Optional[int] = None,
+                       through_unknown: bool = False, start_exempt: bool = False, device: bool = False):
+        """The same motion templates driven from every pose, placed on the GPU and checked as check_paths checks a path:
+        `templates` is [K, M, 2+] (metres in the robot's frame, e.g. plan.arc_templates; further columns are ignored) or a list of
+        K arrays [m_k, 2+] of 1 .. 128 waypoints, `poses` is [N, 3] (or [3]).  `particle`: an index, "best" (the first argmax of
+        weights()) or None (pose p in particle p's map, N == P; e.g. poses()).  radius_m, clear_max, through_unknown and
+        start_exempt are check_paths's.  The rollout of template k from pose n is plan.place_templates(poses, templates)[n, k]:
+        check_paths of that gives the same numbers, but builds and uploads N * K * M points to do so.  A pose from which a
+        template could leave the tile lattice is refused (RbpfError, which names it).  Returns plan.PathCheck with every field, steps too, [N, K].
+        device=True: torch tensors on the engine's device, steps among them, ready for work on torch's current stream."""
+        from .plan import PathCheck
+        p = self._particle(particle)
+        ps = _f64(poses)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or ps.shape[0] < 1:
+            raise ValueError("poses must be [N, 3] (or [3]), N >= 1")
+        tlist = [_f64(q) for q in (list(templates) if isinstance(templates, (list, tuple)) else list(_f64(templates)))]
+        if not tlist or any(q.ndim != 2 or q.shape[1] < 2 or q.shape[0] < 1 for q in tlist):
+            raise ValueError("templates must be [K, M, 2+] or a list of [m, 2+] arrays, K >= 1 and every m >= 1")
+        xy = np.ascontiguousarray(np.concatenate([q[:, :2] for q in tlist]))
+        start = np.zeros(len(tlist) + 1, dtype=np.int32)
+        np.cumsum([q.shape[0] for q in tlist], out=start[1:])
+        inv = self.dim / float(self.cfg.tile_len_m)
+        inflate = int(np.floor(float(radius_m) * inv * 5.0))
+        cmax = max(inflate + 1, inflate + 1 if clear_max is None else int(clear_max))
+        shape = (ps.shape[0], len(tlist))
+        out = self._outputs(device)
+        res, steps = out.empty(shape + (4,), "int32"), out.empty(shape, "int32")
+        flags = ((_lib.RBPF_PATHS_DEVICE_OUT if device else 0) | (_lib.RBPF_PATHS_THROUGH_UNKNOWN if through_unknown else 0)
+                 | (_lib.RBPF_PATHS_START_EXEMPT if start_exempt else 0))
+        with out:
+            self._check(self._lib.rbpf_check_rollouts(self._h, p, _dp(ps), ps.shape[0], _dp(xy), _ip(start), len(tlist), inflate, cmax, flags,
+                                                      out.ptr(res), out.ptr(steps)))
+        return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps, float(self.cfg.tile_len_m) / self.dim, inflate, cmax)
+
     # -- frontier regions (include/rbpf_hip.h: rbpf_frontier_regions; DESIGN.md 3.13; thesis_amd/explore.py) ----------------------
     def frontier_regions(self, particle="best", box=None, clearance_cells: int = 4, min_size: int = 1, max_regions: int = 64,
                          labels: bool = True, device: bool = False):

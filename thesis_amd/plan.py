@@ -1,6 +1,7 @@
 """Paths from a travel-cost field (ParticleEngine.travel_cost; include/rbpf_hip.h, rbpf_travel_cost).  Host side,
 NumPy only: the field is the work of the GPU, a path is a walk down it.  Below that, what goes with ParticleEngine.check_paths
-(rbpf_check_paths): the result type, the cells of a walk, any-angle shortcuts, velocity rollouts and their ranking."""
+(rbpf_check_paths): the result type, the cells of a walk, any-angle shortcuts, velocity rollouts and their ranking,
+and with ParticleEngine.check_rollouts (rbpf_check_rollouts): rollout templates and their placement at poses."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -71,7 +72,8 @@ class PathCheck(NamedTuple):
     first_unknown: np.ndarray        # int32 likewise: the least step on an unknown cell (lattice value 0), -1 if none
     min_clearance: np.ndarray        # int32 likewise: min over the path's cells of min(chamfer distance to an occupied cell, clear_max)
     n_unknown: np.ndarray            # int32 likewise: steps on unknown cells
-    steps: np.ndarray                # int32 [K] (with own=True [P, K]): steps of each path, 1 + the sum of its segments' max(|dX|, |dY|)
+    steps: np.ndarray                # int32 [K] (with own=True [P, K]): steps of each path, 1 + the sum of its segments' max(|dX|, |dY|);
+                                     # from check_rollouts [N, K] as every field, and a tensor as they are with device=True
     cell: float                      # metres per cell
     inflate: int                     # a cell carries the robot if its clearance exceeds inflate
     clear_max: int
@@ -199,6 +201,32 @@ def rollouts(poses, speeds, turn_rates, horizon_s: float, dt: float):
     q = ps.reshape(-1, 3)
     ang = q[:, None, None, 2] + half[None]
     out = np.stack([q[:, None, None, 0] + chord[None] * np.cos(ang), q[:, None, None, 1] + chord[None] * np.sin(ang)], axis=-1)
+    return out[0] if ps.ndim == 1 else out
+
+
+def arc_templates(speeds, turn_rates, horizon_s: float, dt: float):
+    """[K, M, 2]: the constant-(v, w) arcs of `rollouts` in the robot's frame, i.e. rollouts(np.zeros(3), ...): what
+    ParticleEngine.check_rollouts places at every pose on the GPU."""
+    return rollouts(np.zeros(3), speeds, turn_rates, horizon_s, dt)
+
+
+def place_templates(poses, templates):
+    """[N, K, M, 2] (one pose [3]: [K, M, 2]): `templates` [K, M, 2+] placed at `poses` [N, 3] by the rule of rbpf_check_rollouts
+    (include/rbpf_hip.h), which this states in NumPy: c = math.cos(theta) and s = math.sin(theta) once per pose, then
+    wx = x + (c * lx - s * ly) and wy = y + (s * lx + c * ly), every operation a float64 operation rounded on its own, in this
+    order.  The cells floor(w * inv) of the result are therefore the cells the device walks, bit for bit, and
+    check_paths(place_templates(...)) is what check_rollouts(...) returns.  rollouts(poses, ...) adds the heading inside the
+    cosine instead of rotating a finished template, so it agrees with placed arc_templates only to rounding."""
+    import math
+    ps = np.asarray(poses, dtype=np.float64)
+    tm = np.asarray(templates, dtype=np.float64)
+    if ps.shape[-1] != 3 or ps.ndim not in (1, 2) or tm.ndim != 3 or tm.shape[2] < 2:
+        raise ValueError("poses must be [3] or [N, 3] and templates [K, M, 2+]")
+    q = ps.reshape(-1, 3)
+    c = np.array([math.cos(th) for th in q[:, 2]], dtype=np.float64)[:, None, None]
+    s = np.array([math.sin(th) for th in q[:, 2]], dtype=np.float64)[:, None, None]
+    lx, ly = tm[None, :, :, 0], tm[None, :, :, 1]
+    out = np.stack([q[:, 0, None, None] + (c * lx - s * ly), q[:, 1, None, None] + (s * lx + c * ly)], axis=-1)
     return out[0] if ps.ndim == 1 else out
 
 
