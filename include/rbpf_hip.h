@@ -626,6 +626,52 @@ int  rbpf_check_rollouts(rbpf_handle* h, int32_t particle, const double* poses_n
                          const int32_t* tmpl_start, int32_t n_tmpl, int32_t inflate, int32_t clear_max, uint32_t flags, int32_t* out,
                          int32_t* steps);
 
+/* ---- footprint checks: the rollouts of rbpf_check_rollouts, driven by a robot that is no disc ----------------------------------
+ * A disc's clearance does not depend on heading; a 0.8 m x 0.5 m base's does.  Every step of every rollout tests, besides the
+ * inscribed-radius test at its centre, the cells an oriented footprint covers there, and a turn on the spot sweeps the corners.
+ * Templates, poses, placement and walk are those of rbpf_check_rollouts, unchanged: tmpl_xy / tmpl_start in CSR with 1 .. 128
+ * waypoints a template, c = cos(theta) and s = sin(theta) from the host's libm, wx = x + (c * lx - s * ly) in float64 with every
+ * operation rounded on its own, cell = floor(w * inv), wstep from max(|dX|, |dY|), the closed-form walk, steps = wstep[m - 1] + 1,
+ * the reach check on the poses and the bound of 2^20 steps.
+ * The footprint table.  n_bins = H heading bins, 1 <= H <= 256; bin b stands for the heading 2 pi b / H.  fp_start [H + 1] is a
+ * CSR offset table from 0, every bin holds 1 .. 256 spans, fp_span is [fp_start[H]][3] = (dx, y0, y1) with |dx| <= 127,
+ * -127 <= y0 <= y1 <= 127 and y1 - y0 <= 63.  A robot whose centre stands on the cell (X, Y) in bin b covers the cells
+ * (X + dx, Y + y), y0 <= y <= y1, of bin b's spans: spans run along y, the contiguous axis of a tile row.  A covered cell outside
+ * the tile lattice has v = 0, as the clearance margin of rbpf_check_paths.
+ * Heading bins: the device never sees an angle.  The entry point forms, on the host in float64 and in this order,
+ *   pb[n] = floor(theta_n * (H / (2 pi)) + 0.5) mod H      (pi = M_PI; reduced into 0 .. H - 1 for negative headings)
+ * and |theta * H / (2 pi)| >= 2^31 is RBPF_EINVAL.  tmpl_bin [tmpl_start[n_tmpl]] holds, per template waypoint, a bin in [0, H):
+ * the same formula applied to the waypoint's heading in the robot's frame.  Waypoint j tests bin (pb[n] + tmpl_bin[j]) mod H.  The
+ * two roundings come to one bin at the most; the table is the caller's to pad for it (plan.footprint_table does).
+ * Which bins a step tests.  A step s that stands on waypoints (s = wstep[j]) tests the bin of every such j: repeated waypoints
+ * test every heading they carry, and a turn on the spot is one step with m bins.  A step strictly between the waypoints j - 1 and
+ * j, t = 1 .. n - 1 of a segment of n steps, tests the bin of j - 1 if 2 t < n, else that of j.
+ * The rules.  v, occ, blocked(c) with and without RBPF_PATHS_THROUGH_UNKNOWN, d(c), the chamfer units and
+ * 0 <= inflate < clear_max <= 320 are those of rbpf_travel_cost.  exempt(c) holds when exempt >= 0 and c lies within Chebyshev
+ * distance `exempt` of the cell of step 0 (the robot is where it is); exempt = -1 turns it off, exempt > 255 is RBPF_EINVAL.
+ *   blocked step  = its centre cell c0 is not exempt and (blocked(c0) or d(c0) <= inflate), or some covered cell c of a tested
+ *                   bin is not exempt and blocked(c).  The centre test is the inscribed-radius test; there is no corner-cut
+ *                   rule, the footprint has area.
+ *   out[..][4]    = {first_blocked: the least blocked step, -1 if none;  first_unknown: the least step at which the centre or a
+ *                   tested covered cell has v == 0, -1 if none;  min_clearance: min over the centre cells of min(d, clear_max),
+ *                   exactly that of rbpf_check_rollouts;  n_unknown: the number of such steps, each counted once; the exemption
+ *                   does not touch it}                                                                              (int32)
+ * All four are order-free reductions of exact integers.  steps is as for rbpf_check_rollouts: may be NULL, lives where out lives.
+ * particle >= 0: every pose in that map, out [n_poses][n_tmpl][4].  particle == -1 with n_poses == P: pose p in particle p's map;
+ * with n_poses == 1: that pose in EVERY particle's map; out [P][n_tmpl][4] both times.  A world path across the posterior is a
+ * template at the pose (0, 0, 0), where the placement is the identity bit for bit.
+ * flags: RBPF_PATHS_DEVICE_OUT and RBPF_PATHS_THROUGH_UNKNOWN; any other bit is RBPF_EINVAL.
+ * RBPF_EINVAL, raised before anything is queued, with nothing written and a message that names the offender: everything
+ * rbpf_check_rollouts rejects, a NULL tmpl_bin, fp_span or fp_start, a bin outside [0, H), a bad n_bins, an offset table that
+ * does not start at 0, has an empty bin or more than 256 spans in a bin, a span outside its bounds, a bad exempt, particle == -1
+ * with n_poses neither 1 nor P, and 2^29 or more results.  A call between rbpf_scan_update_begin and _end is RBPF_ESTATE.  The
+ * call changes no engine state.  It runs on the handle's stream in one launch; what is uploaded is 36 bytes a pose, 20 a template
+ * waypoint and 4 a span.  DESIGN.md 3.25 has the kernel. */
+int  rbpf_check_footprints(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* tmpl_xy,
+                           const int32_t* tmpl_bin, const int32_t* tmpl_start, int32_t n_tmpl, const int32_t* fp_span,
+                           const int32_t* fp_start, int32_t n_bins, int32_t inflate, int32_t clear_max, int32_t exempt, uint32_t flags,
+                           int32_t* out, int32_t* steps);
+
 /* ---- scan checks: how well does the scan the robot took agree with a particle's map? ----------------------------------------
  * ranges is [n_scans][n_beams] in metres, n_scans 1 (one scan, checked at every pose) or n_poses (scan n at pose n); non-finite
  * and non-positive ranges are data and are classified below.  particle >= 0: every pose (x, y, theta) is checked in that particle's

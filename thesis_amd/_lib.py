@@ -148,6 +148,8 @@ PROTOTYPES = {
     "rbpf_travel_stats": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "rbpf_check_paths": (C.c_int, [_H, C.c_int32, _D, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, _I]),
     "rbpf_check_rollouts": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rbpf_check_footprints": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _I, _I, C.c_int32, _I, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_check_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_double, C.c_double, _I, C.c_int32,
                                    C.c_int32, _I, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_frontier_regions": (C.c_int, [_H, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),

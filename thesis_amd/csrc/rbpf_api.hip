@@ -14,6 +14,7 @@
 #include "rbpf_scanbatch.h"
 #include "rbpf_pathbatch.h"
 #include "rbpf_rolloutbatch.h"
+#include "rbpf_footbatch.h"
 
 using namespace rbpf;
 
@@ -2327,6 +2328,68 @@ int rbpf_check_rollouts(rbpf_handle* h, int32_t particle, const double* poses_n3
     a.out = dev_out ? out : d.as<int32_t>(out_at);
     a.steps = !steps ? nullptr : dev_out ? steps : d.as<int32_t>(steps_at);
     launch_check_rollouts(v, a, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return dev_out ? RBPF_OK : fetch(h, {{out, a.out, nres * 16}, {steps, a.steps, nres * 4}});
+}
+
+// ---- footprint checks (kernels_footprint.hip; the host side is rbpf_footbatch.h) ------------------------------------------------
+int rbpf_check_footprints(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const double* tmpl_xy,
+                          const int32_t* tmpl_bin, const int32_t* tmpl_start, int32_t n_tmpl, const int32_t* fp_span, const int32_t* fp_start,
+                          int32_t n_bins, int32_t inflate, int32_t clear_max, int32_t exempt, uint32_t flags, int32_t* out, int32_t* steps) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    ARG_TRY(h, check_footprint_args(poses_n3, tmpl_xy, tmpl_bin, tmpl_start, fp_span, fp_start, out, particle, v.P, n_poses, n_tmpl, n_bins,
+                                    inflate, clear_max, exempt, flags));
+    ARG_TRY(h, check_footprint_results(particle, v.P, n_poses, n_tmpl));
+    const long long off = (long long)v.R * v.dim + v.dim / 2;             // mosaic X + off counts from the lattice's first cell
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as rbpf_check_paths forms it
+    RolloutBatch rb;
+    rollout_templates(rb, tmpl_xy, tmpl_start, n_tmpl, inv);
+    ARG_TRY(h, rb.error());
+    rollout_poses(rb, poses_n3, n_poses, inv, -off, (long long)v.L * v.dim - off);
+    ARG_TRY(h, rb.error());
+    FootTable ft;
+    footprint_table(ft, fp_span, fp_start, n_bins);
+    ARG_TRY(h, ft.error());
+    footprint_template_bins(ft, tmpl_bin, tmpl_start, n_tmpl, n_bins);
+    ARG_TRY(h, ft.error());
+    std::vector<int32_t> pb((size_t)n_poses);
+    footprint_pose_bins(ft, pb.data(), poses_n3, n_poses, n_bins);
+    ARG_TRY(h, ft.error());
+    MID_STEP_TRY(h, "a footprint check");
+    const bool dev_out = (flags & RBPF_PATHS_DEVICE_OUT) != 0;
+    const size_t N = (size_t)n_poses, nw = (size_t)tmpl_start[n_tmpl], ns = (size_t)fp_start[n_bins];
+    const size_t nres = (size_t)footprint_results(particle, v.P, n_poses, n_tmpl);
+    Carve c;            // scratch: [poses] [template waypoints] [pose bins] [template bins] [offsets] [span offsets] [spans] | host out, host steps
+    const size_t pose_at = c.pack(N * 32), xy_at = c.pack(nw * 16), pbin_at = c.pack(N * 4), tbin_at = c.pack(nw * 4);
+    const size_t start_at = c.pack(((size_t)n_tmpl + 1) * 4), fstart_at = c.pack(((size_t)n_bins + 1) * 4), span_at = c.pack(ns * 4), in_b = c.close();
+    const size_t out_at = c.take(dev_out ? 0 : nres * 16), steps_at = c.take(dev_out || !steps ? 0 : nres * 4);
+    HIP_TRY(h, h->reserve(B_FOOTPRINTS, c.total()));
+    const Block& d = h->buf[B_FOOTPRINTS];
+    Staging& st = h->stage[S_FOOTPRINTS];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    double* txy = stage_pose4(st.as<double>(pose_at), poses_n3, N);
+    memcpy(txy, tmpl_xy, nw * 16);
+    memcpy(st.p + pbin_at, pb.data(), N * 4);
+    memcpy(st.p + tbin_at, tmpl_bin, nw * 4);
+    memcpy(st.p + start_at, tmpl_start, ((size_t)n_tmpl + 1) * 4);
+    memcpy(st.p + fstart_at, fp_start, ((size_t)n_bins + 1) * 4);
+    int32_t* spans = st.as<int32_t>(span_at);
+    for (size_t k = 0; k < ns; ++k) spans[k] = footprint_pack(fp_span + 3 * k);
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    FootArgs a;
+    a.pose4 = d.as<const double>(pose_at); a.pose_bin = d.as<const int32_t>(pbin_at);
+    a.tmpl_xy = d.as<const double>(xy_at); a.tmpl_bin = d.as<const int32_t>(tbin_at); a.tmpl_start = d.as<const int32_t>(start_at);
+    a.fp_start = d.as<const int32_t>(fstart_at); a.fp_span = d.as<const int32_t>(span_at);
+    a.n_tmpl = n_tmpl; a.n_bins = n_bins; a.particle = particle; a.one_pose = particle < 0 && n_poses == 1;
+    a.off = (int)off; a.inv = inv;
+    a.pairs = (long long)nres;
+    a.inflate = inflate; a.clear_max = clear_max;
+    a.through_unknown = (flags & RBPF_PATHS_THROUGH_UNKNOWN) != 0; a.exempt = exempt;
+    a.out = dev_out ? out : d.as<int32_t>(out_at);
+    a.steps = !steps ? nullptr : dev_out ? steps : d.as<int32_t>(steps_at);
+    launch_check_footprints(v, a, h->stream);
     HIP_TRY(h, hipGetLastError());
     return dev_out ? RBPF_OK : fetch(h, {{out, a.out, nres * 16}, {steps, a.steps, nres * 4}});
 }

@@ -350,6 +350,29 @@ struct RolloutArgs {
     int32_t* steps;                    // [pairs] or null
 };
 
+// footprint checks (kernels_footprint.hip): the rollouts of RolloutArgs, every step also testing the cells an
+// oriented footprint covers; one wave per (row, template), result r = row * n_tmpl + template, row a pose or a particle
+struct FootArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
+    const int32_t* pose_bin;           // [n_poses] heading bin of the pose
+    const double* tmpl_xy;             // [n_waypoints][2] metres in the robot's frame
+    const int32_t* tmpl_bin;           // [n_waypoints] heading bin of the waypoint in the robot's frame
+    const int32_t* tmpl_start;         // [n_tmpl + 1] first waypoint of each template; every template has 1 .. PATH_STAGE
+    const int32_t* fp_start;           // [n_bins + 1] first span of each bin
+    const int32_t* fp_span;            // [n_spans] dx, y0, y1 as signed bytes 0, 1, 2 (rbpf_footbatch.h, footprint_pack)
+    int n_tmpl, n_bins;
+    int particle;                      // >= 0: every pose in this particle's map; -1: row n is particle n
+    int one_pose;                      // 1: every row takes pose 0 (one pose in every particle's map); 0: row n takes pose n
+    int off;                           // mosaic cell X + off counts from the lattice's first cell
+    double inv;                        // cells per metre (dim / tile_len)
+    long long pairs;                   // results: rows * n_tmpl
+    int inflate, clear_max;            // as PathArgs, for the centre cell
+    int through_unknown;               // 1: blocked = occupied, else v >= 0
+    int exempt;                        // >= 0: cells within this Chebyshev distance of the cell of step 0 block nothing; -1: none
+    int32_t* out;                      // [pairs][4] first_blocked, first_unknown, min_clearance, n_unknown
+    int32_t* steps;                    // [pairs] or null
+};
+
 // scan checks (kernels_scancheck.hip): measured scans against the maps; ray r = pose * B + beam as in CastArgs
 struct ScanCheckArgs {
     const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta)
@@ -526,6 +549,7 @@ void launch_locate_field(const DevView& v, const LocateArgs& a, hipStream_t s); 
 void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs& a, hipStream_t s);   // a.packed preset to 0
 void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s);   // one wave per (particle, path)
 void launch_check_rollouts(const DevView& v, const RolloutArgs& a, hipStream_t s);   // one wave per (pose, template)
+void launch_check_footprints(const DevView& v, const FootArgs& a, hipStream_t s);    // one wave per (pose or particle, template)
 void launch_check_scans(const DevView& v, const ScanCheckArgs& a, hipStream_t s);   // a.cost, a.counts and a.votes preset to 0
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran

@@ -1085,6 +1085,58 @@ class ParticleEngine:
                                                       out.ptr(res), out.ptr(steps)))
         return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps, float(self.cfg.tile_len_m) / self.dim, inflate, cmax)
 
+    # -- footprint checks (include/rbpf_hip.h: rbpf_check_footprints; thesis_amd/plan.py) -------------------------
+    def check_footprints(self, poses, templates, headings, footprint, particle=None, radius_m: float = 0.0, clear_max: Optional[int] = None,
+                         through_unknown: bool = False, exempt_cells: Optional[int] = None, device: bool = False):
+        """check_rollouts for a robot that is no disc: every step of every rollout tests, besides its centre cell (not known free,
+        or clearance <= inflate = floor(radius_m * cells per metre * 5): radius_m is the INSCRIBED radius here), the cells an
+        oriented footprint covers there.  `poses` [N, 3] (or [3]) and `templates` ([K, M, 2+] or a list of [m_k, 2+], 1 .. 128
+        waypoints) are check_rollouts's; `headings` is [K, M] or a list of K arrays [m_k]: the robot's heading at each waypoint
+        in the robot's frame (plan.arc_headings goes with plan.arc_templates, plan.path_headings with a world path placed at the
+        pose (0, 0, 0)); `footprint` is a plan.Footprint (plan.footprint_table of the robot's outline, cut for this engine's cell
+        size).  A step on a waypoint tests the heading bin of every waypoint it stands on - a turn on the spot sweeps the corners -
+        and a step between two waypoints that of the nearer one.  `particle`: an index or "best": every pose in that map, [N, K];
+        None: pose p in particle p's map (N == P), or one pose in EVERY particle's map (N == 1), [P, K].  exempt_cells: cells
+        within this Chebyshev distance of a rollout's first cell block nothing (the robot is where it is); None: no exemption.
+        Returns plan.PathCheck as check_rollouts does, min_clearance and steps equal to its; first_unknown and n_unknown count the
+        steps at which the centre or a covered cell is unknown.  device=True: torch tensors on the engine's device."""
+        from .plan import PathCheck, heading_bins
+        p = self._particle(particle)
+        ps = _f64(poses)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or ps.shape[0] < 1:
+            raise ValueError("poses must be [N, 3] (or [3]), N >= 1")
+        tlist = [_f64(q) for q in (list(templates) if isinstance(templates, (list, tuple)) else list(_f64(templates)))]
+        if not tlist or any(q.ndim != 2 or q.shape[1] < 2 or q.shape[0] < 1 for q in tlist):
+            raise ValueError("templates must be [K, M, 2+] or a list of [m, 2+] arrays, K >= 1 and every m >= 1")
+        hlist = [_f64(q).reshape(-1) for q in (list(headings) if isinstance(headings, (list, tuple)) else list(_f64(headings)))]
+        if len(hlist) != len(tlist) or any(a.shape[0] != q.shape[0] for a, q in zip(hlist, tlist)):
+            raise ValueError("headings must hold one heading for every waypoint of every template")
+        H = int(footprint.H)
+        spans = np.ascontiguousarray(footprint.spans, dtype=np.int32).reshape(-1, 3)
+        offsets = np.ascontiguousarray(footprint.offsets, dtype=np.int32).reshape(-1)
+        if offsets.shape[0] != H + 1 or (H >= 1 and int(offsets[-1]) != spans.shape[0]):
+            raise ValueError("footprint.offsets must be [H + 1] and end at the number of spans")
+        if abs(float(footprint.cell) - float(self.cfg.tile_len_m) / self.dim) > 1e-9 * float(footprint.cell):
+            raise ValueError("the footprint table was cut for another cell size")
+        xy = np.ascontiguousarray(np.concatenate([q[:, :2] for q in tlist]))
+        tbin = np.ascontiguousarray(heading_bins(np.concatenate(hlist), H))
+        start = np.zeros(len(tlist) + 1, dtype=np.int32)
+        np.cumsum([q.shape[0] for q in tlist], out=start[1:])
+        inv = self.dim / float(self.cfg.tile_len_m)
+        inflate = int(np.floor(float(radius_m) * inv * 5.0))
+        cmax = max(inflate + 1, inflate + 1 if clear_max is None else int(clear_max))
+        shape = (ps.shape[0] if p >= 0 else self.P, len(tlist))
+        out = self._outputs(device)
+        res, steps = out.empty(shape + (4,), "int32"), out.empty(shape, "int32")
+        flags = (_lib.RBPF_PATHS_DEVICE_OUT if device else 0) | (_lib.RBPF_PATHS_THROUGH_UNKNOWN if through_unknown else 0)
+        with out:
+            self._check(self._lib.rbpf_check_footprints(self._h, p, _dp(ps), ps.shape[0], _dp(xy), _ip(tbin), _ip(start), len(tlist), _ip(spans),
+                                                        _ip(offsets), H, inflate, cmax, -1 if exempt_cells is None else int(exempt_cells), flags,
+                                                        out.ptr(res), out.ptr(steps)))
+        return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps, float(self.cfg.tile_len_m) / self.dim, inflate, cmax)
+
     # -- frontier regions (include/rbpf_hip.h: rbpf_frontier_regions; DESIGN.md 3.13; thesis_amd/explore.py) ----------------------
     def frontier_regions(self, particle="best", box=None, clearance_cells: int = 4, min_size: int = 1, max_regions: int = 64,
                          labels: bool = True, device: bool = False):

@@ -1,7 +1,8 @@
 """Paths from a travel-cost field (ParticleEngine.travel_cost; include/rbpf_hip.h, rbpf_travel_cost).  Host side,
 NumPy only: the field is the work of the GPU, a path is a walk down it.  Below that, what goes with ParticleEngine.check_paths
 (rbpf_check_paths): the result type, the cells of a walk, any-angle shortcuts, velocity rollouts and their ranking,
-and with ParticleEngine.check_rollouts (rbpf_check_rollouts): rollout templates and their placement at poses."""
+and with ParticleEngine.check_rollouts (rbpf_check_rollouts): rollout templates and their placement at poses, and
+with ParticleEngine.check_footprints (rbpf_check_footprints): heading bins and the span table of a footprint."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -253,3 +254,126 @@ def rank_rollouts(check: PathCheck, end_cost=None, weights=None, min_p_clear: fl
         score = mean(np.where(c < 0, np.inf, c)) - float(clearance_weight) * clearance
     keep = np.flatnonzero(p >= float(min_p_clear))
     return keep[np.argsort(score[keep], kind="stable")]
+
+
+# ---- footprint checks (ParticleEngine.check_footprints; include/rbpf_hip.h, rbpf_check_footprints) --------------
+def heading_bins(angles, H: int):
+    """int32, the shape of `angles`: the heading bin of each angle (radians) among H, by the rule of rbpf_check_footprints:
+    floor(angle * (H / (2 pi)) + 0.5) mod H in float64 and in this order, reduced into 0 .. H - 1 for negative angles.  An angle
+    whose |angle * H / (2 pi)| reaches 2^31 (or is not finite) is a ValueError."""
+    H = int(H)
+    if not 1 <= H <= 256:
+        raise ValueError("1 <= H <= 256 is required")
+    q = np.asarray(angles, dtype=np.float64) * np.float64(H / (2.0 * np.pi))
+    if not np.all(np.abs(q) < 2147483648.0):
+        raise ValueError("|angle * H / (2 pi)| < 2^31 is required")
+    return (np.floor(q + 0.5).astype(np.int64) % H).astype(np.int32)
+
+
+def arc_headings(turn_rates, horizon_s: float, dt: float):
+    """[K, M]: the heading w t of the constant-(v, w) arcs of arc_templates at their M points t = 0, dt, ..., in the robot's frame:
+    the `headings` that go with arc_templates(speeds, turn_rates, horizon_s, dt) into ParticleEngine.check_footprints."""
+    w = np.asarray(turn_rates, dtype=np.float64).reshape(-1)
+    if not dt > 0 or not horizon_s >= 0:
+        raise ValueError("dt > 0 and horizon_s >= 0 are required")
+    t = np.arange(int(round(float(horizon_s) / float(dt))) + 1, dtype=np.float64) * float(dt)
+    return w[:, None] * t[None, :]
+
+
+def path_headings(path):
+    """[m]: a heading for every waypoint of the world path `path` [m, 2+] from its segments: waypoint j looks along the segment
+    to waypoint j + 1, the last waypoint repeats the one before it, and a segment of no length keeps the heading before it (0
+    where there is none).  With the path as a template at the pose (0, 0, 0), check_footprints drives it in every map."""
+    p = np.asarray(path, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or len(p) < 1:
+        raise ValueError("path must be [m, 2+] with m >= 1")
+    out, last = np.zeros(len(p)), 0.0
+    for j in range(len(p) - 1):
+        dx, dy = p[j + 1, 0] - p[j, 0], p[j + 1, 1] - p[j, 1]
+        if dx != 0.0 or dy != 0.0:
+            last = float(np.arctan2(dy, dx))
+        out[j] = last
+    out[-1] = last
+    return out
+
+
+class Footprint(NamedTuple):
+    spans: np.ndarray                # int32 [S, 3]: (dx, y0, y1), the cells (dx, y0 .. y1) relative to the cell the robot's centre stands on
+    offsets: np.ndarray              # int32 [H + 1]: bin b holds spans[offsets[b]:offsets[b + 1]]
+    H: int                           # heading bins; bin b stands for the heading 2 pi b / H
+    cell: float                      # metres per cell the table was cut for
+
+
+FOOTPRINT_MAX_OFFSET, FOOTPRINT_MAX_SPANS, FOOTPRINT_MAX_WIDTH = 127, 256, 64
+
+
+def _polygon_distance(poly, px, py):
+    """Distance of the points (px, py) to the polygon `poly` [n, 2]: 0 inside (even-odd rule), else to the nearest edge."""
+    a, b = poly, np.roll(poly, -1, axis=0)
+    best = np.full(px.shape, np.inf)
+    inside = np.zeros(px.shape, dtype=bool)
+    for (ax, ay), (bx, by) in zip(a, b):
+        ex, ey = bx - ax, by - ay
+        ll = ex * ex + ey * ey
+        t = np.clip(((px - ax) * ex + (py - ay) * ey) / ll, 0.0, 1.0) if ll > 0 else np.zeros(px.shape)
+        best = np.minimum(best, np.hypot(px - (ax + t * ex), py - (ay + t * ey)))
+        if ay != by:
+            cross = ((ay > py) != (by > py)) & (px < ax + (py - ay) * (ex / (by - ay)))
+            inside ^= cross
+    return np.where(inside, 0.0, best)
+
+
+def footprint_table(polygon_xy, cell: float, heading_bins: int = 64, pad_m: Optional[float] = None):
+    """The Footprint of the robot outline `polygon_xy` [n >= 3, 2] (metres, robot frame, x ahead; the origin is the point whose
+    poses are checked) for maps of `cell` metres a cell and H = `heading_bins` bins.  Bin b holds the cells whose centre, with the
+    robot's centre on the centre of cell (0, 0), lies inside or within `pad_m` of the polygon turned by 2 pi b / H; a row of cells
+    is cut into spans of at most 64.
+    The default pad_m is cell * sqrt(2) + r_max * 2 pi / H, r_max the farthest vertex.  The robot stands anywhere in its cell, up to
+    half a cell diagonal from the centre; a point it covers lies anywhere in the cell that is reported for it, up to half a diagonal
+    from that centre; and the heading tested is that of the bin pb + tmpl_bin, two roundings of half a bin each, which move a point
+    at radius r by at most r * 2 pi / H.  So the table covers the true footprint wherever the robot stands in its cell and whichever
+    way the two roundings fall.  pad_m = 0 is the bare outline on the cell centres.
+    A table that passes +-127 cells, or 256 spans in a bin, is a ValueError that names the limit."""
+    poly = np.asarray(polygon_xy, dtype=np.float64)
+    H, cell = int(heading_bins), float(cell)
+    if poly.ndim != 2 or poly.shape[1] != 2 or len(poly) < 3 or not np.all(np.isfinite(poly)) or not cell > 0 or not 1 <= H <= 256:
+        raise ValueError("polygon_xy must be [n >= 3, 2] and finite, cell > 0 and 1 <= heading_bins <= 256")
+    r_max = float(np.hypot(poly[:, 0], poly[:, 1]).max())
+    pad = cell * np.sqrt(2.0) + r_max * 2.0 * np.pi / H if pad_m is None else float(pad_m)
+    if not pad >= 0:
+        raise ValueError("pad_m >= 0 is required")
+    m = int(np.ceil((r_max + pad) / cell)) + 1
+    if (r_max + pad) / cell > 4 * FOOTPRINT_MAX_OFFSET:                      # before a raster of that size is built
+        raise ValueError(f"the footprint reaches {(r_max + pad) / cell:.0f} cells: a span's offsets are limited to +-{FOOTPRINT_MAX_OFFSET} cells")
+    k = np.arange(-m, m + 1)
+    gx, gy = np.meshgrid(k * cell, k * cell, indexing="ij")
+    spans, offsets = [], [0]
+    for b in range(H):
+        th = 2.0 * np.pi * b / H
+        c, s = np.cos(th), np.sin(th)
+        turned = np.stack([c * poly[:, 0] - s * poly[:, 1], s * poly[:, 0] + c * poly[:, 1]], axis=1)
+        mask = _polygon_distance(turned, gx, gy) <= pad
+        mask[m, m] = True                                                   # the cell the robot stands on, however small the outline
+        for i in np.flatnonzero(mask.any(axis=1)):
+            ys = np.flatnonzero(mask[i])
+            for run in np.split(ys, np.flatnonzero(np.diff(ys) > 1) + 1):
+                for y0 in range(int(run[0]), int(run[-1]) + 1, FOOTPRINT_MAX_WIDTH):
+                    y1 = min(y0 + FOOTPRINT_MAX_WIDTH - 1, int(run[-1]))
+                    spans.append((int(i) - m, y0 - m, y1 - m))
+        offsets.append(len(spans))
+    sp = np.asarray(spans, dtype=np.int32).reshape(-1, 3)
+    if np.abs(sp).max() > FOOTPRINT_MAX_OFFSET:
+        raise ValueError(f"the footprint reaches {int(np.abs(sp).max())} cells: a span's offsets are limited to +-{FOOTPRINT_MAX_OFFSET} cells")
+    for b in range(H):
+        if offsets[b + 1] - offsets[b] > FOOTPRINT_MAX_SPANS:
+            raise ValueError(f"bin {b} needs {offsets[b + 1] - offsets[b]} spans: a bin is limited to {FOOTPRINT_MAX_SPANS} spans")
+    return Footprint(sp, np.asarray(offsets, dtype=np.int32), H, cell)
+
+
+def footprint_cells(fp: Footprint, b: int):
+    """int64 [n, 2]: the cells (dx, dy) bin `b` of the table covers, relative to the cell the robot's centre stands on."""
+    if not 0 <= int(b) < fp.H:
+        raise ValueError("bin out of range")
+    rows = fp.spans[int(fp.offsets[b]):int(fp.offsets[b + 1])]
+    out = [np.stack([np.full(int(y1) - int(y0) + 1, int(dx), np.int64), np.arange(int(y0), int(y1) + 1, dtype=np.int64)], axis=1) for dx, y0, y1 in rows]
+    return np.concatenate(out) if out else np.zeros((0, 2), np.int64)
