@@ -20,6 +20,8 @@ def load():
     lib.orc_map_n_tiles.argtypes = [C.c_void_p]; lib.orc_map_dim.argtypes = [C.c_void_p]
     lib.orc_map_cells_visited.restype = C.c_ulonglong; lib.orc_map_cells_visited.argtypes = [C.c_void_p]
     lib.orc_map_tile.restype = _D; lib.orc_map_tile.argtypes = [C.c_void_p, C.c_int, _D]
+    lib.orc_map_tile_visited.restype = C.POINTER(C.c_uint8); lib.orc_map_tile_visited.argtypes = [C.c_void_p, C.c_int]
+    lib.orc_map_clear_visited.argtypes = [C.c_void_p]
     lib.orc_map_set_tile.argtypes = [C.c_void_p, C.c_long, C.c_long, _D]
     lib.orc_map_update.argtypes = [C.c_void_p, _LD, C.c_int, _D, _D, C.c_int]
     lib.orc_sample_weight.argtypes = [C.c_void_p, _LD, C.c_int, C.c_int, _D, _D, C.c_int, _D, _LD]
@@ -66,6 +68,24 @@ class CMap:
             ptr = self.lib.orc_map_tile(self.h, k, dp(c))
             out[(float(c[0]), float(c[1]))] = np.ctypeslib.as_array(ptr, shape=(self.dim, self.dim)).copy()
         return out
+
+    def visited(self):
+        """{centre: uint8 [dim, dim]}, 1 where an update wrote the cell since the last clear_visited(); beside tiles()."""
+        out = {}
+        for k in range(self.lib.orc_map_n_tiles(self.h)):
+            c = np.empty(2)
+            self.lib.orc_map_tile(self.h, k, dp(c))
+            ptr = self.lib.orc_map_tile_visited(self.h, k)
+            out[(float(c[0]), float(c[1]))] = np.ctypeslib.as_array(ptr, shape=(self.dim, self.dim)).copy()
+        return out
+
+    def clear_visited(self):
+        self.lib.orc_map_clear_visited(self.h)
+
+    @property
+    def cells_visited(self):
+        """Sum over rays of Bresenham points, as OracleHybridMap.cells_visited."""
+        return int(self.lib.orc_map_cells_visited(self.h))
 
     def sample_weight(self, guesses, sx, sy, prs, ld=False):
         g = np.ascontiguousarray(guesses, dtype=np.longdouble)

@@ -26,6 +26,7 @@
 typedef struct {
     long cx, cy;          /* tile centre (integer metres on the 40 m lattice) */
     double* map;          /* dim*dim, map[x*dim + y] */
+    uint8_t* visited;     /* dim*dim, 1 where an update wrote the cell (test bookkeeping, not the reference's) */
 } tile_t;
 
 typedef struct {
@@ -46,12 +47,13 @@ omap_t* orc_map_new(double cs, long len_m) {
     m->n_tiles = 1;                                               /* hybridmap.py:70 */
     m->tiles[0].cx = 0; m->tiles[0].cy = 0;
     m->tiles[0].map = (double*)calloc((size_t)m->dim * m->dim, sizeof(double));
+    m->tiles[0].visited = (uint8_t*)calloc((size_t)m->dim * m->dim, 1);
     return m;
 }
 
 void orc_map_free(omap_t* m) {
     if (!m) return;
-    for (int i = 0; i < m->n_tiles; ++i) free(m->tiles[i].map);
+    for (int i = 0; i < m->n_tiles; ++i) { free(m->tiles[i].map); free(m->tiles[i].visited); }
     free(m);
 }
 
@@ -62,6 +64,8 @@ omap_t* orc_map_copy(const omap_t* s) {                           /* hybridmap.p
     for (int i = 0; i < s->n_tiles; ++i) {
         m->tiles[i].map = (double*)malloc(n * sizeof(double));
         memcpy(m->tiles[i].map, s->tiles[i].map, n * sizeof(double));
+        m->tiles[i].visited = (uint8_t*)malloc(n);
+        memcpy(m->tiles[i].visited, s->tiles[i].visited, n);
     }
     return m;
 }
@@ -73,12 +77,17 @@ double* orc_map_tile(omap_t* m, int k, double* centre2) {
     centre2[0] = (double)m->tiles[k].cx; centre2[1] = (double)m->tiles[k].cy;
     return m->tiles[k].map;
 }
+uint8_t* orc_map_tile_visited(omap_t* m, int k) { return m->tiles[k].visited; }
+void orc_map_clear_visited(omap_t* m) {
+    for (int i = 0; i < m->n_tiles; ++i) memset(m->tiles[i].visited, 0, (size_t)m->dim * m->dim);
+}
 void orc_map_set_tile(omap_t* m, long cx, long cy, const double* cells) {
     int k;
     for (k = 0; k < m->n_tiles; ++k) if (m->tiles[k].cx == cx && m->tiles[k].cy == cy) break;
     if (k == m->n_tiles) {
         m->tiles[k].cx = cx; m->tiles[k].cy = cy;
         m->tiles[k].map = (double*)calloc((size_t)m->dim * m->dim, sizeof(double));
+        m->tiles[k].visited = (uint8_t*)calloc((size_t)m->dim * m->dim, 1);
         m->n_tiles++;
     }
     memcpy(m->tiles[k].map, cells, (size_t)m->dim * m->dim * sizeof(double));
@@ -182,16 +191,22 @@ void orc_map_update(omap_t* m, const long double* pose, int ld, const double* sx
                     t = &m->tiles[m->n_tiles++];
                     t->cx = ncx; t->cy = ncy;
                     t->map = (double*)calloc((size_t)m->dim * m->dim, sizeof(double));
+                    t->visited = (uint8_t*)calloc((size_t)m->dim * m->dim, 1);
                 }
             }
             double rx = posx - t->cx, ry = posy - t->cy;          /* hybridmap.py:136 */
-            double* cell = &t->map[(size_t)set_index(m, rx) * m->dim + set_index(m, ry)];
+            const size_t at = (size_t)set_index(m, rx) * m->dim + set_index(m, ry);
+            double* cell = &t->map[at];
+            t->visited[at] = 1;
             if (end_is_occ && px[j] == ex && py[j] == ey) {       /* hybridmap.py:137 */
                 clamp_occ(m, cell);
                 if (j > 0) {                                      /* hybridmap.py:139-142 */
                     double nx = px[j - 1] * cs, ny = py[j - 1] * cs;
-                    if (in_map_d(m, t, nx, ny))
-                        clamp_near(m, &t->map[(size_t)set_index(m, nx - t->cx) * m->dim + set_index(m, ny - t->cy)]);
+                    if (in_map_d(m, t, nx, ny)) {
+                        const size_t nat = (size_t)set_index(m, nx - t->cx) * m->dim + set_index(m, ny - t->cy);
+                        clamp_near(m, &t->map[nat]);
+                        t->visited[nat] = 1;
+                    }
                 }
             } else {
                 clamp_emp(m, cell);                               /* hybridmap.py:144 */

@@ -132,6 +132,7 @@ class OracleTile:
         self.cell_size = cell_size
         self.dim = round(map_len_m / cell_size)  # gridmap.py:31
         self.map = np.zeros((self.dim, self.dim))  # [x][y], gridmap.py:32
+        self.visited = np.zeros((self.dim, self.dim), dtype=bool)  # cells an update wrote (test bookkeeping, not the reference's)
         r = map_len_m / 2  # hybridmap.py:31-36
         self.min_x, self.min_y = cx - r, cy - r
         self.max_x, self.max_y = cx + r, cy + r
@@ -174,6 +175,7 @@ class OracleTile:
     def copy(self):
         t = OracleTile(self.cx, self.cy, self.size, self.cell_size)
         t.map = self.map.copy()
+        t.visited = self.visited.copy()
         return t
 
 
@@ -240,16 +242,24 @@ class OracleHybridMap:
                 if end_is_occ and ind[0] == end[0] and ind[1] == end[1]:  # :137
                     a, b = set_index(rx, cs, m.dim), set_index(ry, cs, m.dim)
                     m.map[a][b] = min(m.map[a][b] + self.occ, self.max_occ)
+                    m.visited[a][b] = True
                     if j > 0:  # :139-142
                         nx, ny = pts[j - 1][0] * cs, pts[j - 1][1] * cs
                         if m.is_in_map(nx, ny):
                             a = set_index(nx - m.cx, cs, m.dim)
                             b = set_index(ny - m.cy, cs, m.dim)
                             m.map[a][b] = min(m.map[a][b] + self.near, self.max_occ)
+                            m.visited[a][b] = True
                 else:  # :144
                     a, b = set_index(rx, cs, m.dim), set_index(ry, cs, m.dim)
                     m.map[a][b] = max(m.map[a][b] + self.emp, self.min_emp)
+                    m.visited[a][b] = True
         return self
+
+    def clear_visited(self) -> None:
+        """Forget which cells the updates so far wrote (OracleTile.visited); the cells stay."""
+        for t in self.tiles:
+            t.visited[:] = False
 
     # -- matcher inputs (a6) -------------------------------------------------
     def scan_match_inputs(self, sx, sy, guess, pose_range):

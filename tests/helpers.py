@@ -45,8 +45,12 @@ MAP_COUNTERS = ("map_windows", "window_fallbacks", "fallback_geometry", "fallbac
 def run_map_case(engine, poses, scans, angles, cell_size=0.05, pool_tiles=32, c_oracle_above=400):
     """Scans into an engine (whose map kernel the caller has forced) and into one oracle map per DISTINCT pose; every tile
     byte and the read-out (get_odds_at) at the flagged cells - the last scan's end points and the points one cell short of
-    them - compared.  Scans of more than c_oracle_above beams go through the oracle's C restatement.  Prints and returns the
-    engine's counters."""
+    them - compared.  Scans of more than c_oracle_above beams go through the oracle's C restatement.  Then what the update
+    maintains beside the cells, for every particle and every held tile (tests/mapupdate_hidden.py): the written boxes against
+    the box of the cells the oracle visited, the occupancy words against the oracle's cells; and the two counters the bench's
+    roofline is computed from: cells_written = the distinct storage cells a scan visited, summed over scans and particles,
+    ray_cells_visited = the oracle's Bresenham points summed the same way.  Prints and returns the engine's counters."""
+    from tests import mapupdate_hidden as hidden
     Q = 0.1
     poses = np.asarray(poses, dtype=np.float64)
     P = len(poses)
@@ -60,14 +64,25 @@ def run_map_case(engine, poses, scans, angles, cell_size=0.05, pool_tiles=32, c_
         maps = {k: c_oracle.CMap(lib, cell_size) for k in keys}
     else:
         maps = {k: orc.OracleHybridMap(cell_size) for k in keys}
+    union = {k: {} for k in keys}                                            # per pose {centre: cells visited by any scan}
+    written = {k: 0 for k in keys}                                           # per pose: distinct cells visited, summed over scans
+    c0 = e.counters()
     for r, a in zip(scans, angs):
         e.set_scan(r, a)
         e.map_update(poses)
         sx, sy = orc.scan_xy(r, a)
         for pose, hm in maps.items():
+            hm.clear_visited()
             hm.update(pose, sx, sy)
+            for cxy, plane in hidden.visited_planes(hm).items():
+                written[pose] += int(plane.sum())
+                union[pose][cxy] = union[pose].get(cxy, False) | plane
     c = e.counters()
     print({k: c[k] for k in MAP_COUNTERS})
+    want_written = sum(written[k] for k in keys)
+    want_visited = sum(maps[k].cells_visited for k in keys)
+    print({"cells_written": c["cells_written"] - c0["cells_written"], "oracle": want_written,
+           "ray_cells_visited": c["ray_cells_visited"] - c0["ray_cells_visited"], "oracle_visited": want_visited})
     for k, hm in list(maps.items()):
         if not isinstance(hm, orc.OracleHybridMap):                      # the C map's tiles in the Python oracle's clothes
             py = orc.OracleHybridMap(cell_size)
@@ -101,5 +116,10 @@ def run_map_case(engine, poses, scans, angles, cell_size=0.05, pool_tiles=32, c_
         want = [hm.get_odds_at(float(x), float(y)) for x, y in pts]
         assert np.array_equal(none, np.array([w is None for w in want]))
         np.testing.assert_allclose(vals[~none], np.array([w for w in want if w is not None], dtype=np.float64), rtol=0, atol=1e-9)
+    got_hidden = hidden.read_hidden_of(e, range(P))
+    for p in range(P):
+        hidden.check_map_hidden(e, p, maps[keys[p]], visited=union[keys[p]], what="run_map_case", hidden=got_hidden[p])
+    assert c["cells_written"] - c0["cells_written"] == want_written, (c["cells_written"] - c0["cells_written"], want_written)
+    assert c["ray_cells_visited"] - c0["ray_cells_visited"] == want_visited, (c["ray_cells_visited"] - c0["ray_cells_visited"], want_visited)
     e.close()
     return c

@@ -5,6 +5,7 @@ import pytest
 
 from oracle import rbpf_oracle as orc
 from tests.helpers import oracle_map_from_dump, golden_dump_as_dict
+from tests.mapupdate_hidden import check_map_hidden
 
 pytestmark = pytest.mark.gpu
 
@@ -139,6 +140,8 @@ def test_map_update_random_particles_vs_oracle(eng_mod, map_kernel):
     assert c["ray_cells_visited"] > 0 and c["cells_written"] > 0
     if map_kernel == "window":
         assert c["window_fallbacks"] == 0
+    for p in range(P):                                      # written boxes and occupancy words (tests/mapupdate_hidden.py)
+        check_map_hidden(e, p, maps[p], what="random particles")
     e.close()
 
 
@@ -190,6 +193,8 @@ def test_map_update_first_kernel_hard_cases(eng_mod, monkeypatch, scene, kernel)
         assert c["window_fallbacks"] == 0, "fallback reasons %x" % c["fallback_reasons"]
     if scene == "negative_side":        # only the third scan (independent random ranges: cells with dozens of events) may fall back
         assert c["window_fallbacks"] <= P, "fallback reasons %x" % c["fallback_reasons"]
+    for p in range(P):                                      # written boxes and occupancy words (tests/mapupdate_hidden.py)
+        check_map_hidden(e, p, maps[p], what=scene)
     e.close()
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import rbpf_oracle as orc
+from tests.mapupdate_hidden import check_map_hidden, compare_hidden, read_hidden_of
 from tests.test_gpu_parity import assert_tiles_equal, oracle_dump
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,9 @@ def same_maps(e, ref, what):
         assert [c for c, _ in got] == [c for c, _ in want], (what, p)
         for (c, a), (_, b) in zip(got, want):
             assert np.array_equal(a, b), (what, p, c, int(np.count_nonzero(a != b)))
+    got, want = read_hidden_of(e, range(e.P)), read_hidden_of(ref, range(e.P))     # written boxes and occupancy words
+    for p in range(e.P):
+        compare_hidden(got[p], want[p], e.dim, f"{what}: particle {p}")
 
 
 def without_offspring(idx, P):
@@ -189,6 +193,8 @@ def test_nan_branch_step_leaves_nobody_out_and_equals_the_oracle(eng_mod, monkey
         np.testing.assert_allclose(e.weights(), [float(rb.weight[-1]) for rb in robots], rtol=1e-9)
     for p, rb in enumerate(robots):
         assert_tiles_equal(e, p, oracle_dump(rb.map), e.dim)
+    for p, rb in enumerate(robots):                          # the update was launched late, by the resample: boxes and occupancy words
+        check_map_hidden(e, p, rb.map, what="nan branch")
     e.close()
 
 
