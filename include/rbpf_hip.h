@@ -672,6 +672,55 @@ int  rbpf_check_footprints(rbpf_handle* h, int32_t particle, const double* poses
                            const int32_t* fp_start, int32_t n_bins, int32_t inflate, int32_t clear_max, int32_t exempt, uint32_t flags,
                            int32_t* out, int32_t* steps);
 
+/* ---- local map: what is around the robot, in the robot's frame, fused over the particles ------------------------------------------
+ * The raster a local planner, a controller or an obstacle layer asks for every cycle: a window of n x n cells of cell_out metres
+ * with the robot at a fixed place in it.  Particles whose trajectories have drifted apart hold the same room at different world
+ * positions, so the world-frame sum of rbpf_render_map doubles every wall; relative to each particle's own pose they agree.
+ * poses_n3 is [n_poses][3] = x, y, theta.  particle >= 0: every pose is read in that particle's map; particle == -1: n_poses must
+ * equal P and pose p is read in particle p's map, the pairing of rbpf_check_rollouts and rbpf_check_scans.
+ * The host turns each pose into x, y, c = cos(theta), s = sin(theta) with its libm: the device never sees an angle.
+ * Sample tables.  With S = samples (1 .. 8) and n >= 1, the host forms in float64, for q = 0 .. n S - 1,
+ *   gx[q] = ((q / S) + ((q % S) + 0.5) / S - 0.5 n) * cell_out + fx        (q / S and q % S in integers)
+ *   gy[q] the same with fy,
+ * every operation rounded on its own, in the written order; offset2 = (fx, fy), NULL for (0, 0), is the window's centre in the
+ * robot's frame in metres (a look-ahead window).  The device does not recompute the tables.
+ * Placement of the sample (qa, qb) at a pose, exactly that of rbpf_check_rollouts, every operation a float64 operation rounded on
+ * its own and in this order:
+ *   wx = x + (c * gx[qa] - s * gy[qb])          wy = y + (s * gx[qa] + c * gy[qb])
+ *   X = floor(wx * inv), Y = floor(wy * inv),   inv = dim / tile_len.
+ * v(X, Y) is the lattice value of rbpf_render_map in the pose's map: 0 without a tile, outside a tile's written box and outside
+ * the lattice.  A pose near or beyond the lattice's edge is legal; its window reads 0 there.
+ * Per pose and output cell (i, j), i along the robot's x (forward), j along its y (left), row-major [n][n]:
+ *   m = max of v over the samples qa in [i S, i S + S), qb in [j S, j S + S)
+ * the rule of rbpf_place_map: a wall that crosses any part of the cell keeps it, a cell is free only if all of it is.  S = 1 is
+ * nearest neighbour.
+ *   crops[n_poses][n][n]   int8, m.  May be NULL.
+ *   fused[n][n][4]         int64, may be NULL (not both).  With thr = occupied_threshold / quantum (strict, as everywhere) and k
+ *                          over the poses: {occ_w = sum wq_k [m_k > thr], free_w = sum wq_k [m_k < 0], unknown_w = sum wq_k [m_k == 0],
+ *                          sum_wv = sum wq_k m_k}.
+ * wq is host uint32 [n_poses]; NULL: every weight is 1.  A pose with wq = 0 adds nothing to fused and still gets its crop.  All
+ * four sums are sums of exact integers: order-free, bit-identical from call to call whatever the grouping.
+ * Without RBPF_LOCAL_DEVICE_OUT fused and crops are host arrays, complete on return; with it they are device pointers written in
+ * stream order, with no host wait.
+ * The window in LDS.  With h = 0.5 n cell_out, reach = ceil(hypot(|fx| + h, |fy| + h) * inv) + 2 cells: every sample of a pose
+ * lies in the square of half-side reach round the pose's own cell (floor(x inv), floor(y inv)), since |c a - s b| <=
+ * hypot(a, b) hypot(c, s) and the two spare cells cover the rounding of c, s and of the six operations (DESIGN.md 3.26 has the
+ * argument).  One workgroup stages that square as bytes; 2 reach + 1 > RBPF_LOCAL_MAX_SIDE is RBPF_EINVAL, and the message gives
+ * the side and the limit.
+ * RBPF_EINVAL, checked before anything is queued, with nothing written: a NULL poses_n3, fused and crops both NULL; a non-finite
+ * pose, cell_out or offset; cell_out <= 0, n < 1, samples outside 1 .. 8, n_poses < 1; a bad particle, particle == -1 with
+ * n_poses != P; |x inv| or |y inv| >= 2^30 (the message names the pose); sum wq equal to 0 or above 2^31 - 1;
+ * n_poses * n * n >= 2^31; an unknown flag; the window limit.  A window whose single crop and sums exceed the scratch cap of
+ * 256 MiB is RBPF_ENOMEM.  A call between rbpf_scan_update_begin and _end is RBPF_ESTATE.
+ * The call changes no engine state (maps, particles, random streams, counters, duplicate grouping) and runs on the handle's
+ * stream.  Poses are worked on in batches whose scratch (crops not asked for, group sums) stays under 256 MiB; the environment
+ * variable RBPF_LOCAL_BATCH=<k>, read per call, caps a batch at k poses (tests).  Batches add into fused; the sums are integers,
+ * so the result does not depend on k.  DESIGN.md 3.26 has the kernels. */
+#define RBPF_LOCAL_DEVICE_OUT 1u   /* fused / crops are device pointers, written in stream order, no host wait */
+#define RBPF_LOCAL_MAX_SIDE   384  /* largest LDS window side in map cells */
+int  rbpf_local_map(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const uint32_t* wq, int32_t n,
+                    double cell_out, int32_t samples, const double* offset2, uint32_t flags, int64_t* fused, int8_t* crops);
+
 /* ---- scan checks: how well does the scan the robot took agree with a particle's map? ----------------------------------------
  * ranges is [n_scans][n_beams] in metres, n_scans 1 (one scan, checked at every pose) or n_poses (scan n at pose n); non-finite
  * and non-positive ranges are data and are classified below.  particle >= 0: every pose (x, y, theta) is checked in that particle's

@@ -21,6 +21,7 @@ RBPF_ALIGN_DEVICE_OUT = 1
 RBPF_GAIN_DEVICE_OUT = 1
 RBPF_TRAVEL_DEVICE_OUT, RBPF_TRAVEL_THROUGH_UNKNOWN = 1, 2
 RBPF_PATHS_DEVICE_OUT, RBPF_PATHS_THROUGH_UNKNOWN, RBPF_PATHS_START_EXEMPT, RBPF_PATHS_OWN = 1, 2, 4, 8
+RBPF_LOCAL_DEVICE_OUT, RBPF_LOCAL_MAX_SIDE = 1, 384
 RBPF_SCANS_DEVICE_OUT = 1
 RBPF_FRONTIER_DEVICE_OUT = 1
 RBPF_SCORE_DEVICE_IN, RBPF_SCORE_DEVICE_OUT, RBPF_SCORE_FIELDS = 1, 2, 13
@@ -150,6 +151,8 @@ PROTOTYPES = {
     "rbpf_check_rollouts": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rbpf_check_footprints": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _I, _I, C.c_int32, _I, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rbpf_local_map": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.c_double, C.c_int32, _D, C.c_uint32, C.c_void_p,
+                                 C.c_void_p]),
     "rbpf_check_scans": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, C.c_int32, _D, C.c_int32, C.c_double, C.c_double, C.c_double, _I, C.c_int32,
                                    C.c_int32, _I, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbpf_frontier_regions": (C.c_int, [_H, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),

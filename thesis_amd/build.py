@@ -17,8 +17,8 @@ SOURCES = ["rbpf_api.hip", "kernels_weight.hip", "kernels_mapupdate.hip", "kerne
            "kernels_propose.hip", "kernels_resample.hip", "kernels_match.hip", "kernels_inputs.hip",
            "kernels_render.hip", "kernels_load.hip", "kernels_cast.hip", "kernels_locate.hip", "kernels_place.hip", "kernels_align.hip", "kernels_gain.hip",
            "kernels_travel.hip", "kernels_frontier.hip", "kernels_score.hip", "kernels_track.hip", "kernels_build.hip", "kernels_refine.hip", "kernels_pairs.hip",
-           "kernels_places.hip", "kernels_surface.hip", "kernels_modes.hip", "kernels_paths.hip", "kernels_scancheck.hip", "kernels_footprint.hip"]
-HEADERS = ["rbpf_internal.h", "rbpf_host.h", "rbpf_scanbatch.h", "rbpf_pathbatch.h", "rbpf_rolloutbatch.h", "rbpf_footbatch.h", "rbpf_pathwalk.h", "rbpf_math.h", "rbpf_device.h", "rbpf_mapupdate.h", "rbpf_tilewrite.h", "rbpf_raywalk.h", "rbpf_blockrelax.h", "rbpf_refine_search.h", "rbpf_estrow.h", os.path.join("..", "..", "include", "rbpf_hip.h")]
+           "kernels_places.hip", "kernels_surface.hip", "kernels_modes.hip", "kernels_paths.hip", "kernels_scancheck.hip", "kernels_footprint.hip", "kernels_local.hip"]
+HEADERS = ["rbpf_internal.h", "rbpf_host.h", "rbpf_scanbatch.h", "rbpf_pathbatch.h", "rbpf_rolloutbatch.h", "rbpf_footbatch.h", "rbpf_localbatch.h", "rbpf_pathwalk.h", "rbpf_math.h", "rbpf_device.h", "rbpf_mapupdate.h", "rbpf_tilewrite.h", "rbpf_raywalk.h", "rbpf_blockrelax.h", "rbpf_refine_search.h", "rbpf_estrow.h", os.path.join("..", "..", "include", "rbpf_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

@@ -15,6 +15,7 @@
 #include "rbpf_pathbatch.h"
 #include "rbpf_rolloutbatch.h"
 #include "rbpf_footbatch.h"
+#include "rbpf_localbatch.h"
 
 using namespace rbpf;
 
@@ -2392,6 +2393,73 @@ int rbpf_check_footprints(rbpf_handle* h, int32_t particle, const double* poses_
     launch_check_footprints(v, a, h->stream);
     HIP_TRY(h, hipGetLastError());
     return dev_out ? RBPF_OK : fetch(h, {{out, a.out, nres * 16}, {steps, a.steps, nres * 4}});
+}
+
+// ---- local map (kernels_local.hip; the host side is rbpf_localbatch.h) ----------------------------------------------------------
+static_assert(RBPF_LOCAL_DEVICE_OUT == LOCAL_DEVICE_OUT && RBPF_LOCAL_MAX_SIDE == LOCAL_MAX_SIDE && LOCAL_GROUP == LOCAL_GROUP_POSES &&
+              LOCAL_LDS == LDS_LIMIT, "rbpf_localbatch.h repeats constants of rbpf_hip.h, rbpf_internal.h and rbpf_host.h");
+int rbpf_local_map(rbpf_handle* h, int32_t particle, const double* poses_n3, int32_t n_poses, const uint32_t* wq, int32_t n,
+                   double cell_out, int32_t samples, const double* offset2, uint32_t flags, int64_t* fused, int8_t* crops) {
+    if (!h) return RBPF_EINVAL;
+    ON_DEVICE(h);
+    const DevView& v = h->v;
+    ARG_TRY(h, check_local_args(poses_n3, fused, crops, particle, v.P, n_poses, n, cell_out, samples, offset2, flags));
+    const double inv = (double)v.dim / v.tile_len;                         // cells per metre, as rbpf_check_rollouts forms it
+    LocalPlan lp;
+    local_plan(lp, n, cell_out, samples, offset2, inv);
+    ARG_TRY(h, lp.error());
+    local_poses(lp, poses_n3, n_poses, inv);
+    ARG_TRY(h, lp.error());
+    local_weights(lp, wq, n_poses);
+    ARG_TRY(h, lp.error());
+    MID_STEP_TRY(h, "a local map");
+    const bool dev_out = (flags & RBPF_LOCAL_DEVICE_OUT) != 0, fuse = fused != nullptr, scratch_crops = !crops;
+    const size_t N = (size_t)n_poses, ncell = (size_t)n * n, nq = (size_t)lp.nq;
+    if (local_batch_bytes(1, n, scratch_crops, fuse) > LOCAL_SCRATCH)
+        return fail(h, RBPF_ENOMEM, "one pose's window needs more than 256 MiB of scratch: use a smaller n");
+    long long cap = 0;
+    if (const char* e = getenv("RBPF_LOCAL_BATCH")) cap = std::max(1LL, atoll(e));
+    const long long batch = local_batch(n_poses, n, scratch_crops, fuse, cap);
+    Carve c;                                                               // scratch: [poses] [gx] [gy] [wq] | host fused, host crops, batch crops, group sums
+    const size_t pose_at = c.pack(N * 32), gx_at = c.pack(nq * 8), gy_at = c.pack(nq * 8), wq_at = c.pack(N * 4), in_b = c.close();
+    const size_t fused_at = c.take(dev_out || !fuse ? 0 : ncell * 32), crops_at = c.take(dev_out || !crops ? 0 : N * ncell);
+    const size_t bcrops_at = c.take(scratch_crops ? (size_t)batch * local_crop_stride(n, false) : 0);
+    const size_t ncellp = local_cells_padded(n), groups = (size_t)local_groups(batch);
+    const size_t pw_at = c.take(fuse ? groups * ncellp * 12 : 0), pv_at = c.take(fuse ? groups * ncellp * 8 : 0);
+    HIP_TRY(h, h->reserve(B_LOCAL, c.total()));
+    const Block& d = h->buf[B_LOCAL];
+    Staging& st = h->stage[S_LOCAL];
+    HIP_TRY(h, st.begin(in_b));                                            // the last upload may still read it
+    stage_pose4(st.as<double>(pose_at), poses_n3, N);
+    memcpy(st.p + gx_at, lp.gx.data(), nq * 8);
+    memcpy(st.p + gy_at, lp.gy.data(), nq * 8);
+    uint32_t* w = st.as<uint32_t>(wq_at);
+    for (size_t k = 0; k < N; ++k) w[k] = wq ? wq[k] : 1u;
+    HIP_TRY(h, st.upload(d.p, in_b, h->stream));
+    LocalArgs a;
+    a.pose4 = d.as<const double>(pose_at); a.gx = d.as<const double>(gx_at); a.gy = d.as<const double>(gy_at); a.wq = d.as<const uint32_t>(wq_at);
+    a.n = n; a.S = samples; a.nq = lp.nq;
+    a.reach = (int)lp.reach; a.side = lp.side; a.row_bytes = local_row_bytes(lp.side); a.tab_lds = local_tables_fit(lp.side, lp.nq);
+    a.particle = particle; a.off = v.R * v.dim + v.dim / 2; a.inv = inv;
+    int8_t* all_crops = !crops ? nullptr : dev_out ? crops : d.as<int8_t>(crops_at);   // [n_poses][n][n], dense
+    a.cstride = local_crop_stride(n, !scratch_crops);
+    a.ncellp = ncellp;
+    a.part_w = d.as<uint32_t>(pw_at); a.part_v = d.as<long long>(pv_at);
+    a.fused = !fuse ? nullptr : dev_out ? reinterpret_cast<long long*>(fused) : d.as<long long>(fused_at);
+    if (fuse) HIP_TRY(h, hipMemsetAsync(a.fused, 0, ncell * 32, h->stream));
+    for (long long p0 = 0; p0 < n_poses; p0 += batch) {
+        a.p0 = (int)p0; a.nb = (int)std::min<long long>(batch, n_poses - p0);
+        a.crops = all_crops ? all_crops + (size_t)p0 * ncell : d.as<int8_t>(bcrops_at);
+        a.wide = a.cstride % 16 == 0 && reinterpret_cast<uintptr_t>(a.crops) % 16 == 0;
+        a.ngroups = (int)local_groups(a.nb);
+        launch_local_crop(v, a, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        if (fuse) {
+            launch_local_fuse(v, a, h->stream);
+            HIP_TRY(h, hipGetLastError());
+        }
+    }
+    return dev_out ? RBPF_OK : fetch(h, {{fused, a.fused, ncell * 32}, {crops, all_crops, N * ncell}});
 }
 
 // ---- frontier regions (kernels_frontier.hip) ----------------------------------------------------------------------------------

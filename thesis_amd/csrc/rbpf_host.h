@@ -60,6 +60,7 @@ enum {
     B_SCANCHECK,                    // poses, beams, ranges, cost tables, host outputs
     B_ROLLOUTS,                     // poses, template waypoints, template offsets, host outputs
     B_FOOTPRINTS,                   // poses, pose bins, template waypoints and bins, template offsets, span offsets, spans, host outputs
+    B_LOCAL,                        // poses, sample tables, weights, host outputs, the crops and the group sums of a batch
     B_COUNT
 };
 
@@ -105,6 +106,7 @@ enum {
     S_SCANCHECK,                    // the upload of B_SCANCHECK
     S_ROLLOUTS,                     // the upload of B_ROLLOUTS
     S_FOOTPRINTS,                   // the upload of B_FOOTPRINTS
+    S_LOCAL,                        // the upload of B_LOCAL
     S_COUNT
 };
 
@@ -162,7 +164,7 @@ struct rbpf_handle {
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
                               {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming},
-                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
+                              {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}, {{MEM_PAGEABLE}, hipEventDisableTiming}};
     // grows scratch buffer b; queued work may still read the old block of those from B_DRAIN_FIRST on, so the stream drains first
     hipError_t reserve(int b, size_t bytes) {
         if (buf[b].cap >= bytes) return hipSuccess;

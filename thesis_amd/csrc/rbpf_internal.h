@@ -391,6 +391,27 @@ struct ScanCheckArgs {
     int32_t* votes;                    // [B][8] or null, preset to 0
 };
 
+// local map (kernels_local.hip): an n x n window in the robot's frame cut out of the map of every pose's particle
+// (one workgroup per pose of a batch) and the four integer sums over the poses; the trigonometry and the tables come from the host
+static const int LOCAL_GROUP_POSES = 64;   // poses of one group of the fusion (rbpf_localbatch.h: LOCAL_GROUP)
+struct LocalArgs {
+    const double* pose4;               // [n_poses][4] x, y, cos(theta), sin(theta), of the whole call
+    const double *gx, *gy;             // [nq] sample coordinates in the robot's frame, metres
+    const uint32_t* wq;                // [n_poses] integer weights, of the whole call
+    int n, S, nq;                      // output cells a side, samples a cell and axis, n * S
+    int reach, side, row_bytes;        // the LDS window: half-side, rows 2 reach + 1, bytes of a row (a multiple of 16, >= side + 15)
+    int tab_lds;                       // 1: gx and gy stand in LDS behind the window
+    int particle;                      // >= 0: every pose in this particle's map; -1: pose n in particle n's
+    int off;                           // mosaic cell X + off counts from the lattice's first cell
+    double inv;                        // cells per metre (dim / tile_len)
+    int p0, nb;                        // the batch: its first pose, its poses
+    int8_t* crops; size_t cstride;     // the crop of pose p0 + k: crops + k * cstride, [n][n]
+    int wide;                          // 1: every crop starts on a 16-byte boundary and holds whole 16-byte strips
+    int ngroups; size_t ncellp;        // groups of the batch; n * n rounded up to a multiple of 16
+    uint32_t* part_w; long long* part_v;   // [ngroups][3][ncellp] occ_w, free_w, unknown_w and [ngroups][ncellp] sum_wv of the groups
+    long long* fused;                  // [n][n][4], added to
+};
+
 // frontier regions (kernels_frontier.hip): frontier cells of a box of one particle's map, or of a batch of particles'
 // maps, their connected components and a table of the largest.  Blocks, particles of the batch and box-relative cells as in
 // TravelArgs; the label of a cell is L = i * ny + j.
@@ -550,6 +571,9 @@ void launch_align_points(const DevView& v, const LocateArgs& f, const AlignArgs&
 void launch_check_paths(const DevView& v, const PathArgs& a, hipStream_t s);   // one wave per (particle, path)
 void launch_check_rollouts(const DevView& v, const RolloutArgs& a, hipStream_t s);   // one wave per (pose, template)
 void launch_check_footprints(const DevView& v, const FootArgs& a, hipStream_t s);    // one wave per (pose or particle, template)
+size_t local_lds_bytes(const LocalArgs& a);
+void launch_local_crop(const DevView& v, const LocalArgs& a, hipStream_t s);        // one workgroup per pose of the batch
+void launch_local_fuse(const DevView& v, const LocalArgs& a, hipStream_t s);        // the batch's sums, added into a.fused (preset to 0 before the first)
 void launch_check_scans(const DevView& v, const ScanCheckArgs& a, hipStream_t s);   // a.cost, a.counts and a.votes preset to 0
 void launch_travel_mask(const DevView& v, const TravelArgs& a, hipStream_t s);   // a.ras preset to TRAVEL_INF, a.dirty to 0: clearance, T, the starts
 void launch_travel_round(const TravelArgs& a, int parity, int32_t* d_count, hipStream_t s);   // one round (rbpf_blockrelax.h); d_count[0] += blocks it changed, d_count[32] += blocks that ran

@@ -1085,6 +1085,57 @@ class ParticleEngine:
                                                       out.ptr(res), out.ptr(steps)))
         return PathCheck(res[..., 0], res[..., 1], res[..., 2], res[..., 3], steps, float(self.cfg.tile_len_m) / self.dim, inflate, cmax)
 
+    # -- local map (include/rbpf_hip.h: rbpf_local_map; thesis_amd/local.py) ---------------------------------------
+    def local_map(self, poses=None, particle=None, size_m: float = 6.4, cell: Optional[float] = None, samples: int = 2,
+                  weights="resample", offset=(0.0, 0.0), crops: bool = False, device: bool = False):
+        """What is round the robot, in the robot's frame, fused over the particles: a window of n x n cells of `cell` metres
+        (default: the engine's), n = ceil(size_m / cell), cut out of the map of every pose's particle with the pose at its
+        centre (moved by `offset` = (ahead, left) metres: a look-ahead window) and x forward, then summed with integer weights.
+        `poses` is [N, 3] (or [3]); None: poses().  `particle`: None (pose p in particle p's map, N == P), an index, or "best"
+        (the first argmax of weights()).  A cell of a cut is the largest of samples x samples map values inside it: a wall
+        that crosses the cell keeps it.  `weights`: "resample" (resample_weights of weights(), as estimate() uses), "uniform" /
+        None, or N non-negative values; they pass through local.quantise_weights.  Returns local.LocalMap: occ_w, free_w,
+        unknown_w, sum_wv [n, n] int64 and, with crops=True, every pose's own cut [N, n, n] int8.  device=True: torch tensors
+        on the engine's device, ready for work on torch's current stream."""
+        from .local import LocalMap, quantise_weights
+        from .mapio import resample_weights
+        p = self._particle(particle)
+        ps = _f64(self.poses() if poses is None else poses)
+        if ps.ndim == 1:
+            ps = ps.reshape(1, -1)
+        if ps.ndim != 2 or ps.shape[1] != 3 or ps.shape[0] < 1:
+            raise ValueError("poses must be [N, 3] (or [3]), N >= 1")
+        N = ps.shape[0]
+        cs = float(self.cfg.cell_size if cell is None else cell)
+        if not (np.isfinite(cs) and cs > 0.0 and np.isfinite(float(size_m)) and float(size_m) > 0.0):
+            raise ValueError("size_m and cell must be finite and > 0")
+        n = max(1, int(np.ceil(float(size_m) / cs - 1e-9)))          # 6.4 / 0.05 is 128 whichever way the quotient rounds
+        off = _f64(offset).reshape(-1)
+        if off.shape != (2,):
+            raise ValueError("offset must be (ahead, left) in metres")
+        if weights is None or (isinstance(weights, str) and weights == "uniform"):
+            wq, total = None, N
+        else:
+            if isinstance(weights, str):
+                if weights != "resample":
+                    raise ValueError(f"unknown weights {weights!r}")
+                w = resample_weights(self.weights())
+            else:
+                w = _f64(weights).reshape(-1)
+            if w.shape != (N,):
+                raise ValueError(f"weights must have shape ({N},): one for every pose")
+            wq = np.ascontiguousarray(quantise_weights(w))
+            total = int(wq.sum(dtype=np.uint64))
+        out = self._outputs(device)
+        fused = out.empty((n, n, 4), "int64")
+        cr = out.empty((N, n, n), "int8") if crops else None
+        with out:
+            self._check(self._lib.rbpf_local_map(self._h, p, _dp(ps), N, None if wq is None else wq.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 n, cs, int(samples), _dp(off), _lib.RBPF_LOCAL_DEVICE_OUT if device else 0,
+                                                 out.ptr(fused), out.ptr(cr)))
+        return LocalMap(occ_w=fused[..., 0], free_w=fused[..., 1], unknown_w=fused[..., 2], sum_wv=fused[..., 3], total=total, cell=cs,
+                        offset=(float(off[0]), float(off[1])), crops=cr)
+
     # -- footprint checks (include/rbpf_hip.h: rbpf_check_footprints; DESIGN.md 3.25; thesis_amd/plan.py) -------------------------
     def check_footprints(self, poses, templates, headings, footprint, particle=None, radius_m: float = 0.0, clear_max: Optional[int] = None,
                          through_unknown: bool = False, exempt_cells: Optional[int] = None, device: bool = False):
